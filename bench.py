@@ -8,6 +8,13 @@ A "step" is one frame: one pass of the per-pixel path-trace hot path over the wh
 per pixel) including the running-mean accumulation and, for N>1, the frame-end gather of the tile
 buffers to rank 0 over RCCL.  Scene, cube map and the accumulation image are resident in HBM before
 the timed region starts.  One JSON line is printed by rank 0.
+
+A plain run does only what `value` and `ms_per_step` need: set up, warm up, time the K frames, print the line.
+`--full` adds everything else the line can carry, each with runs of its own: HIP events around the scan
+launches of the timed region (`roofline`, `compute`), a counted frame (`counters_per_frame`), the frame-batched
+region (`frame_batched`) and the CPU baselines.  `--dump-outputs DIR` writes the image the last timed frame left
+(what a caller of the frame loop receives) to DIR/image.npy, float32; above 64 MiB a fixed, seeded sample of
+its pixels goes to DIR/image_sample.npy instead.
 """
 from __future__ import annotations
 
@@ -23,6 +30,22 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: peak FP32 vector
 BF16_DENSE_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: dense bf16 matrix peak (the headline 5 PF figure includes 2:1 sparsity)
+DUMP_LIMIT_BYTES = 64 * 2**20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, image) -> None:
+    """--dump-outputs: the (H, W, 4) float32 image as image.npy, or, when it is larger than DUMP_LIMIT_BYTES, a fixed
+    sample of its pixels (seed 0, in pixel order; the same pixels every run at that size) as image_sample.npy, shape (n, 4)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(dirname, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (px.shape[1] * px.itemsize)
+    pick = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(dirname, "image_sample.npy"), px[pick])
 
 
 def scene_bytes(scene) -> int:
@@ -100,16 +123,22 @@ def main():
     ap.add_argument("--sort-min-rays", type=int, default=None, help="kernel 4, cull 3: a bounce's queue is binned when at least this many rays are expected")
     ap.add_argument("--debug-bounces", type=int, default=None, help="diagnostic: override the bounce limit of the configuration (not the named workload)")
     ap.add_argument("--strip-rows", type=int, default=8, help="rows per interleaved strip (multiple of 8); 8 balances the ranks to +-3%% at N = 8, 16 to +-6%%")
-    ap.add_argument("--timing-period", type=int, default=None, help="frames between kernel-timed frames (default: 4)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel timing, roofline, work counters, the frame-batched region and the CPU "
+                    "baselines (a plain run measures `value` / `ms_per_step` alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed frames, write the image the last one left to DIR/image.npy "
+                    "(float32; above 64 MiB a fixed seeded pixel sample, DIR/image_sample.npy)")
+    ap.add_argument("--timing-period", type=int, default=None, help="with --full: frames between kernel-timed frames (default: 4)")
     ap.add_argument("--frame-batch", type=int, default=1, help="opt-in (rtgl option frame_batch): trace this many consecutive frames in one set of launches; the image "
                     "(and the gather at N > 1) then follows every batch instead of every frame, bit-identical; disables the per-launch kernel timing")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--batched-extra", choices=("auto", "on", "off"), default="auto", help="the second, separately reported region (frame_batch = 8, or 2 x N at N > 4, frames per set "
+    ap.add_argument("--batched-extra", choices=("auto", "on", "off"), default="auto", help="with --full: the second, separately reported region (frame_batch = 8, or 2 x N at N > 4, frames per set "
                     "of launches; reported under `frame_batched`, never as `value`): auto = on; the profiling scripts pass `off` so that a profile holds the launches of the `value` region alone")
     ap.add_argument("--sync-each-frame", action="store_true", help="diagnostic: host waits for every frame")
     ap.add_argument("--no-kernel-timing", action="store_true", help="diagnostic: no HIP events around the scan launches")
     ap.add_argument("--cpu-rows", type=int, default=1080, help="rows of the frame the CPU baseline renders (8-row strips, uniformly strided): 1080 = the whole C2 frame, ~10 s on 16 threads")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # typed without a launcher: start the ranks as a child job (nothing has touched the GPU yet)
         raise SystemExit(relaunch(sys.argv[1:], args.gpus))
@@ -158,13 +187,13 @@ def main():
     if not shared_device:
         ctx.bind_device_image(gat.local.data_ptr())      # render straight into the buffer the gather sends
         ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-    # HIP events around every launch of the dominant kernel, in every 4th frame: each event pair is ~3 us of launch gap, 16 pairs per frame
-    # are 1.4 % of a C2 frame at N = 1 and 7 % of a rank's frame at N = 8
+    # --full: HIP events around every launch of the dominant kernel, in every 4th frame: each event pair is ~3 us of launch gap, 16 pairs per
+    # frame are 1.4 % of a C2 frame at N = 1 and 7 % of a rank's frame at N = 8; a plain run records none
     if args.frame_batch > 1:
         args.no_kernel_timing = True                      # (a context that times its launches renders frame by frame)
         ctx.set_option("frame_batch", args.frame_batch)
         assert args.steps % args.frame_batch == 0, "--steps must be a multiple of --frame-batch"
-    timing_period = 0 if args.no_kernel_timing else (args.timing_period or 4)
+    timing_period = 0 if args.no_kernel_timing or not args.full else (args.timing_period or 4)
     ctx.set_option("kernel_timing", timing_period)
 
     rnd = sc.GlibcRand(0)
@@ -209,7 +238,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     timed_frames = args.steps                              # frames the event timing covers
-    if args.no_kernel_timing:
+    if timing_period == 0:
         frame_ms, scan_ms, scan_launches = dt * 1e3, dt * 1e3, args.steps * base.max_bounce
     else:
         t = ctx.accumulated_timing()                      # HIP events recorded on the launch stream around every scan launch
@@ -220,11 +249,13 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if shared_device else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gat.finish().cpu().numpy())     # the image the last timed frame left, before anything renders again
 
     # A second region, reported beside `value`, never as it: the same workload with 2 x N (at most 16) frames traced per set of launches (option
     # "frame_batch", DESIGN.md 7: bit-identical image; the image -- and at N > 1 the gather -- follows every batch instead of every frame).
     batched = None
-    if args.frame_batch == 1 and args.batched_extra in ("on", "auto") and args.steps >= 8 and not args.sync_each_frame and not shared_device:
+    if args.full and args.frame_batch == 1 and args.batched_extra in ("on", "auto") and args.steps >= 8 and not args.sync_each_frame and not shared_device:
         try:                                               # (whatever happens here must not cost the line its `value`)
             B = min(max(8, 2 * world), 16, args.steps // 8 * 8 if args.steps < 16 else 16)   # eight frames per set of launches (a rank of N > 4: what two whole frames are to a single GPU)
             B = max(B, 2)
@@ -261,82 +292,84 @@ def main():
             ctx.set_option("frame_batch", 1)
             batch_now[0] = 1
 
-    # untimed: work counters of one representative frame (atomics are off in the timed region)
-    ctx.set_option("counters", 1)
-    ctx.render(timed[0].replace(frames=frame_no[0] + 1), sync=True)
-    cnt = ctx.counters()
-    ctx.set_option("counters", 0)
-    if world > 1:
-        ct = torch.tensor([cnt["segments"], cnt["triangle_tests"], cnt["env_lookups"], cnt["paths"], cnt["candidates"], cnt["culled_tests"]],
-                          dtype=torch.float64, device="cpu" if shared_device else dev)
-        dist.all_reduce(ct, op=dist.ReduceOp.SUM)
-        cnt = dict(segments=int(ct[0]), triangle_tests=int(ct[1]), env_lookups=int(ct[2]), paths=int(ct[3]), candidates=int(ct[4]), culled_tests=int(ct[5]))
+    if args.full:
+        # untimed: work counters of one representative frame (atomics are off in the timed region)
+        ctx.set_option("counters", 1)
+        ctx.render(timed[0].replace(frames=frame_no[0] + 1), sync=True)
+        cnt = ctx.counters()
+        ctx.set_option("counters", 0)
+        if world > 1:
+            ct = torch.tensor([cnt["segments"], cnt["triangle_tests"], cnt["env_lookups"], cnt["paths"], cnt["candidates"], cnt["culled_tests"]],
+                              dtype=torch.float64, device="cpu" if shared_device else dev)
+            dist.all_reduce(ct, op=dist.ReduceOp.SUM)
+            cnt = dict(segments=int(ct[0]), triangle_tests=int(ct[1]), env_lookups=int(ct[2]), paths=int(ct[3]), candidates=int(ct[4]), culled_tests=int(ct[5]))
 
     if rank == 0:
         px = (W // 8 * 8) * (H // 8 * 8)
         paths = px * base.samples * args.steps
-        # dominant kernel = the ray x triangle scan (rank 0's launches; its share of the frame is 1/world)
-        share = 1.0 / world
-        alg = algorithmic_bytes(W, H, cnt, scene)
-        launches_per_frame = max(scan_launches // max(timed_frames, 1), 1)
-        avg_launch_s = max(scan_ms, 1e-9) / 1e3 / max(scan_launches, 1)
-        bytes_per_launch = alg["scan"] * share / launches_per_frame
-        if scan_launches == 0:            # a scene without triangles has no scan launches: describe the whole frame instead
-            launches_per_frame, avg_launch_s, bytes_per_launch = 1, frame_ms / 1e3 / max(timed_frames, 1), alg["total"] * share
-        flops_per_launch = cnt["triangle_tests"] * 36.0 * share / launches_per_frame   # 18 fma per edge-function triple
-        kname = {0: "pathtrace_mega_kernel", 1: "bounce_kernel", 2: "intersect_kernel", 4: "scan_solo_kernel"}[ctx.get_option("kernel_in_use")]
-        if scan_launches == 0:
-            kname = "whole frame (generate_rays + shade)"
-        k = ctx.get_option("kernel_in_use")
-        gtests = cnt["triangle_tests"] * share / launches_per_frame / avg_launch_s / 1e9
-        tflops = flops_per_launch / avg_launch_s / 1e12
-        hbm = {"achieved": bytes_per_launch / avg_launch_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-               "frac": bytes_per_launch / avg_launch_s / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": bytes_per_launch,
-               "note": "SURVEY 8(d3) accounting: one scene stream per 256 live rays per bounce; the scene lives in L2/LDS, so this fraction is small by construction"}
-        traffic, traffic_src = None, None
-        tf = os.path.join(ROOT, "profiles", "hbm_traffic.json")     # written by tools/diagnostics/gpu_profile.sh (rocprofv3 PMC passes), keyed "<config>/<kernel>"
-        if os.path.exists(tf) and world == 1:
-            ent = json.load(open(tf)).get(f"{args.config}/{kname}")
-            if ent:
-                traffic, traffic_src = ent["hbm_bytes_per_launch"], f"committed rocprofv3 PMC profile ({ent.get('profile', 'profiles/')}), not measured in this run"
-        if k == 4:
-            # The dominant kernel issues one v_mfma_f32_32x32x16_bf16 (32,768 flop) per 320 ray x triangle tests (10 triangles x 32
-            # rays) plus 8 VALU instructions examining its 16 results.  Matrix and vector instructions share the SIMD's issue port:
-            # the bound is matrix/vector ISSUE, priced against the dense bf16 MFMA peak (one such MFMA per 32 cycles per SIMD).
-            n_simd, clk = 1024.0, 2.4e9
-            products_per_launch = cnt["triangle_tests"] * share / launches_per_frame / 320.0
-            executed_per_launch = (cnt["triangle_tests"] - cnt["culled_tests"]) * share / launches_per_frame / 320.0   # packet culling skips the rest
-            executed_tflops = executed_per_launch * 32768.0 / avg_launch_s / 1e12
-            effective_tflops = products_per_launch * 32768.0 / avg_launch_s / 1e12
-            # matrix-pipe occupancy and shader clock of the same command under rocprofv3 / in the stamps build: committed profile, not this run
-            derived = None
-            df = os.path.join(ROOT, "profiles", "pmc_derived.json")        # tools/diagnostics/summarize_profile.py
-            if os.path.exists(df) and world == 1:
-                derived = json.load(open(df)).get(args.config)
-            roof = {"bound": "mfma", "achieved": executed_tflops, "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": executed_tflops / BF16_DENSE_PEAK_TFLOPS,
-                    "traffic": traffic, "traffic_source": traffic_src, "kernel": kname, "launches_per_frame": launches_per_frame, "avg_launch_ms": avg_launch_s * 1e3,
-                    "definition": "achieved = matrix flops of the v_mfma_f32_32x32x16_bf16 instructions actually ISSUED per launch (32,768 flop per product of 10 triangles x 32 rays; "
-                                  "tests a granule skips because all of its rays are certified rejections are not counted) / average launch duration",
-                    "products_per_launch": executed_per_launch, "culled_fraction": cnt["culled_tests"] / max(cnt["triangle_tests"], 1),
-                    "cycles_per_product": n_simd * clk * avg_launch_s / max(executed_per_launch, 1.0),
-                    "frac_of_mfma_issue_peak": executed_per_launch / avg_launch_s / (n_simd * clk / 32.0),
-                    "issue_floor_cycles_per_product": 44.0,
-                    "mfma_busy": derived,
-                    "effective": {"products_per_launch": products_per_launch, "tflops": effective_tflops, "frac": effective_tflops / BF16_DENSE_PEAK_TFLOPS,
-                                  "cycles_per_product": n_simd * clk * avg_launch_s / max(products_per_launch, 1.0),
-                                  "note": "algorithmic equivalent, NOT an achieved-of-peak figure: every ray x triangle test the reference performs priced as if it had been "
-                                          "multiplied, including the tests packet culling never issues (this can exceed 1)"},
-                    "note": "dominant kernel launch = packet culling (culled bounces) + scan + narrow phase, timed together.  bound = matrix/vector issue of a SIMD: 32 cycles of matrix pipe per product; 44 cycles of issue "
-                            "(MFMA 8 + 9 VALU x 4) measured for the bare instruction stream of one wave, 33 with two waves per SIMD, 38-40 with the loop's scalar instructions (tools/scan_stage_rate.hip); cycles are counted at the "
-                            "nominal 2.4 GHz (the clock the chip holds in this loop: mfma_busy.in_kernel_clock_ghz).  SURVEY 8(d3)'s fp32-VALU and HBM rows are superseded for this kernel (DESIGN.md 6)",
-                    "hbm": hbm}
-            compute = {"pipe": "bf16 MFMA broad phase + fp32 VALU examination (one issue port per SIMD)", "algorithmic_tflops": tflops, "flop_per_test": 36,
-                       "gtests_per_s": gtests, "scan_share_of_frame": scan_ms / max(frame_ms, 1e-9)}
-        else:
-            roof = {"bound": "hbm", "traffic": traffic, "traffic_source": traffic_src, "kernel": kname, "launches_per_frame": launches_per_frame,
-                    "avg_launch_ms": avg_launch_s * 1e3, **hbm}
-            compute = {"pipe": "fp32 VALU", "achieved": tflops, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tflops / FP32_PEAK_TFLOPS,
-                       "flop_per_test": 36, "gtests_per_s": gtests, "scan_share_of_frame": scan_ms / max(frame_ms, 1e-9)}
+        if args.full:
+            # dominant kernel = the ray x triangle scan (rank 0's launches; its share of the frame is 1/world)
+            share = 1.0 / world
+            alg = algorithmic_bytes(W, H, cnt, scene)
+            launches_per_frame = max(scan_launches // max(timed_frames, 1), 1)
+            avg_launch_s = max(scan_ms, 1e-9) / 1e3 / max(scan_launches, 1)
+            bytes_per_launch = alg["scan"] * share / launches_per_frame
+            if scan_launches == 0:            # a scene without triangles has no scan launches: describe the whole frame instead
+                launches_per_frame, avg_launch_s, bytes_per_launch = 1, frame_ms / 1e3 / max(timed_frames, 1), alg["total"] * share
+            flops_per_launch = cnt["triangle_tests"] * 36.0 * share / launches_per_frame   # 18 fma per edge-function triple
+            kname = {0: "pathtrace_mega_kernel", 1: "bounce_kernel", 2: "intersect_kernel", 4: "scan_solo_kernel"}[ctx.get_option("kernel_in_use")]
+            if scan_launches == 0:
+                kname = "whole frame (generate_rays + shade)"
+            k = ctx.get_option("kernel_in_use")
+            gtests = cnt["triangle_tests"] * share / launches_per_frame / avg_launch_s / 1e9
+            tflops = flops_per_launch / avg_launch_s / 1e12
+            hbm = {"achieved": bytes_per_launch / avg_launch_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                   "frac": bytes_per_launch / avg_launch_s / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": bytes_per_launch,
+                   "note": "SURVEY 8(d3) accounting: one scene stream per 256 live rays per bounce; the scene lives in L2/LDS, so this fraction is small by construction"}
+            traffic, traffic_src = None, None
+            tf = os.path.join(ROOT, "profiles", "hbm_traffic.json")     # written by tools/diagnostics/gpu_profile.sh (rocprofv3 PMC passes), keyed "<config>/<kernel>"
+            if os.path.exists(tf) and world == 1:
+                ent = json.load(open(tf)).get(f"{args.config}/{kname}")
+                if ent:
+                    traffic, traffic_src = ent["hbm_bytes_per_launch"], f"committed rocprofv3 PMC profile ({ent.get('profile', 'profiles/')}), not measured in this run"
+            if k == 4:
+                # The dominant kernel issues one v_mfma_f32_32x32x16_bf16 (32,768 flop) per 320 ray x triangle tests (10 triangles x 32
+                # rays) plus 8 VALU instructions examining its 16 results.  Matrix and vector instructions share the SIMD's issue port:
+                # the bound is matrix/vector ISSUE, priced against the dense bf16 MFMA peak (one such MFMA per 32 cycles per SIMD).
+                n_simd, clk = 1024.0, 2.4e9
+                products_per_launch = cnt["triangle_tests"] * share / launches_per_frame / 320.0
+                executed_per_launch = (cnt["triangle_tests"] - cnt["culled_tests"]) * share / launches_per_frame / 320.0   # packet culling skips the rest
+                executed_tflops = executed_per_launch * 32768.0 / avg_launch_s / 1e12
+                effective_tflops = products_per_launch * 32768.0 / avg_launch_s / 1e12
+                # matrix-pipe occupancy and shader clock of the same command under rocprofv3 / in the stamps build: committed profile, not this run
+                derived = None
+                df = os.path.join(ROOT, "profiles", "pmc_derived.json")        # tools/diagnostics/summarize_profile.py
+                if os.path.exists(df) and world == 1:
+                    derived = json.load(open(df)).get(args.config)
+                roof = {"bound": "mfma", "achieved": executed_tflops, "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": executed_tflops / BF16_DENSE_PEAK_TFLOPS,
+                        "traffic": traffic, "traffic_source": traffic_src, "kernel": kname, "launches_per_frame": launches_per_frame, "avg_launch_ms": avg_launch_s * 1e3,
+                        "definition": "achieved = matrix flops of the v_mfma_f32_32x32x16_bf16 instructions actually ISSUED per launch (32,768 flop per product of 10 triangles x 32 rays; "
+                                      "tests a granule skips because all of its rays are certified rejections are not counted) / average launch duration",
+                        "products_per_launch": executed_per_launch, "culled_fraction": cnt["culled_tests"] / max(cnt["triangle_tests"], 1),
+                        "cycles_per_product": n_simd * clk * avg_launch_s / max(executed_per_launch, 1.0),
+                        "frac_of_mfma_issue_peak": executed_per_launch / avg_launch_s / (n_simd * clk / 32.0),
+                        "issue_floor_cycles_per_product": 44.0,
+                        "mfma_busy": derived,
+                        "effective": {"products_per_launch": products_per_launch, "tflops": effective_tflops, "frac": effective_tflops / BF16_DENSE_PEAK_TFLOPS,
+                                      "cycles_per_product": n_simd * clk * avg_launch_s / max(products_per_launch, 1.0),
+                                      "note": "algorithmic equivalent, NOT an achieved-of-peak figure: every ray x triangle test the reference performs priced as if it had been "
+                                              "multiplied, including the tests packet culling never issues (this can exceed 1)"},
+                        "note": "dominant kernel launch = packet culling (culled bounces) + scan + narrow phase, timed together.  bound = matrix/vector issue of a SIMD: 32 cycles of matrix pipe per product; 44 cycles of issue "
+                                "(MFMA 8 + 9 VALU x 4) measured for the bare instruction stream of one wave, 33 with two waves per SIMD, 38-40 with the loop's scalar instructions (tools/scan_stage_rate.hip); cycles are counted at the "
+                                "nominal 2.4 GHz (the clock the chip holds in this loop: mfma_busy.in_kernel_clock_ghz).  SURVEY 8(d3)'s fp32-VALU and HBM rows are superseded for this kernel (DESIGN.md 6)",
+                        "hbm": hbm}
+                compute = {"pipe": "bf16 MFMA broad phase + fp32 VALU examination (one issue port per SIMD)", "algorithmic_tflops": tflops, "flop_per_test": 36,
+                           "gtests_per_s": gtests, "scan_share_of_frame": scan_ms / max(frame_ms, 1e-9)}
+            else:
+                roof = {"bound": "hbm", "traffic": traffic, "traffic_source": traffic_src, "kernel": kname, "launches_per_frame": launches_per_frame,
+                        "avg_launch_ms": avg_launch_s * 1e3, **hbm}
+                compute = {"pipe": "fp32 VALU", "achieved": tflops, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tflops / FP32_PEAK_TFLOPS,
+                           "flop_per_test": 36, "gtests_per_s": gtests, "scan_share_of_frame": scan_ms / max(frame_ms, 1e-9)}
         out = {
             "metric": "Mpaths/s at 1920x1080, 8 bounces, 10k tris" if args.config == "C2" else f"Mpaths/s ({args.config})",
             "value": paths / dt / 1e6, "unit": "Mpaths/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -349,13 +382,12 @@ def main():
                        "frame_batch": args.frame_batch,
                        "kernel": ctx.get_option("kernel_in_use"), "wf_rays": ctx.get_option("wf_rays"), "wf_mode": ctx.get_option("wf_mode"), "wf_chunk": ctx.get_option("wf_chunk"), "wf_early": ctx.get_option("wf_early"), "wf_packed": ctx.get_option("wf_packed"),
                        "mf_sets": ctx.get_option("mf_sets"), "mf_group_quads": ctx.get_option("mf_group_quads"), "mf_chunk_quads": ctx.get_option("mf_chunk_quads")},
-            "roofline": roof,
-            "compute": compute,
-            "counters_per_frame": cnt,
         }
+        if args.full:
+            out.update(roofline=roof, compute=compute, counters_per_frame=cnt)
         if batched:
             out["frame_batched"] = batched
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(rt, scene, timed[0], W, H, args.cpu_rows)
             # the reference itself cannot travel to the GPU box: its llvmpipe timing is measured in the build container by
             # oracle/time_reference.py and carried here as a second, stated baseline

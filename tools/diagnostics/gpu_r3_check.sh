@@ -1,16 +1,17 @@
 # round-3 check: GPU test suite, then the bench line of C2 / C4 / C5 (short)
 set -e
-mkdir -p gpurun_out
+export OUT=${OUT:-build/diagnostics}    # where the logs and bench lines go
+mkdir -p "$OUT"
 make -s -C oracle liboracle.so
-timeout -k 10 1100 python -m pytest tests -m gpu -x -q > gpurun_out/r3_pytest.log 2>&1 || (tail -40 gpurun_out/r3_pytest.log; exit 1)
-tail -2 gpurun_out/r3_pytest.log
-timeout -k 10 300 python bench.py --steps 200 --warmup 10 --no-cpu-baseline > gpurun_out/r3_bench_C2.json 2> gpurun_out/r3_bench_C2.err || (tail -5 gpurun_out/r3_bench_C2.err; exit 1)
+timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $OUT/r3_pytest.log 2>&1 || (tail -40 $OUT/r3_pytest.log; exit 1)
+tail -2 $OUT/r3_pytest.log
+timeout -k 10 300 python bench.py --steps 200 --warmup 10 --no-cpu-baseline --full > $OUT/r3_bench_C2.json 2> $OUT/r3_bench_C2.err || (tail -5 $OUT/r3_bench_C2.err; exit 1)
 for c in C4 C5; do
-timeout -k 10 300 python bench.py --config $c --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/r3_bench_$c.json 2> gpurun_out/r3_bench_$c.err || (tail -5 gpurun_out/r3_bench_$c.err; exit 1)
+timeout -k 10 300 python bench.py --config $c --steps 30 --warmup 5 --no-cpu-baseline --full > $OUT/r3_bench_$c.json 2> $OUT/r3_bench_$c.err || (tail -5 $OUT/r3_bench_$c.err; exit 1)
 done
 python - <<'PY'
-import json
+import json, os
 for n in ("C2","C4","C5"):
-    d=json.load(open(f"gpurun_out/r3_bench_{n}.json")); r=d["roofline"]; cn=d["counters_per_frame"]
+    d=json.load(open(f"{os.environ['OUT']}/r3_bench_{n}.json")); r=d["roofline"]; cn=d["counters_per_frame"]
     print(n, round(d["value"],2), "Mpaths/s", round(d["ms_per_step"],3), "ms", "scan launch ms", round(r["avg_launch_ms"],4), "frac (executed)", round(r["frac"],4), "culled", round(cn.get("culled_tests",0)/max(cn["triangle_tests"],1),4), "cand", cn["candidates"])
 PY
