@@ -247,7 +247,9 @@ __device__ __forceinline__ float mf_margin(const MfGroup &G, float ncv, float no
 //       |w - W| <= ro + Rc + sigma |O - C| =: slack,   W = D x (O - C);     |w_p| >= sqrt(|W|^2 - M^2) - slack,  M >= max |W.n^|.
 // Degenerate or non-finite triangles, or normals spread over more than ~84 degrees, make the record unusable (Nmin = 0: every
 // comparison fails, the tile is scanned).  The theory is tested on the CPU against the reference's own fp32 test
-// (tests/test_cull_certificate.py restates the record and the three certificates in numpy).
+// (tests/test_cull_certificate.py restates the record and the three certificates in numpy).  The same record over the union of a NODE
+// of 4, 16 or 64 consecutive tiles (a subtree of the k-d storage order) certifies all of them at once (packet_cull_kernel, pass 1;
+// tests/test_cull_node_certificate.py).
 struct alignas(16) MfCull {
     float cx, cy, cz, R;          // bounding sphere of the tile's vertices
     float ax, ay, az, Rc;         // axis of the normals; radius of the centroids about (cx, cy, cz)
@@ -262,75 +264,119 @@ static_assert(sizeof(MfCull) == 112, "seven uint4 per tile");
 
 __device__ __forceinline__ float wave_sum(float x) { for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off); return x; }
 
-// one wave per tile, one lane per triangle (storage order)
+// One wave per record.  A record covers `rec_tris` consecutive triangles of the storage order: a tile (10, one lane per triangle) or a
+// node of 4, 16 or 64 tiles (packet_cull_kernel, pass 1), whose lanes take every 64th triangle.  A node record is the tile record of
+// the union: every bound below is a min or a max over the set (or, for the frame of the normals, any frame that holds them all), so
+// the certificates' derivation carries over unchanged.  For a tile each lane holds at most one triangle and the
+// result is what one lane per triangle computes.
+struct CullTri { f3 w[3]; };
+__device__ __forceinline__ CullTri cull_tri_at(const float4 *__restrict__ vertices, const uint32_t *__restrict__ visit_tri, const uint32_t *__restrict__ order, uint32_t pos)
+{
+    CullTri t;
+    const uint32_t tri = visit_tri[order[pos]];
+    for (int k = 0; k < 3; ++k) { const float4 p = vertices[3 * (size_t)tri + k]; t.w[k] = mk(p.x, p.y, p.z); }
+    return t;
+}
+__device__ __forceinline__ f3 cull_unit_normal(const CullTri &t, float *nn_out)
+{
+    const f3 e0 = t.w[1] - t.w[0], e2 = t.w[0] - t.w[2];
+    const f3 N = cross3(e0, mk(-e2.x, -e2.y, -e2.z));                        // (v1 - v0) x (v2 - v0)
+    const float nn = __builtin_sqrtf(dot3(N, N));
+    if (nn_out) *nn_out = nn;
+    return (nn > 0.0f) ? mk(N.x / nn, N.y / nn, N.z / nn) : mk(0.0f, 0.0f, 0.0f);
+}
+
 __global__ void __launch_bounds__(64) prepare_cull_kernel(const float4 *__restrict__ vertices, const uint32_t *__restrict__ visit_tri,
-                                                          const uint32_t *__restrict__ order, uint32_t n_visits, uint32_t n_tiles, MfCull *__restrict__ out)
+                                                          const uint32_t *__restrict__ order, uint32_t n_visits, uint32_t n_recs, uint32_t rec_tris,
+                                                          MfCull *__restrict__ out)
 {
     const uint32_t q = blockIdx.x, lane = threadIdx.x;
-    if (q >= n_tiles) return;
-    const uint32_t pos = q * kMfTileTris + lane;
-    const bool have = lane < (uint32_t)kMfTileTris && pos < n_visits;
+    if (q >= n_recs) return;
+    const uint64_t p_begin = (uint64_t)q * rec_tris, p_end = min(p_begin + rec_tris, (uint64_t)n_visits);
     const float inf = __builtin_inff();
-    f3 w[3] = {mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f)};
-    if (have) { const uint32_t tri = visit_tri[order[pos]]; for (int k = 0; k < 3; ++k) { const float4 p = vertices[3 * (size_t)tri + k]; w[k] = mk(p.x, p.y, p.z); } }
+    // (every pass below reads the lane's triangles again: an upload-time kernel)
     f3 lo = mk(inf, inf, inf), hi = mk(-inf, -inf, -inf);
     bool bad = false;
-    if (have) for (int k = 0; k < 3; ++k) {
-        lo = mk(fminf(lo.x, w[k].x), fminf(lo.y, w[k].y), fminf(lo.z, w[k].z));
-        hi = mk(fmaxf(hi.x, w[k].x), fmaxf(hi.y, w[k].y), fmaxf(hi.z, w[k].z));
-        bad |= !(fabsf(w[k].x) < 1e18f) || !(fabsf(w[k].y) < 1e18f) || !(fabsf(w[k].z) < 1e18f);
+    for (uint64_t p = p_begin + lane; p < p_end; p += 64u) {
+        const CullTri t = cull_tri_at(vertices, visit_tri, order, (uint32_t)p);
+        for (int k = 0; k < 3; ++k) {
+            lo = mk(fminf(lo.x, t.w[k].x), fminf(lo.y, t.w[k].y), fminf(lo.z, t.w[k].z));
+            hi = mk(fmaxf(hi.x, t.w[k].x), fmaxf(hi.y, t.w[k].y), fmaxf(hi.z, t.w[k].z));
+            bad |= !(fabsf(t.w[k].x) < 1e18f) || !(fabsf(t.w[k].y) < 1e18f) || !(fabsf(t.w[k].z) < 1e18f);
+        }
     }
     lo = mk(wave_min(lo.x), wave_min(lo.y), wave_min(lo.z));
     hi = mk(wave_max(hi.x), wave_max(hi.y), wave_max(hi.z));
     const f3 c = mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z);
     float R = 0.0f, Rc = 0.0f, E = 0.0f, Pw = 0.0f, Nmin = inf, shape = inf, hmin = inf;
-    f3 nh = mk(0.0f, 0.0f, 0.0f);
-    if (have) {
+    f3 nsum = mk(0.0f, 0.0f, 0.0f);
+    bool nan_normal = false;
+    for (uint64_t p = p_begin + lane; p < p_end; p += 64u) {
+        const CullTri t = cull_tri_at(vertices, visit_tri, order, (uint32_t)p);
+        const f3 *w = t.w;
         const f3 e0 = w[1] - w[0], e1 = w[2] - w[1], e2 = w[0] - w[2];
-        const f3 N = cross3(e0, mk(-e2.x, -e2.y, -e2.z));                    // (v1 - v0) x (v2 - v0)
-        const float nn = __builtin_sqrtf(dot3(N, N));
+        float nn;
+        const f3 nh = cull_unit_normal(t, &nn);
         const float l0 = __builtin_sqrtf(dot3(e0, e0)), l1 = __builtin_sqrtf(dot3(e1, e1)), l2 = __builtin_sqrtf(dot3(e2, e2));
         for (int k = 0; k < 3; ++k) { const f3 r = w[k] - c; R = fmaxf(R, __builtin_sqrtf(dot3(r, r))); }
         { const f3 g = mk((w[0].x + w[1].x + w[2].x) * (1.0f / 3.0f), (w[0].y + w[1].y + w[2].y) * (1.0f / 3.0f), (w[0].z + w[1].z + w[2].z) * (1.0f / 3.0f)) - c;
-          Rc = __builtin_sqrtf(dot3(g, g)); }
-        E = fmaxf(l0, fmaxf(l1, l2));
+          Rc = fmaxf(Rc, __builtin_sqrtf(dot3(g, g))); }
+        const float El = fmaxf(l0, fmaxf(l1, l2));
+        E = fmaxf(E, El);
         const float a0 = __builtin_sqrtf(dot3(w[0], w[0])), a1 = __builtin_sqrtf(dot3(w[1], w[1])), a2 = __builtin_sqrtf(dot3(w[2], w[2]));
-        Pw = fmaxf(a0 * a1, fmaxf(a1 * a2, a2 * a0));
-        Nmin = nn;
-        nh = (nn > 0.0f) ? mk(N.x / nn, N.y / nn, N.z / nn) : mk(0.0f, 0.0f, 0.0f);
+        Pw = fmaxf(Pw, fmaxf(a0 * a1, fmaxf(a1 * a2, a2 * a0)));
+        Nmin = fminf(Nmin, nn);
+        nan_normal |= !(nh.x == nh.x && nh.y == nh.y && nh.z == nh.z);
         // smallest interior angle: cos at the vertex between the two edges leaving it; sin(angle / 2) = sqrt((1 - cos) / 2)
         const float c0 = -dot3(e0, e2) / (l0 * l2), c1 = -dot3(e1, e0) / (l1 * l0), c2 = -dot3(e2, e1) / (l2 * l1);
         const float cmax = fminf(1.0f, fmaxf(c0, fmaxf(c1, c2)));
         const float s = __builtin_sqrtf(fmaxf(0.0f, 0.5f * (1.0f - cmax)));
         const float lmin = fminf(l0, fminf(l1, l2));
-        shape = (nn > 0.0f) ? 0.999f * s * lmin / nn : 0.0f;                 // s / h_max, h_max = |N| / shortest edge
-        if (!(shape == shape)) shape = 0.0f;
-        hmin = (E > 0.0f) ? 0.999f * nn / E : 0.0f;                          // smallest altitude = |N| / longest edge
-        if (!(hmin == hmin)) hmin = 0.0f;
+        float sh = (nn > 0.0f) ? 0.999f * s * lmin / nn : 0.0f;               // s / h_max, h_max = |N| / shortest edge
+        if (!(sh == sh)) sh = 0.0f;
+        float hm = (El > 0.0f) ? 0.999f * nn / El : 0.0f;                      // smallest altitude = |N| / longest edge
+        if (!(hm == hm)) hm = 0.0f;
+        shape = fminf(shape, sh); hmin = fminf(hmin, hm);
+        nsum = mk(nsum.x + nh.x, nsum.y + nh.y, nsum.z + nh.z);
     }
     R = wave_max(R); Rc = wave_max(Rc); E = wave_max(E); Pw = wave_max(Pw); Nmin = wave_min(Nmin); shape = wave_min(shape); hmin = wave_min(hmin);
-    bad = __any(bad) || __any(have && !(nh.x == nh.x && nh.y == nh.y && nh.z == nh.z));
+    bad = __any(bad) || __any(nan_normal);
     // axis of the normals: their normalised sum
-    f3 a = mk(wave_sum(have ? nh.x : 0.0f), wave_sum(have ? nh.y : 0.0f), wave_sum(have ? nh.z : 0.0f));
+    f3 a = mk(wave_sum(nsum.x), wave_sum(nsum.y), wave_sum(nsum.z));
     const float al = __builtin_sqrtf(dot3(a, a));
     a = (al > 0.0f) ? mk(a.x / al, a.y / al, a.z / al) : mk(0.0f, 0.0f, 1.0f);
-    const float ca = have ? dot3(nh, a) : 1.0f;
-    bad |= !(al > 0.0f) || __any(have && !(ca > 0.1f));                       // normals spread over more than ~84 degrees: no rectangle
     // gnomonic coordinates of the normals in a first tangent basis (b1, b2); t1 = the principal axis of their second moments
     const f3 ref = (fabsf(a.x) < 0.7f) ? mk(1.0f, 0.0f, 0.0f) : mk(0.0f, 1.0f, 0.0f);
     f3 b1 = cross3(a, ref);
     { const float bl = __builtin_sqrtf(dot3(b1, b1)); b1 = mk(b1.x / bl, b1.y / bl, b1.z / bl); }
     const f3 b2 = cross3(a, b1);
-    const float ica = 1.0f / fmaxf(ca, 0.1f);
-    const float gu = have ? dot3(nh, b1) * ica : 0.0f, gv = have ? dot3(nh, b2) * ica : 0.0f;
-    const float suu = wave_sum(gu * gu), suv = wave_sum(gu * gv), svv = wave_sum(gv * gv);
+    bool spread = false;
+    float suu = 0.0f, suv = 0.0f, svv = 0.0f;
+    for (uint64_t p = p_begin + lane; p < p_end; p += 64u) {
+        const CullTri t = cull_tri_at(vertices, visit_tri, order, (uint32_t)p);
+        const f3 nh = cull_unit_normal(t, nullptr);
+        const float ca = dot3(nh, a);
+        spread |= !(ca > 0.1f);                                               // normals spread over more than ~84 degrees: no rectangle
+        const float ica = 1.0f / fmaxf(ca, 0.1f);
+        const float gu = dot3(nh, b1) * ica, gv = dot3(nh, b2) * ica;
+        suu += gu * gu; suv += gu * gv; svv += gv * gv;
+    }
+    bad |= !(al > 0.0f) || __any(spread);
+    suu = wave_sum(suu); suv = wave_sum(suv); svv = wave_sum(svv);
     const float phi = 0.5f * atan2f(2.0f * suv, suu - svv);                  // (any frame is valid: only the tightness of the rectangle depends on phi)
     const float cp = cosf(phi), sp = sinf(phi);
     f3 t1 = mk(cp * b1.x + sp * b2.x, cp * b1.y + sp * b2.y, cp * b1.z + sp * b2.z);
     { const float tl = __builtin_sqrtf(dot3(t1, t1)); t1 = mk(t1.x / tl, t1.y / tl, t1.z / tl); }
     f3 t2 = cross3(a, t1);
     { const float tl = __builtin_sqrtf(dot3(t2, t2)); t2 = mk(t2.x / tl, t2.y / tl, t2.z / tl); }
-    const float X = wave_max(have ? fabsf(dot3(nh, t1) * ica) : 0.0f), Y = wave_max(have ? fabsf(dot3(nh, t2) * ica) : 0.0f);
+    float X = 0.0f, Y = 0.0f;
+    for (uint64_t p = p_begin + lane; p < p_end; p += 64u) {
+        const CullTri t = cull_tri_at(vertices, visit_tri, order, (uint32_t)p);
+        const f3 nh = cull_unit_normal(t, nullptr);
+        const float ica = 1.0f / fmaxf(dot3(nh, a), 0.1f);
+        X = fmaxf(X, fabsf(dot3(nh, t1) * ica)); Y = fmaxf(Y, fabsf(dot3(nh, t2) * ica));
+    }
+    X = wave_max(X); Y = wave_max(Y);
     if (lane != 0) return;
     MfCull rec;
     rec.cx = c.x; rec.cy = c.y; rec.cz = c.z; rec.R = R * 1.0001f + 1e-30f;

@@ -197,7 +197,7 @@ struct rtgl_context {
 
     // bounce-wavefront pipeline buffers
     float2 *d_group_bounds = nullptr;
-    MfGroup *d_mf_groups = nullptr; MfCull *d_mf_cull = nullptr; uint4 *d_mf_A = nullptr; uint32_t *d_mf_order = nullptr; uint32_t n_mf_groups = 0, mf_group_quads = 32; uint32_t *d_dbg_log = nullptr;   // bf16 matrix-core broad phase
+    MfGroup *d_mf_groups = nullptr; MfCull *d_mf_cull = nullptr; MfCull *d_mf_cull_node = nullptr; uint32_t cull_node_shift = 0; uint4 *d_mf_A = nullptr; uint32_t *d_mf_order = nullptr; uint32_t n_mf_groups = 0, mf_group_quads = 32; uint32_t *d_dbg_log = nullptr;   // bf16 matrix-core broad phase
     void *d_wave = nullptr; size_t wave_capacity = 0; bool wave_multi = false;   // queues (+ per-pixel state when u_samples > 1)
     uint32_t *d_counts = nullptr; uint32_t counts_capacity = 0;
     uint32_t *h_counts = nullptr;            // pinned: ray counts per bounce of the most recent finished frame
@@ -434,7 +434,7 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
 #endif
     void *ptrs[] = { ctx->d_spheres, ctx->d_materials, ctx->d_vertices, ctx->d_sphere_visits, ctx->d_edges, ctx->d_planes,
                      ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
-                     ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad };
+                     ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -745,6 +745,15 @@ static std::vector<uint32_t> kd_order(const rtgl_context *ctx, const std::vector
     return order;
 }
 
+// Packet culling in nodes of 4, 16 or 64 tiles (rt_scan.hpp, packet_cull_kernel) or tile by tile (0).  Tuning switch RTGL_AMD_CULL_NODE =
+// 0 or the node size; other sizes are taken to the nearest valid one.  Read when the triangles are uploaded (the node records are built then).
+static uint32_t cull_node_shift_option()
+{
+    uint32_t shift = 4;
+    if (const char *e = getenv("RTGL_AMD_CULL_NODE")) { const long v = atol(e); shift = v <= 0 ? 0u : v <= 8 ? 2u : v <= 32 ? 4u : 6u; }      // (tuning)
+    return shift;
+}
+
 static int rebuild_triangles(rtgl_context *ctx)
 {
     std::vector<uint32_t> visit_tri;
@@ -788,6 +797,7 @@ static int rebuild_triangles(rtgl_context *ctx)
         if (ctx->d_mf_A) { HIPCHK(ctx, hipFree(ctx->d_mf_A)); ctx->d_mf_A = nullptr; }
         if (ctx->d_mf_order) { HIPCHK(ctx, hipFree(ctx->d_mf_order)); ctx->d_mf_order = nullptr; }
         if (ctx->d_mf_cull) { HIPCHK(ctx, hipFree(ctx->d_mf_cull)); ctx->d_mf_cull = nullptr; }
+        if (ctx->d_mf_cull_node) { HIPCHK(ctx, hipFree(ctx->d_mf_cull_node)); ctx->d_mf_cull_node = nullptr; }
         if (ctx->d_edges_s) { HIPCHK(ctx, hipFree(ctx->d_edges_s)); ctx->d_edges_s = nullptr; }
         if (ctx->d_planes_s) { HIPCHK(ctx, hipFree(ctx->d_planes_s)); ctx->d_planes_s = nullptr; }
         // quads sharing one local origin: 32 (= a chunk: one ray set-up per work item of the scan) unless the caller chose.  Smaller
@@ -816,8 +826,17 @@ static int rebuild_triangles(rtgl_context *ctx)
         HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_cull, (size_t)n_tiles_alloc * sizeof(MfCull)));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_mf_cull, 0, (size_t)n_tiles_alloc * sizeof(MfCull), ctx->stream));
         hipLaunchKernelGGL(prepare_cull_kernel, dim3(n_tiles_all), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
-                           ctx->d_mf_order, ctx->n_tri_visits, n_tiles_all, ctx->d_mf_cull);
+                           ctx->d_mf_order, ctx->n_tri_visits, n_tiles_all, (uint32_t)kMfTileTris, ctx->d_mf_cull);
         HIPCHK(ctx, hipGetLastError());
+        // ... and one per node of 2^cull_node_shift consecutive tiles (packet_cull_kernel, pass 1)
+        ctx->cull_node_shift = cull_node_shift_option();
+        if (ctx->cull_node_shift) {
+            const uint32_t n_nodes_all = (n_tiles_all + (1u << ctx->cull_node_shift) - 1u) >> ctx->cull_node_shift;
+            HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_cull_node, (size_t)n_nodes_all * sizeof(MfCull)));
+            hipLaunchKernelGGL(prepare_cull_kernel, dim3(n_nodes_all), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
+                               ctx->d_mf_order, ctx->n_tri_visits, n_nodes_all, (uint32_t)kMfTileTris << ctx->cull_node_shift, ctx->d_mf_cull_node);
+            HIPCHK(ctx, hipGetLastError());
+        }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipFree(d_visit));
     } else ctx->n_mf_groups = 0;
@@ -1127,7 +1146,8 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
             if (!have_bits) { ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_params = *cam; }
         } else { ctx->wb.keep = ctx->d_keep; ro_add = sigma_add = 0.0f; }
         if (!have_bits)
-        hipLaunchKernelGGL(packet_cull_kernel, dim3(std::max(1u, std::min((est_gran + 3u) / 4u, 8192u))), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add);
+        hipLaunchKernelGGL(packet_cull_kernel, dim3(std::max(1u, std::min((est_gran + 3u) / 4u, 8192u))), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
+                           ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u);
         if (dist == 2) {
             // planned: cost prefix sums per chunk [chunks x stride u32][chunks totals u32][chunks + 1 starts u64]
             const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
