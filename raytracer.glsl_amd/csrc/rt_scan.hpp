@@ -96,8 +96,12 @@ __device__ __forceinline__ bool cull_lane(const MfCull &c, bool have, const MfPa
     return skip;
 }
 
-__global__ void __launch_bounds__(256) packet_cull_kernel(WaveBuffers wb, const MfCull *__restrict__ cull, uint32_t n_tiles, uint32_t bounce, float ro_add, float sigma_add,
-                                                          const MfCull *__restrict__ node, uint32_t node_shift)
+// gather (a binned queue under RTGL_AMD_SORT_MOVE = 1): the queue's rays still wait in the staging queue; the slot of each is in
+// wb.sort_src (sort_place_kernel).  The load of the granule fetches them from there and writes all five streams of the queue, coalesced.
+// This is the first kernel to read a binned queue (the bounds need only `a` and `b`; the scan, the narrow phase and shade come after).
+// (five waves per SIMD, <= 96 VGPRs, as before the gather: left to itself the compiler took 98 registers for it, i.e. four waves)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) packet_cull_kernel(WaveBuffers wb, const MfCull *__restrict__ cull, uint32_t n_tiles, uint32_t bounce, float ro_add, float sigma_add,
+                                                          const MfCull *__restrict__ node, uint32_t node_shift, uint32_t gather)
 {
     __shared__ uint32_t s_row[4][kCullRowWords];                          // per wave: the keep bits of the batch being assembled
     __shared__ uint32_t s_open[4][64];                                    // per wave: the open nodes of one pass-1 step, compacted
@@ -114,7 +118,20 @@ __global__ void __launch_bounds__(256) packet_cull_kernel(WaveBuffers wb, const 
             valid[k] = slot < n_rays;
             o[k] = mk(0.0f, 0.0f, 0.0f); dh[k] = o[k];
             if (valid[k]) {
-                const float4 a = qin.a[slot], b = qin.b[slot];
+                float4 a, b;
+                const uint32_t from = gather ? wb.sort_src[slot] : n_rays;
+                if (from < n_rays) {
+                    const float4 *const rec = wb.stage + 4u * from;      // (one 64-byte record: one line fetched per ray)
+                    a = rec[0]; b = rec[1];
+                    const float4 c = rec[2];
+                    const uint4 r = *reinterpret_cast<const uint4 *>(rec + 3);
+                    const uint32_t px = wb.stage_pixel[from];
+                    store_through(qin.a + slot, a.x, a.y, a.z, a.w);               // (read by later kernels: rt_wavefront.hpp, store_through)
+                    store_through(qin.b + slot, b.x, b.y, b.z, b.w);
+                    store_through(qin.c + slot, c.x, c.y, c.z, c.w);
+                    store_through(qin.rng + slot, r.x, r.y, r.z, r.w);
+                    store_through(qin.pixel + slot, px);
+                } else { a = qin.a[slot]; b = qin.b[slot]; }
                 o[k] = mk(a.x, a.y, a.z);
                 const f3 d = mk(a.w, b.x, b.y);
                 // (v_rsq_f32, 1 ulp: this feeds bounds that carry 1e-4 relative and 1e-6 absolute slack)

@@ -61,14 +61,18 @@ struct WaveBuffers {
     uint32_t *sched;              // kernel 4: per scan launch (bounce) and chunk the next unclaimed item; zeroed with the ray counts at frame start
     uint32_t sched_stride;        //   entries per bounce
     uint32_t *cand_peak;          // max over the frame's scan waves of the pairs a wave wanted to append (host: sizes the regions)
-    // ray binning (kernel 4, option "cull" = 3): shade_kernel leaves the rays of the next bounce in the staging queue `qt` with a bin key
-    // each, sort_scatter_kernel moves them into the next queue in key order, so that the 128 rays of a granule are neighbours in origin
-    // AND direction and packet culling has something to certify on bounces >= 1.  Queue order never shows in a result: the state of
-    // a path travels with its ray, hits merge by visit index, every pixel has one path per frame.
-    RayQueue qt;                  // staging queue (a third queue)
+    // ray binning (kernel 4, option "cull" = 3): shade_kernel leaves the rays of the next bounce in the staging queue `stage` with a bin key
+    // each, and the rays are moved into the next queue in key order, so that the 128 rays of a granule are neighbours in origin AND
+    // direction and packet culling has something to certify on bounces >= 1.  Queue order never shows in a result: the state of a path
+    // travels with its ray, hits merge by visit index, every pixel has one path per frame.  The move (RTGL_AMD_SORT_MOVE): 1 (default)
+    // sort_place_kernel writes the staging slot of every queue slot to sort_src and packet_cull_kernel gathers the rays from there as
+    // it loads its granules; 0 sort_scatter_kernel scatters the rays themselves.
+    float4 *stage;                // staging queue: per slot one 64-byte record (a, b, c, rng as in RayQueue) -- a gathered ray is one line
+    uint32_t *stage_pixel;        //   ... and its pixel word
     uint2 *sort_kr;               // per staging slot: (bin key, rank inside the bin)
+    uint32_t *sort_src;           // per slot of the binned queue: the staging slot its ray waits in (sort_place_kernel -> packet_cull_kernel)
     uint32_t *sort_hist;          // rays per bin -> first slot of the bin (sort_prefix_kernel); 2^sort_bits entries + one block sum per 4096
-    uint32_t *sort_hist_other;    // the counters of the NEXT binned bounce: sort_scatter_kernel leaves them zero (two sets take turns; no fill launch per bounce)
+    uint32_t *sort_hist_other;    // the counters of the NEXT binned bounce: the move leaves them zero (two sets take turns; no fill launch per bounce)
     uint32_t sort_bits;           // key = direction bin (8 bits: 16 x 16 octahedral cells in Morton order) << 3 sort_ob | origin word (3 sort_ob bits)
     uint32_t sort_ob;
     uint32_t sort_db, sort_T;     // direction cells per axis = 2^sort_db (4); origin cell bits behind the flag
@@ -661,7 +665,7 @@ __global__ void __launch_bounds__(256) intersect_kernel(SceneView sc, WaveBuffer
 // One lane per live ray: sphere scan, pick the nearer hit, material response, termination or
 // compaction into the next queue (wave ballot + prefix popcount, one atomicAdd per wave).
 // kSort: the survivors go to the staging queue with their bin key and their rank inside the bin (one atomic per ray on the bin's
-// counter: the rays of a wave scatter over hundreds of bins); sort_prefix_kernel + sort_scatter_kernel finish the job.
+// counter: the rays of a wave scatter over hundreds of bins); sort_prefix_kernel + sort_place_kernel (or sort_scatter_kernel) finish the job.
 __device__ __forceinline__ uint32_t spread2(uint32_t x)        // 8 bits -> every second bit
 {
     x &= 0xffu; x = (x | (x << 4)) & 0x0f0fu; x = (x | (x << 2)) & 0x3333u; x = (x | (x << 1)) & 0x5555u;
@@ -712,12 +716,15 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
 {
     const uint32_t n_rays = wb.counts[bounce];
     const RayQueue qin = (bounce & 1u) ? wb.q[1] : wb.q[0];
-    const RayQueue qout = kSort ? wb.qt : ((bounce & 1u) ? wb.q[0] : wb.q[1]);
+    const RayQueue qout = (bounce & 1u) ? wb.q[0] : wb.q[1];
     const unsigned long long *best_in = (bounce & 1u) ? wb.best[1] : wb.best[0];
     unsigned long long *best_out = (bounce & 1u) ? wb.best[0] : wb.best[1];
     const bool last_bounce = (bounce + 1u >= P.max_bounce);
     unsigned long long c_env = 0;
     __shared__ uint32_t s_cnt[5];
+    // kSort: the 64-byte staging records of a wave's survivors (WaveBuffers::stage), assembled here and written out as whole lines.  Each
+    // lane storing its own record took four store instructions that each wrote 16 bytes of every 64: shade 320 -> 380 us per C2 frame.
+    __shared__ float4 s_rec[kSort ? 4 * 64 * 4 : 1];
     for (uint32_t blk = blockIdx.x; blk * 256u < n_rays; blk += gridDim.x) {      // grid-stride, see intersect_kernel
     const uint32_t slot = blk * 256u + threadIdx.x;
     const bool valid = slot < n_rays;
@@ -756,9 +763,9 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
         s_cnt[4] = total ? atomicAdd(&wb.counts[bounce + 1u], total) : 0u;
     }
     __syncthreads();
+    uint32_t wave_base = s_cnt[4];
+    for (int w = 0; w < wave; ++w) wave_base += s_cnt[w];
     if (alive) {
-        uint32_t wave_base = s_cnt[4];
-        for (int w = 0; w < wave; ++w) wave_base += s_cnt[w];
         const uint32_t out_slot = wave_base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
         if (kSort) {
             // (the bin's counter first: its round trip -- a device-scope atomic is performed at the memory side -- runs beside the ray's stores)
@@ -775,10 +782,24 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
             }
             uint32_t base = 0u;
             if (lane == grp_leader) base = atomicAdd(wb.sort_hist + key, grp_n);
+            float4 *const r = s_rec + (wave * 64u + (out_slot - wave_base)) * 4u;
+            r[0] = make_float4(s.o.x, s.o.y, s.o.z, s.d.x); r[1] = make_float4(s.d.y, s.d.z, s.thr.x, s.thr.y);
+            r[2] = make_float4(s.thr.z, s.rad.x, s.rad.y, s.rad.z);
+            r[3] = make_float4(__uint_as_float(s.rng.x), __uint_as_float(s.rng.y), __uint_as_float(s.rng.z), __uint_as_float(s.rng.w));
+            store_through(wb.stage_pixel + out_slot, s.pixel);
             const uint32_t rank = (uint32_t)__shfl((int)base, grp_leader) + grp_rank;
-            store_ray(qout, out_slot, s);
             store_through(reinterpret_cast<unsigned long long *>(wb.sort_kr + out_slot), (unsigned long long)key | ((unsigned long long)rank << 32));
         } else { store_ray(qout, out_slot, s); store_through(best_out + out_slot, kNoHitKey); }
+    }
+    if (kSort) {
+        // the wave's records, 1 KiB per store instruction: slots wave_base .. wave_base + survivors - 1 (a multiple of 64 bytes)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // (LDS traffic inside one wave)
+        const uint32_t parts = 4u * (uint32_t)__popcll(mask);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t i = k * 64u + lane;
+            if (i < parts) { const float4 v = s_rec[wave * 256u + i]; store_through(wb.stage + 4u * wave_base + i, v.x, v.y, v.z, v.w); }
+        }
     }
     __syncthreads();                                                              // s_cnt is rewritten by the next batch
     }
@@ -834,25 +855,45 @@ __global__ void __launch_bounds__(256) sort_prefix_kernel(WaveBuffers wb)
 #pragma unroll
     for (int k = 0; k < 4; ++k) store_through(reinterpret_cast<uint4 *>(h) + k, base + c[4 * k], base + c[4 * k + 1], base + c[4 * k + 2], base + c[4 * k + 3]);
 }
-// the rays entering `bounce` (just left in the staging queue by the shade kernel of bounce - 1) to their slots in key order
+// the other set of bin counters (last used two binned bounces ago; its move launch has ended): zero for the next binned bounce
+// (4 MB of stores beside the move's ~200: in sort_prefix_kernel, a launch of 5 us, they cost 3 us)
+__device__ __forceinline__ void sort_zero_other(const WaveBuffers &wb)
+{
+    uint4 *const z = reinterpret_cast<uint4 *>(wb.sort_hist_other);
+    const uint32_t n4 = (uint32_t)(((size_t)1u << wb.sort_bits) / 4u);
+    for (uint32_t w = blockIdx.x * 256u + threadIdx.x; w < n4; w += gridDim.x * 256u) store_through(z + w, 0u, 0u, 0u, 0u);
+}
+// The move, RTGL_AMD_SORT_MOVE = 1 (default): per staging slot ONE scattered 4-byte store, src[to] = slot, of the ray's destination
+// `to` in key order.  The rays stay in the staging queue until packet_cull_kernel, the first kernel to read the binned queue, gathers
+// them as it loads its granules and writes all five streams coalesced (the next shade launch overwrites the staging queue, so one
+// staging queue is enough).  Five scattered write-through stores per ray, four of 16 bytes and one of 4, were the move's cost.
+__global__ void __launch_bounds__(256) sort_place_kernel(WaveBuffers wb, uint32_t bounce)
+{
+    const uint32_t n_rays = wb.counts[bounce];
+    unsigned long long *best_out = (bounce & 1u) ? wb.best[1] : wb.best[0];
+    sort_zero_other(wb);
+    for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < n_rays; slot += gridDim.x * 256u) {
+        const uint2 kr = wb.sort_kr[slot];
+        const uint32_t to = wb.sort_hist[kr.x] + kr.y;
+        if (to < n_rays) store_through(wb.sort_src + to, slot);      // (always: the bins hold exactly the staged rays)
+        store_through(best_out + slot, kNoHitKey);                   // (every slot below n_rays is some thread's own: coalesced)
+    }
+}
+// RTGL_AMD_SORT_MOVE = 0: the rays entering `bounce` (just left in the staging queue by the shade kernel of bounce - 1) scattered to their
+// slots in key order
 __global__ void __launch_bounds__(256) sort_scatter_kernel(WaveBuffers wb, uint32_t bounce)
 {
     const uint32_t n_rays = wb.counts[bounce];
     const RayQueue qout = (bounce & 1u) ? wb.q[1] : wb.q[0];
     unsigned long long *best_out = (bounce & 1u) ? wb.best[1] : wb.best[0];
-    // the other set of bin counters (last used two binned bounces ago; its scatter launch has ended): zero for the next binned bounce
-    // (4 MB of stores beside this launch's ~200: in sort_prefix_kernel, a launch of 5 us, they cost 3 us)
-    {
-        uint4 *const z = reinterpret_cast<uint4 *>(wb.sort_hist_other);
-        const uint32_t n4 = (uint32_t)(((size_t)1u << wb.sort_bits) / 4u);
-        for (uint32_t w = blockIdx.x * 256u + threadIdx.x; w < n4; w += gridDim.x * 256u) store_through(z + w, 0u, 0u, 0u, 0u);
-    }
+    sort_zero_other(wb);
     for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < n_rays; slot += gridDim.x * 256u) {
         const uint2 kr = wb.sort_kr[slot];
         const uint32_t to = wb.sort_hist[kr.x] + kr.y;
-        const float4 a = wb.qt.a[slot], b = wb.qt.b[slot], c = wb.qt.c[slot];
-        const uint4 g = wb.qt.rng[slot];
-        const uint32_t px = wb.qt.pixel[slot];
+        const float4 *const r = wb.stage + 4u * slot;
+        const float4 a = r[0], b = r[1], c = r[2];
+        const uint4 g = *reinterpret_cast<const uint4 *>(r + 3);
+        const uint32_t px = wb.stage_pixel[slot];
         if (to >= n_rays) { store_through(best_out + slot, kNoHitKey); continue; }      // (cannot happen: the bins hold exactly the staged rays)
         store_through(qout.a + to, a.x, a.y, a.z, a.w);
         store_through(qout.b + to, b.x, b.y, b.z, b.w);

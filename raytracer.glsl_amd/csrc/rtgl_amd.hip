@@ -217,9 +217,10 @@ struct rtgl_context {
     uint32_t *d_keep0 = nullptr; size_t keep0_capacity = 0; bool keep0_valid = false; FrameParams keep0_params{}; uint32_t keep0_n0 = 0, keep0_words = 0; uint64_t keep0_scene = 0;
     uint64_t scene_version = 0;
     void *d_plan = nullptr; size_t plan_capacity = 0;             // planned work distribution of culled scan launches: cost prefix sums per chunk
-    void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) per slot
+    void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
     uint32_t *d_sort_hist = nullptr; uint32_t sort_bits_alloc = 0;      // two sets of bin counters, used in turns
     int sort_set = 0; uint32_t sort_set_bits = 0; bool sort_sets_clean = false;      // the set the next binned bounce counts in; false: zero both first (fresh, or a frame was abandoned half way)
+    int opt_sort_move = 1;                   // ray binning's move (rt_wavefront.hpp, WaveBuffers): 1 gathered by packet_cull_kernel, 0 scattered (RTGL_AMD_SORT_MOVE)
     float mesh_lo[3] = {0.0f, 0.0f, 0.0f}, mesh_hi[3] = {0.0f, 0.0f, 0.0f}, mesh_ext = 0.0f;       // box of the triangles' finite vertices (origin cells of the bin key)
     uint2 *d_cand = nullptr; uint32_t cand_regions = 0, cand_region_pairs = 0, cand_region_target = 0; bool cand_fixed = false;
     bool solo_attr_set = false;              // hipFuncAttributeMaxDynamicSharedMemorySize is per device: raised once per context (= per device binding)
@@ -368,6 +369,7 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     if (const char *k = getenv("RTGL_AMD_SCAN_WAVES")) { const int v = atoi(k); if (v >= 0 && v <= 2) ctx->opt_scan_waves = v; }   // A/B of the scan's occupancy
     if (const char *k = getenv("RTGL_AMD_FRAME_BATCH")) { const int v = atoi(k); if (v >= 1 && v <= (int)kBatchMax) ctx->opt_frame_batch = v; }
     if (const char *k = getenv("RTGL_AMD_SCAN_DYNAMIC")) { const int v = atoi(k); if (v >= 0 && v <= 4) ctx->opt_scan_dynamic = v; }   // ... and of its work distribution
+    if (const char *k = getenv("RTGL_AMD_SORT_MOVE")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_sort_move = v; }   // A/B of ray binning's move
     *out = ctx;
     return RTGL_OK;
 }
@@ -939,16 +941,16 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
             }
             ctx->wb.sched = ctx->d_sched;
         }
-        if (ctx->opt_cull == 3) {                            // ray binning: staging queue (a, b, c, rng: 4 x 16 B, pixel 4 B, key + rank 8 B) and the bin counters
+        if (ctx->opt_cull == 3) {                            // ray binning: staging queue (64-byte records of a, b, c, rng, pixel 4 B), key + rank 8 B, source slot 4 B, and the bin counters
             if (ctx->stage_capacity < n0) {
                 if (ctx->d_stage) { HIPCHK(ctx, hipFree(ctx->d_stage)); ctx->d_stage = nullptr; }
-                HIPCHK(ctx, hipMalloc(&ctx->d_stage, (size_t)n0 * 76 + 1024));
+                HIPCHK(ctx, hipMalloc(&ctx->d_stage, (size_t)n0 * 80 + 1024));
                 ctx->stage_capacity = n0;
             }
             uint8_t *p = (uint8_t *)ctx->d_stage;
             const size_t cap = ctx->stage_capacity;
-            ctx->wb.qt.a = (float4 *)p; p += cap * 16; ctx->wb.qt.b = (float4 *)p; p += cap * 16; ctx->wb.qt.c = (float4 *)p; p += cap * 16;
-            ctx->wb.qt.rng = (uint4 *)p; p += cap * 16; ctx->wb.sort_kr = (uint2 *)p; p += cap * 8; ctx->wb.qt.pixel = (uint32_t *)p;
+            ctx->wb.stage = (float4 *)p; p += cap * 64; ctx->wb.sort_kr = (uint2 *)p; p += cap * 8; ctx->wb.stage_pixel = (uint32_t *)p; p += cap * 4;
+            ctx->wb.sort_src = (uint32_t *)p;
             // origin cell bits behind the flag: 11, 14 for more than twelve million rays
             ctx->wb.sort_ob = n0 > (12u << 20) ? 5u : 4u;            // (C5, 8.3 M rays: 917 Mpaths/s with 4, 909 with 5; C2 in batches of eight, 16.6 M: 2.12 against 2.10 ms per frame)
             if (const char *e = getenv("RTGL_AMD_SORT_OB")) { const int v = atoi(e); if (v >= 1 && v <= 5) ctx->wb.sort_ob = (uint32_t)v; }      // (tuning)
@@ -1145,9 +1147,11 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
             ctx->wb.keep = ctx->d_keep0;
             if (!have_bits) { ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_params = *cam; }
         } else { ctx->wb.keep = ctx->d_keep; ro_add = sigma_add = 0.0f; }
+        // (a binned queue is always culled here, and never from kept bits: bounce >= 1.  Under RTGL_AMD_SORT_MOVE = 1 this launch is what
+        // moves its rays out of the staging queue)
         if (!have_bits)
         hipLaunchKernelGGL(packet_cull_kernel, dim3(std::max(1u, std::min((est_gran + 3u) / 4u, 8192u))), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
-                           ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u);
+                           ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt_sort_move == 1));
         if (dist == 2) {
             // planned: cost prefix sums per chunk [chunks x stride u32][chunks totals u32][chunks + 1 starts u64]
             const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
@@ -1257,7 +1261,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                 const bool bin_next = ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->opt_cull == 3 && sc.n_tri_visits > 0 && b + 1u < P.max_bounce
                                       && est_next >= (uint32_t)ctx->opt_sort_min_rays;
                 if (bin_next) {
-                    // two sets of bin counters take turns: sort_scatter_kernel zeroes the one the next binned bounce will count in
+                    // two sets of bin counters take turns: the move (sort_place_kernel or sort_scatter_kernel) zeroes the one the next binned bounce will count in
                     const size_t bins = (size_t)1 << ctx->wb.sort_bits, set_words = bins + bins / kSortSeg;
                     if (!ctx->sort_sets_clean || ctx->sort_set_bits != ctx->wb.sort_bits) {
                         HIPCHK(ctx, hipMemsetAsync(ctx->d_sort_hist, 0, 2 * set_words * sizeof(uint32_t), ctx->stream));
@@ -1271,7 +1275,9 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     else hipLaunchKernelGGL((shade_kernel<false, true>), shade_grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, b, rng_out, ctx->d_counters);
                     hipLaunchKernelGGL(sort_sums_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     hipLaunchKernelGGL(sort_prefix_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
-                    hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
+                    // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
+                    if (ctx->opt_sort_move == 1) hipLaunchKernelGGL(sort_place_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
+                    else hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     HIPCHK(ctx, hipGetLastError());
                     ctx->sort_set ^= 1; ctx->sort_sets_clean = true;
                 } else if (ctx->opt_counters)
