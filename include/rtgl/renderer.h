@@ -25,6 +25,7 @@
 #include <memory>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../rtgl_amd.h"
@@ -344,13 +345,30 @@ public:
         return write_file(path, "", img.data(), img.size() * sizeof(float));
     }
     // Portable float map: "PF\n<w> <h>\n-1.0\n" (colour, little-endian), RGB float32, bottom row first -- the image's own row order
-    bool save_pfm(const std::string &path) const
+    bool save_pfm(const std::string &path) const { return write_pfm(path, read_image()); }
+
+    // ---- first-hit planes (option "aov", include/rtgl_amd.h; extension): albedo, normal, position and hit ids of the camera ray's first hit.
+    // set_aov(mask of RTGL_AOV_* bits) allocates the planes zeroed and restarts their running mean; 0 frees them.
+    void set_aov(int mask) { if (m_ctx) check(rtgl_set_option(m_ctx, "aov", mask)); }
+    // one plane (a single RTGL_AOV_* bit), 4 values per pixel, row 0 = bottom: read_aov(RTGL_AOV_NORMAL) for the float planes,
+    // read_aov<int32_t>(RTGL_AOV_IDS) for the ids.  Empty (and a message) when the plane is not enabled or T does not fit it.
+    template <typename T = float>
+    std::vector<T> read_aov(int plane) const
     {
-        const std::vector<float> img = read_image();
-        std::vector<float> rgb(img.size() / 4 * 3);
-        for (size_t i = 0; i < img.size() / 4; ++i) { rgb[3 * i] = img[4 * i]; rgb[3 * i + 1] = img[4 * i + 1]; rgb[3 * i + 2] = img[4 * i + 2]; }
-        const std::string head = "PF\n" + std::to_string(m_width) + " " + std::to_string(img.size() / 4 / (size_t)std::max(m_width, 1)) + "\n-1.0\n";
-        return write_file(path, head, rgb.data(), rgb.size() * sizeof(float));
+        static_assert(std::is_same<T, float>::value || std::is_same<T, int32_t>::value, "the planes hold float32 or int32 values");
+        if (!m_ctx) return {};
+        if ((plane == RTGL_AOV_IDS) != std::is_same<T, int32_t>::value) { std::cerr << "rtgl: read_aov: the ids plane is int32, the others float" << std::endl; return {}; }
+        std::vector<T> out((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_aov(m_ctx, plane, out.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return out;
+    }
+    // a float plane as a PFM, exactly like save_pfm (its first three channels)
+    bool save_aov_pfm(int plane, const std::string &path) const
+    {
+        if (plane == RTGL_AOV_IDS) { std::cerr << "rtgl: save_aov_pfm: the ids plane is not a float image" << std::endl; return false; }
+        const std::vector<float> img = read_aov(plane);
+        if (!m_ctx || img.size() != (size_t)m_width * rtgl_local_rows(m_ctx) * 4) return false;      // (read_aov has said why)
+        return write_pfm(path, img);
     }
     // The progressive state: the accumulation image and the frame counters the running mean depends on (u_frames, src/renderer.cpp:98).
     // load_state() into a Renderer of the same size continues exactly where save_state() stopped: the next frame is mixed in with
@@ -379,6 +397,14 @@ public:
 
 private:
     struct StateHeader { char magic[8]; int32_t width, height, frames; float time; };
+    // Portable float map of the RGB channels of an RGBA float image
+    bool write_pfm(const std::string &path, const std::vector<float> &img) const
+    {
+        std::vector<float> rgb(img.size() / 4 * 3);
+        for (size_t i = 0; i < img.size() / 4; ++i) { rgb[3 * i] = img[4 * i]; rgb[3 * i + 1] = img[4 * i + 1]; rgb[3 * i + 2] = img[4 * i + 2]; }
+        const std::string head = "PF\n" + std::to_string(m_width) + " " + std::to_string(img.size() / 4 / (size_t)std::max(m_width, 1)) + "\n-1.0\n";
+        return write_file(path, head, rgb.data(), rgb.size() * sizeof(float));
+    }
     static bool write_file(const std::string &path, const std::string &head, const void *data, size_t bytes)
     {
         std::ofstream f(path, std::ios::binary);

@@ -81,6 +81,31 @@ enum {
                                          * separate narrow-phase kernel */
 };
 
+/* First-hit auxiliary planes (option "aov" = a mask of the bits below; no reference counterpart).  Per local pixel one 16-byte record per
+ * enabled plane, laid out like the image (rows bottom-up; a tiled context holds its local strips, packed like the image):
+ *   RTGL_AOV_ALBEDO    float4  hit: albedo of the hit material exactly as the shader loads it, a = 1.  Miss: the background colour, or the
+ *                              cube-map value the camera ray received when u_use_envmap is on, a = 0.
+ *   RTGL_AOV_NORMAL    float4  hit: the normal shading uses (sphere: (p - c) / r; triangle: its stored plane normal), not flipped for
+ *                              inside hits, w = 0.  Miss: 0.
+ *   RTGL_AOV_POSITION  float4  hit: the hit point shading uses (o + d t), w = t.  Miss: 0.
+ *   RTGL_AOV_IDS       int32x4 {kind, object, primitive, material}: kind 1 sphere (object = primitive = sphere index), kind 2 triangle (object =
+ *                              mesh index, primitive = the triangle's index in the vertex buffer, vertex / 3).  Miss: {0, -1, -1, -1}.
+ * The first hit is the camera ray's hit at bounce 0, chosen exactly as shading chooses it (a mesh wins a tie with a sphere; among
+ * triangles the lowest visit index, which also decides the mesh of a triangle listed by two meshes).  With u_samples > 1 every sample
+ * reuses the camera ray: the planes are written once per frame.  u_max_bounce == 0 traces no ray: the frame contributes a miss with albedo 0.
+ * Accumulation: the three float planes hold the mean over the frames since they last restarted, v = (x + prev * (n - 1)) / n in float32
+ * (n == 1: v = x exactly), where n restarts at 1 on a frame with u_reset_flag != 0, on the first frame after rtgl_clear_image and on the
+ * first frame after "aov" is set, and otherwise counts the frames.  (Not the image's formula, which divides a reset frame by frames + 1.)
+ * The ids plane is always the last frame's.  rtgl_write_image_f32 does not touch the planes.  Default 0: no planes, nothing changes.
+ * Setting "aov" allocates the enabled planes zeroed (and frees the others); while it is non-zero frames are rendered one by one. */
+enum {
+    RTGL_AOV_ALBEDO = 1,
+    RTGL_AOV_NORMAL = 2,
+    RTGL_AOV_POSITION = 4,
+    RTGL_AOV_IDS = 8,
+    RTGL_AOV_ALL = 15
+};
+
 /* -- lifetime: replaces Renderer::Renderer(width,height) GL object creation (src/renderer.cpp:21-64).
  * The accumulation image is RGBA32F, width x height, zero-initialised (the reference leaves it
  * undefined).  device = HIP device ordinal. */
@@ -155,6 +180,13 @@ int rtgl_set_stream(rtgl_context *ctx, void *hip_stream);
 /* -- diagnostics */
 int rtgl_get_counters(rtgl_context *ctx, rtgl_counters *out);  /* synchronises */
 int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw);    /* per local pixel final PCG4D state of the last frame; needs option "rng_state"=1 */
+
+/* -- first-hit planes (option "aov", above).  plane = ONE RTGL_AOV_* bit.  rtgl_read_aov copies local_rows x width x 16 bytes (a multi-device
+ * handle: the whole image's rows, assembled on the host); RTGL_ERR_STATE when the plane is not enabled, RTGL_ERR_INVALID for a bad plane or
+ * a NULL pointer.  rtgl_device_aov: the plane's device pointer (torch interop); NULL on a multi-device handle or for a plane that is not
+ * enabled, see rtgl_last_error.  The pointer stays valid until "aov" is set again or the context is destroyed. */
+int rtgl_read_aov(rtgl_context *ctx, int plane, void *out);
+void *rtgl_device_aov(rtgl_context *ctx, int plane);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads
@@ -164,12 +196,12 @@ int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw);    /* per local pixe
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"
  * (cull 3: a bounce's queue is binned when at least this many rays are expected, default 131072), "mf_group_quads" (quads
  * sharing one local origin: a power of two up to 64; changing it rebuilds the broad-phase data at the next frame),
- * "rng_state", "counters", "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
+ * "rng_state", "counters", "aov" (first-hit planes, above), "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
  * event pairs around its dominant-kernel launches), "frame_batch" (1 (default) .. 16, also RTGL_AMD_FRAME_BATCH: with B > 1 rtgl_render_frame
  * only records the frame until B frames are waiting, then traces them in ONE set of launches and applies their results to the image in
  * frame order -- bit-identical to frame-by-frame, B times the rays per launch (what a rank of a multi-GPU run lacks).  Every other entry
  * point submits the waiting frames first, so the image a caller reads is always complete; frames that differ in samples, bounce limit,
- * environment switch or background close a batch early; with "counters", "rng_state" or "kernel_timing" on, with more than one sample
+ * environment switch or background close a batch early; with "counters", "rng_state", "aov" or "kernel_timing" on, with more than one sample
  * per frame and for scenes without triangles frames are rendered one by one; rtgl_destroy submits frames that are still waiting;
  * rtgl_device_image returns NULL when that submission fails) */
 int rtgl_set_option(rtgl_context *ctx, const char *key, int value);

@@ -173,7 +173,10 @@ __device__ __forceinline__ float sphere_intersect(f3 o, f3 d, f3 c, float radius
 // traverse (:272-329).  The walk over the node buffer does not depend on the ray (the AABB cull
 // is compiled out in the reference, :288-292), so the host flattens it once per scene into
 // `sphere_visits`; the per-ray work is the closest-hit scan in that order.
-__device__ __forceinline__ bool sphere_pass(const SceneView &sc, f3 o, f3 d, Hit &hit)
+// kId (first-hit planes only): `id` receives the index of the sphere that was hit (kNoSphere for the all-zero record of an index past the
+// buffer); the arithmetic that decides the hit is the same.
+template <bool kId>
+__device__ __forceinline__ bool sphere_pass_impl(const SceneView &sc, f3 o, f3 d, Hit &hit, uint32_t &id)
 {
     bool any = false;
     for (uint32_t k = 0; k < sc.n_sphere_visits; ++k) {
@@ -192,11 +195,14 @@ __device__ __forceinline__ bool sphere_pass(const SceneView &sc, f3 o, f3 d, Hit
             f3 pc = hit.point - c;
             hit.normal = mk(pc.x / radius, pc.y / radius, pc.z / radius);
             hit.material = material;
+            if (kId) id = i;
             any = true;
         }
     }
     return any;
 }
+__device__ __forceinline__ bool sphere_pass(const SceneView &sc, f3 o, f3 d, Hit &hit) { uint32_t unused; return sphere_pass_impl<false>(sc, o, d, hit, unused); }
+__device__ __forceinline__ bool sphere_pass_id(const SceneView &sc, f3 o, f3 d, Hit &hit, uint32_t &id) { return sphere_pass_impl<true>(sc, o, d, hit, id); }
 
 // Per-ray constants of the triangle pass.
 struct TriRay {

@@ -157,6 +157,46 @@ __device__ __forceinline__ void finish_path(const FrameParams &P, const ImageVie
     if (rng_out) rng_out[s.pixel] = make_uint4(s.rng.x, s.rng.y, s.rng.z, s.rng.w);
 }
 
+// ---- first-hit planes (option "aov", include/rtgl_amd.h) ----------------------------------------------
+// The camera ray's hit at bounce 0 of sample 0, written by the kAov instances of pathtrace_mega_kernel, bounce_kernel and shade_kernel
+// (launched for that bounce only).  Per local pixel one 16-byte record per enabled plane; NULL planes are skipped.
+struct AovView {
+    float4 *albedo, *normal, *position;   // running means over the frames since the planes last restarted
+    uint4 *ids;                           // {kind, object, primitive, material} of the last frame
+    const uint32_t *visit_mesh, *visit_tri;   // per triangle visit: its mesh and its triangle (vertex / 3); set while `ids` is
+    uint32_t n;                           // frames in the mean, this one included (1: the plane becomes this frame's value)
+};
+enum { kAovMiss = 0, kAovSphere = 1, kAovTriangle = 2 };
+
+// v = (x + prev * (n - 1)) / n, each operation rounded to float32 (the translation unit does not contract)
+__device__ __forceinline__ void aov_blend(float4 *p, float x, float y, float z, float w, uint32_t n)
+{
+    if (n == 1u) { store_through(p, x, y, z, w); return; }
+    const float4 q = *p;
+    const float m = (float)(n - 1u), fn = (float)n;
+    store_through(p, (x + q.x * m) / fn, (y + q.y * m) / fn, (z + q.z * m) / fn, (w + q.w * m) / fn);
+}
+
+// kind = kAovMiss: `bg` is what the camera ray received (background or cube map; zero when no ray was traced).  Otherwise `h` is the hit
+// shading uses and `index` the sphere index or the triangle's visit index.
+__device__ __forceinline__ void aov_write(const SceneView &sc, const AovView &aov, uint32_t pixel, int kind, const Hit &h, uint32_t index, f3 bg)
+{
+    if (kind == kAovMiss) {
+        if (aov.albedo) aov_blend(aov.albedo + pixel, bg.x, bg.y, bg.z, 0.0f, aov.n);
+        if (aov.normal) aov_blend(aov.normal + pixel, 0.0f, 0.0f, 0.0f, 0.0f, aov.n);
+        if (aov.position) aov_blend(aov.position + pixel, 0.0f, 0.0f, 0.0f, 0.0f, aov.n);
+        if (aov.ids) store_through(aov.ids + pixel, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+        return;
+    }
+    if (aov.albedo) { const MaterialRec m = load_material(sc, h.material); aov_blend(aov.albedo + pixel, m.ar, m.ag, m.ab, 1.0f, aov.n); }
+    if (aov.normal) aov_blend(aov.normal + pixel, h.normal.x, h.normal.y, h.normal.z, 0.0f, aov.n);
+    if (aov.position) aov_blend(aov.position + pixel, h.point.x, h.point.y, h.point.z, h.t, aov.n);
+    if (aov.ids) {
+        const uint32_t object = kind == kAovSphere ? index : aov.visit_mesh[index], prim = kind == kAovSphere ? index : aov.visit_tri[index];
+        store_through(aov.ids + pixel, (uint32_t)kind, object, prim, (uint32_t)h.material);
+    }
+}
+
 // ---- queue 0 ---------------------------------------------------------------------------------------
 // sample 0: camera rays from scratch.  sample > 0: same camera ray, RNG continued (:556-559).
 // Frame batching: the launch of frame f of a batch writes slots [slot_off, slot_off + n0) with pixel_tag = f << 28; only the first stores
@@ -312,9 +352,10 @@ __device__ __forceinline__ TriCoef load_coef(const float4 *p)
     return T;
 }
 
-template <int R, int MODE, bool kCount>
+// kAov: the launch of bounce 0 of sample 0 while option "aov" is on; it also writes the first-hit planes
+template <int R, int MODE, bool kCount, bool kAov>
 __global__ void __launch_bounds__(256) bounce_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
-                                                     uint32_t bounce, uint4 *rng_out, Counters *counters)
+                                                     uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
 {
     __shared__ float4 lds_tile[MODE == kLds ? 2 * kTile * 5 : 1];
     const uint32_t n_rays = wb.counts[bounce];
@@ -407,18 +448,23 @@ __global__ void __launch_bounds__(256) bounce_kernel(SceneView sc, FrameParams P
         if (valid) {
             s = load_ray(qin, slot, bounce == 0u);
             Hit h; h.t = kInf; h.material = 0; h.point = h.normal = mk(0.0f, 0.0f, 0.0f);
-            const bool hit_sphere = sphere_pass(sc, s.o, s.d, h);                        // traverse (:433)
+            uint32_t sphere_id = kNoSphere;
+            const bool hit_sphere = kAov ? sphere_pass_id(sc, s.o, s.d, h, sphere_id) : sphere_pass(sc, s.o, s.d, h);   // traverse (:433)
             const bool hit_mesh = hr.best_v[r] != 0xFFFFFFFFu;
             if (!hit_sphere && !hit_mesh) {                                              // :441-445
                 f3 bg;
                 if (P.use_envmap) { bg = env_lookup(sc, s.d); if (kCount) c_env++; }
                 else bg = mk(P.background[0], P.background[1], P.background[2]);
+                if (kAov) aov_write(sc, aov, s.pixel & kBatchPixelMask, kAovMiss, h, 0u, bg);
                 s.rad = s.rad + bg * s.thr;
             } else {
+                int aov_kind = kAovTriangle;
+                if (kAov && h.t < hr.best_t[r]) aov_kind = kAovSphere;
                 if (!(h.t < hr.best_t[r])) {                                             // :447
                     const TriPlane pl = sc.tri_planes[hr.best_v[r]];
                     h.t = hr.best_t[r]; h.point = s.o + s.d * hr.best_t[r]; h.normal = mk(pl.nx, pl.ny, pl.nz); h.material = pl.material;
                 }
+                if (kAov) aov_write(sc, aov, s.pixel & kBatchPixelMask, aov_kind, h, aov_kind == kAovSphere ? sphere_id : hr.best_v[r], mk(0.0f, 0.0f, 0.0f));
                 alive = shade_hit(sc, h, s.rng, s.o, s.d, s.thr, s.rad) && !last_bounce;
             }
             if (!alive) finish_path(P, im, wb, s, rng_out);
@@ -710,9 +756,10 @@ __device__ __forceinline__ uint32_t ray_bin_key(const WaveBuffers &wb, f3 o, f3 
     return (dir << (T + 1u)) | (inside ? 0u : 1u << T) | (cell << (T - n));
 }
 
-template <bool kCount, bool kSort>
+// kAov: the launch of bounce 0 of sample 0 while option "aov" is on; it also writes the first-hit planes
+template <bool kCount, bool kSort, bool kAov>
 __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
-                                                    uint32_t bounce, uint4 *rng_out, Counters *counters)
+                                                    uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
 {
     const uint32_t n_rays = wb.counts[bounce];
     const RayQueue qin = (bounce & 1u) ? wb.q[1] : wb.q[0];
@@ -734,19 +781,24 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
         s = load_ray(qin, slot, bounce == 0u);
         const unsigned long long key = best_in[slot];
         Hit h; h.t = kInf; h.material = 0; h.point = h.normal = mk(0.0f, 0.0f, 0.0f);
-        const bool hit_sphere = sphere_pass(sc, s.o, s.d, h);                            // traverse (:433)
+        uint32_t sphere_id = kNoSphere;
+        const bool hit_sphere = kAov ? sphere_pass_id(sc, s.o, s.d, h, sphere_id) : sphere_pass(sc, s.o, s.d, h);   // traverse (:433)
         const bool hit_mesh = key != kNoHitKey;
         if (!hit_sphere && !hit_mesh) {                                                  // :441-445
             f3 bg;
             if (P.use_envmap) { bg = env_lookup(sc, s.d); if (kCount) c_env++; }
             else bg = mk(P.background[0], P.background[1], P.background[2]);
+            if (kAov) aov_write(sc, aov, s.pixel & kBatchPixelMask, kAovMiss, h, 0u, bg);
             s.rad = s.rad + bg * s.thr;
         } else {
             const float mesh_t = hit_mesh ? __uint_as_float((uint32_t)(key >> 32)) : kInf;
+            int aov_kind = kAovTriangle;
+            if (kAov && h.t < mesh_t) aov_kind = kAovSphere;
             if (!(h.t < mesh_t)) {                                                       // :447
                 const TriPlane pl = sc.tri_planes[(uint32_t)key];
                 h.t = mesh_t; h.point = s.o + s.d * mesh_t; h.normal = mk(pl.nx, pl.ny, pl.nz); h.material = pl.material;
             }
+            if (kAov) aov_write(sc, aov, s.pixel & kBatchPixelMask, aov_kind, h, aov_kind == kAovSphere ? sphere_id : (uint32_t)key, mk(0.0f, 0.0f, 0.0f));
             alive = shade_hit(sc, h, s.rng, s.o, s.d, s.thr, s.rad) && !last_bounce;
         }
         if (!alive) finish_path(P, im, wb, s, rng_out);

@@ -63,8 +63,9 @@ __global__ void __launch_bounds__(256) prepare_triangles_kernel(const float4 *__
 // Triangle records are wave-uniform, so the compiler fetches them with scalar loads (SGPR operands
 // feed the fma chain directly); no LDS traffic.  Baseline variant, kept as the A/B reference for the
 // tiled / wavefront kernels.
-template <bool kCount>
-__global__ void __launch_bounds__(256) pathtrace_mega_kernel(SceneView sc, FrameParams P, ImageView im, uint4 *rng_out, Counters *counters)
+// kAov: option "aov" is on -- the camera ray's hit (bounce 0 of sample 0) also goes to the first-hit planes (rt_wavefront.hpp, aov_write)
+template <bool kCount, bool kAov>
+__global__ void __launch_bounds__(256) pathtrace_mega_kernel(SceneView sc, FrameParams P, ImageView im, uint4 *rng_out, Counters *counters, AovView aov)
 {
     // 8x8 pixel block per wave (matches the reference work-group shape :38), 4 waves side by side
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -90,7 +91,8 @@ __global__ void __launch_bounds__(256) pathtrace_mega_kernel(SceneView sc, Frame
         for (uint32_t bounce = 0; bounce < P.max_bounce; ++bounce) {                        // :425
             if (kCount) c_seg++;
             Hit h1; h1.t = kInf; h1.material = 0; h1.point = h1.normal = mk(0.0f, 0.0f, 0.0f);
-            bool hit_sphere = sphere_pass(sc, o, d, h1);                                    // :433
+            uint32_t sphere_id = kNoSphere;
+            bool hit_sphere = kAov ? sphere_pass_id(sc, o, d, h1, sphere_id) : sphere_pass(sc, o, d, h1);   // :433
             // find_closest_mesh (:331-361)
             TriRay tr = make_tri_ray(o, d);
             float best_t = kInf; uint32_t best_v = 0xFFFFFFFFu;
@@ -108,6 +110,7 @@ __global__ void __launch_bounds__(256) pathtrace_mega_kernel(SceneView sc, Frame
                 f3 bg;
                 if (P.use_envmap) { bg = env_lookup(sc, d); if (kCount) c_env++; }
                 else bg = mk(P.background[0], P.background[1], P.background[2]);
+                if (kAov && s == 0u && bounce == 0u) aov_write(sc, aov, (uint32_t)(lrow * im.width + px), kAovMiss, h1, 0u, bg);
                 radiance = radiance + bg * thr;
                 break;
             }
@@ -116,9 +119,15 @@ __global__ void __launch_bounds__(256) pathtrace_mega_kernel(SceneView sc, Frame
                 const TriPlane &pl = sc.tri_planes[best_v];
                 h.t = best_t; h.point = o + d * best_t; h.normal = mk(pl.nx, pl.ny, pl.nz); h.material = pl.material;
             }
+            if (kAov && s == 0u && bounce == 0u)
+                aov_write(sc, aov, (uint32_t)(lrow * im.width + px), !(h1.t < best_t) ? kAovTriangle : kAovSphere, h, !(h1.t < best_t) ? best_v : sphere_id, mk(0.0f, 0.0f, 0.0f));
             if (!shade_hit(sc, h, rng, o, d, thr, radiance)) break;
         }
         color = color + radiance;
+    }
+    if (kAov && P.max_bounce == 0u) {                    // no ray was traced: a miss that received nothing
+        Hit none; none.t = kInf; none.material = 0; none.point = none.normal = mk(0.0f, 0.0f, 0.0f);
+        aov_write(sc, aov, (uint32_t)(lrow * im.width + px), kAovMiss, none, 0u, mk(0.0f, 0.0f, 0.0f));
     }
     { const float4 v = accumulate_pixel(P, color, prev); store_through(pix, v.x, v.y, v.z, v.w); }      // (rt_wavefront.hpp: read by the next frame's kernel, from whichever XCD)
     if (rng_out) rng_out[(size_t)lrow * im.width + px] = make_uint4(rng.x, rng.y, rng.z, rng.w);
@@ -244,9 +253,16 @@ struct rtgl_context {
     float4 *d_batch_rad = nullptr; size_t batch_capacity = 0;
     uint32_t last_batch_frames = 1;
     bool tris_dirty = false, visits_dirty = false;
+    // first-hit planes (option "aov"): one buffer of local_rows x width 16-byte records per enabled plane (albedo, normal, position, ids);
+    // aov_n frames in their running mean, restarted by the next frame when aov_restart is set
+    float4 *d_aov[3] = {nullptr, nullptr, nullptr}; uint4 *d_aov_ids = nullptr;
+    uint32_t aov_n = 0; bool aov_restart = true;
+    // ... and, for the ids plane only, per triangle visit its mesh and its triangle (uploaded while that plane is enabled)
+    std::vector<uint32_t> h_visit_mesh, h_visit_tri;
+    uint32_t *d_visit_mesh = nullptr, *d_visit_tri = nullptr; bool visit_ids_dirty = true;
     FrameParams params{};
     bool have_params = false;
-    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1;
+    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0;
 };
 
 static int fail(rtgl_context *ctx, int code, const std::string &msg)
@@ -436,7 +452,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
 #endif
     void *ptrs[] = { ctx->d_spheres, ctx->d_materials, ctx->d_vertices, ctx->d_sphere_visits, ctx->d_edges, ctx->d_planes,
                      ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
-                     ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad };
+                     ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
+                     ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -758,15 +775,16 @@ static uint32_t cull_node_shift_option()
 
 static int rebuild_triangles(rtgl_context *ctx)
 {
-    std::vector<uint32_t> visit_tri;
+    std::vector<uint32_t> visit_tri, visit_mesh;
     uint32_t n_tris = ctx->n_vec4 / 3;   // to_triangles() drops a trailing partial triangle (src/renderer.h:34-48)
     for (uint32_t m = 0; m < ctx->n_meshes; ++m) {
         uint32_t start, size;
         memcpy(&start, ctx->h_meshes.data() + (size_t)m * 16, 4);
         memcpy(&size, ctx->h_meshes.data() + (size_t)m * 16 + 4, 4);
         uint64_t end = std::min<uint64_t>((uint64_t)start + size, n_tris);
-        for (uint64_t t = start; t < end; ++t) visit_tri.push_back((uint32_t)t);
+        for (uint64_t t = start; t < end; ++t) { visit_tri.push_back((uint32_t)t); visit_mesh.push_back(m); }
     }
+    ctx->h_visit_tri = visit_tri; ctx->h_visit_mesh.swap(visit_mesh); ctx->visit_ids_dirty = true;      // (the ids plane's triangle ids)
     if (ctx->d_edges) { HIPCHK(ctx, hipFree(ctx->d_edges)); ctx->d_edges = nullptr; }
     if (ctx->d_planes) { HIPCHK(ctx, hipFree(ctx->d_planes)); ctx->d_planes = nullptr; }
     ctx->n_tri_visits = (uint32_t)visit_tri.size();
@@ -1005,14 +1023,31 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
     return RTGL_OK;
 }
 
+// aov != NULL: the launch of bounce 0 of sample 0 with option "aov" on (the instance that also writes the first-hit planes)
 template <int R, int MODE>
-static void launch_bounce(rtgl_context *ctx, const SceneView &sc, const FrameParams &P, const ImageView &im, uint32_t n0, uint32_t bounce, uint4 *rng_out)
+static void launch_bounce(rtgl_context *ctx, const SceneView &sc, const FrameParams &P, const ImageView &im, uint32_t n0, uint32_t bounce, uint4 *rng_out, const AovView *aov)
 {
     dim3 grid((n0 + 256u * R - 1) / (256u * R));
-    if (ctx->opt_counters)
-        hipLaunchKernelGGL((bounce_kernel<R, MODE, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters);
+    if (aov) {
+        if (ctx->opt_counters) hipLaunchKernelGGL((bounce_kernel<R, MODE, true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
+        else hipLaunchKernelGGL((bounce_kernel<R, MODE, false, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
+    } else if (ctx->opt_counters)
+        hipLaunchKernelGGL((bounce_kernel<R, MODE, true, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
     else
-        hipLaunchKernelGGL((bounce_kernel<R, MODE, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters);
+        hipLaunchKernelGGL((bounce_kernel<R, MODE, false, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
+}
+
+// shade_kernel of one bounce; aov as for launch_bounce
+template <bool kSort>
+static void launch_shade(rtgl_context *ctx, dim3 grid, const SceneView &sc, const FrameParams &P, const ImageView &im, uint32_t bounce, uint4 *rng_out, const AovView *aov)
+{
+    if (aov) {
+        if (ctx->opt_counters) hipLaunchKernelGGL((shade_kernel<true, kSort, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
+        else hipLaunchKernelGGL((shade_kernel<false, kSort, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
+    } else if (ctx->opt_counters)
+        hipLaunchKernelGGL((shade_kernel<true, kSort, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
+    else
+        hipLaunchKernelGGL((shade_kernel<false, kSort, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
 }
 
 // Upper estimate of the rays entering `bounce`, for grid sizing only (kernels grid-stride, so a low
@@ -1204,7 +1239,8 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
 
 // frames.size() > 1: a batch -- every frame's camera rays are generated into its own stretch of queue 0 (n0_frame slots), everything
 // behind that sees ONE frame of n0 = B x n0_frame rays, and resolve_batch_kernel applies the frames' results to the image in order
-static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::vector<FrameParams> &frames, const ImageView &im, uint32_t n0_frame, uint4 *rng_out)
+static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::vector<FrameParams> &frames, const ImageView &im, uint32_t n0_frame, uint4 *rng_out,
+                            const AovView *aov)
 {
     const FrameParams &P = frames[0];
     const uint32_t B = (uint32_t)frames.size(), n0 = n0_frame * B;
@@ -1234,6 +1270,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
         bool binned = false;                                 // the queue of the bounce about to be launched was binned
         for (uint32_t b = 0; b < P.max_bounce; ++b) {
             const int key = ctx->opt_wf_mode * 10 + ctx->opt_wf_rays;
+            const AovView *aov_b = (s == 0u && b == 0u) ? aov : nullptr;      // the first-hit planes: the camera rays of sample 0
             if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_SPLIT || ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
                 if (sc.n_tri_visits > 0 && ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
                     kev_mark(ctx);
@@ -1271,8 +1308,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     if (getenv("RTGL_AMD_HIST_FILL")) HIPCHK(ctx, hipMemsetAsync(ctx->d_sort_hist + (size_t)ctx->sort_set * set_words, 0, bins * sizeof(uint32_t), ctx->stream));      // (measurement: the fill launch per bounce that the turns replace)
                     ctx->wb.sort_hist = ctx->d_sort_hist + (size_t)ctx->sort_set * set_words;
                     ctx->wb.sort_hist_other = ctx->d_sort_hist + (size_t)(ctx->sort_set ^ 1) * set_words;
-                    if (ctx->opt_counters) hipLaunchKernelGGL((shade_kernel<true, true>), shade_grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, b, rng_out, ctx->d_counters);
-                    else hipLaunchKernelGGL((shade_kernel<false, true>), shade_grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, b, rng_out, ctx->d_counters);
+                    launch_shade<true>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
                     hipLaunchKernelGGL(sort_sums_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     hipLaunchKernelGGL(sort_prefix_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
@@ -1280,21 +1316,18 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     else hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     HIPCHK(ctx, hipGetLastError());
                     ctx->sort_set ^= 1; ctx->sort_sets_clean = true;
-                } else if (ctx->opt_counters)
-                    hipLaunchKernelGGL((shade_kernel<true, false>), shade_grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, b, rng_out, ctx->d_counters);
-                else
-                    hipLaunchKernelGGL((shade_kernel<false, false>), shade_grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, b, rng_out, ctx->d_counters);
+                } else launch_shade<false>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
                 binned = bin_next;
                 continue;
             }
             kev_mark(ctx);
             switch (key) {
-            case 1: launch_bounce<1, kScalar>(ctx, sc, P, im, n0, b, rng_out); break;
-            case 2: launch_bounce<2, kScalar>(ctx, sc, P, im, n0, b, rng_out); break;
-            case 4: launch_bounce<4, kScalar>(ctx, sc, P, im, n0, b, rng_out); break;
-            case 11: launch_bounce<1, kLds>(ctx, sc, P, im, n0, b, rng_out); break;
-            case 12: launch_bounce<2, kLds>(ctx, sc, P, im, n0, b, rng_out); break;
-            case 14: launch_bounce<4, kLds>(ctx, sc, P, im, n0, b, rng_out); break;
+            case 1: launch_bounce<1, kScalar>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
+            case 2: launch_bounce<2, kScalar>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
+            case 4: launch_bounce<4, kScalar>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
+            case 11: launch_bounce<1, kLds>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
+            case 12: launch_bounce<2, kLds>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
+            case 14: launch_bounce<4, kLds>(ctx, sc, P, im, n0, b, rng_out, aov_b); break;
             default: return fail(ctx, RTGL_ERR_STATE, "unsupported wf_mode / wf_rays combination");
             }
             kev_mark(ctx);
@@ -1370,7 +1403,7 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
     // frame batching: hold the frame back until the batch is full.  Only what the batched pipeline covers: one sample per frame, the
     // per-bounce pipeline (a scene with triangles), no per-frame read-outs (counters, RNG states)
     const bool batchable = ctx->opt_frame_batch > 1 && ctx->params.samples == 1 && ctx->params.max_bounce > 0 && !ctx->opt_counters && !ctx->opt_rng_state
-                           && !ctx->opt_kernel_timing && (ctx->n_tri_visits > 0 || ctx->tris_dirty || ctx->kernel_explicit) && ctx->opt_kernel != RTGL_KERNEL_MEGA;
+                           && !ctx->opt_kernel_timing && !ctx->opt_aov && (ctx->n_tri_visits > 0 || ctx->tris_dirty || ctx->kernel_explicit) && ctx->opt_kernel != RTGL_KERNEL_MEGA;
     if (!ctx->pending.empty() && (!batchable || !batch_compatible(ctx->pending.front(), ctx->params))) { const int rc = flush_pending(ctx); if (rc) return rc; }
     if (batchable) {
         ctx->pending.push_back(ctx->params);
@@ -1387,6 +1420,13 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
     if (ctx->opt_rng_state && !ctx->d_rng)
         HIPCHK(ctx, hipMalloc((void **)&ctx->d_rng, (size_t)std::max(ctx->local_rows, 1) * ctx->width * sizeof(uint4)));
+    if ((ctx->opt_aov & RTGL_AOV_IDS) && ctx->visit_ids_dirty) {
+        const size_t bytes = ctx->h_visit_tri.size() * sizeof(uint32_t);
+        int rc = realloc_upload(ctx, ctx->d_visit_mesh, ctx->h_visit_mesh.data(), bytes);
+        if (!rc) rc = realloc_upload(ctx, ctx->d_visit_tri, ctx->h_visit_tri.data(), bytes);
+        if (rc) return rc;
+        ctx->visit_ids_dirty = false;
+    }
 
     SceneView sc{};
     sc.spheres = ctx->d_spheres; sc.n_spheres = ctx->n_spheres;
@@ -1410,6 +1450,14 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if ((uint64_t)n0_frame * B > 0xFFFFFFF0ull || (size_t)std::max(ctx->local_rows, 1) * ctx->width > (size_t)kBatchPixelMask) return fail(ctx, RTGL_ERR_INVALID, "frame_batch: the batch does not fit 32-bit ray slots");
     const uint32_t n0 = n0_frame * B;            // rays entering bounce 0: all frames of the batch
     uint4 *rng_out = ctx->opt_rng_state ? ctx->d_rng : nullptr;
+    // first-hit planes: frames are rendered one by one while they are on (B == 1); the running mean restarts with a reset frame
+    AovView aov{};
+    if (ctx->opt_aov) {
+        ctx->aov_n = (P.reset_flag || ctx->aov_restart) ? 1u : ctx->aov_n + 1u;
+        ctx->aov_restart = false;
+        aov.albedo = ctx->d_aov[0]; aov.normal = ctx->d_aov[1]; aov.position = ctx->d_aov[2]; aov.ids = ctx->d_aov_ids;
+        aov.visit_mesh = ctx->d_visit_mesh; aov.visit_tri = ctx->d_visit_tri; aov.n = ctx->aov_n;
+    }
     // a scene without triangles has no scan to split off: one megakernel launch per frame beats the per-bounce pipeline
     // (C1, 256x256 spheres: 1460 vs 1025 Mpaths/s) unless the caller asked for a specific variant
     const int kernel = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt_kernel;
@@ -1442,14 +1490,17 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if (n0 > 0 && !use_wavefront) {
         dim3 grid((im.disp_w + 31) / 32, (local_disp_rows + 7) / 8);
         kev_mark(ctx);
-        if (ctx->opt_counters)
-            hipLaunchKernelGGL(pathtrace_mega_kernel<true>, grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters);
+        if (ctx->opt_aov) {
+            if (ctx->opt_counters) hipLaunchKernelGGL((pathtrace_mega_kernel<true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, aov);
+            else hipLaunchKernelGGL((pathtrace_mega_kernel<false, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, aov);
+        } else if (ctx->opt_counters)
+            hipLaunchKernelGGL((pathtrace_mega_kernel<true, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, AovView{});
         else
-            hipLaunchKernelGGL(pathtrace_mega_kernel<false>, grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters);
+            hipLaunchKernelGGL((pathtrace_mega_kernel<false, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, AovView{});
         kev_mark(ctx);
         HIPCHK(ctx, hipGetLastError());
     } else if (n0 > 0) {
-        int rc = launch_wavefront(ctx, sc, frames, im, n0_frame, rng_out);
+        int rc = launch_wavefront(ctx, sc, frames, im, n0_frame, rng_out, ctx->opt_aov ? &aov : nullptr);
         if (rc) return rc;
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -1567,6 +1618,7 @@ extern "C" int rtgl_clear_image(rtgl_context *ctx)
     ENTER(ctx);
     FANOUT(ctx, rtgl_clear_image(part));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
+    ctx->aov_restart = true;                              // the first-hit planes' mean restarts with the next frame (their contents stay)
     return RTGL_OK;
 }
 
@@ -1672,6 +1724,80 @@ extern "C" int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw)
     return RTGL_OK;
 }
 
+// ---- first-hit planes (option "aov") ----------------------------------------------------------------
+// plane bit -> index (0 albedo, 1 normal, 2 position, 3 ids); -1 for anything but one RTGL_AOV_* bit
+static int aov_index(int plane)
+{
+    switch (plane) {
+    case RTGL_AOV_ALBEDO: return 0;
+    case RTGL_AOV_NORMAL: return 1;
+    case RTGL_AOV_POSITION: return 2;
+    case RTGL_AOV_IDS: return 3;
+    default: return -1;
+    }
+}
+static void *aov_plane(const rtgl_context *ctx, int idx) { return idx == 3 ? (void *)ctx->d_aov_ids : (void *)ctx->d_aov[idx]; }
+
+// (re)allocate the enabled planes, zeroed; the mean restarts with the next frame.  The triangle ids are uploaded by the next frame.
+static int set_aov(rtgl_context *ctx, int mask)
+{
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // frames in flight may still write the old planes
+    for (int k = 0; k < 3; ++k) if (ctx->d_aov[k]) { HIPCHK(ctx, hipFree(ctx->d_aov[k])); ctx->d_aov[k] = nullptr; }
+    if (ctx->d_aov_ids) { HIPCHK(ctx, hipFree(ctx->d_aov_ids)); ctx->d_aov_ids = nullptr; }
+    if (!(mask & RTGL_AOV_IDS)) {
+        if (ctx->d_visit_mesh) { HIPCHK(ctx, hipFree(ctx->d_visit_mesh)); ctx->d_visit_mesh = nullptr; }
+        if (ctx->d_visit_tri) { HIPCHK(ctx, hipFree(ctx->d_visit_tri)); ctx->d_visit_tri = nullptr; }
+        ctx->visit_ids_dirty = true;
+    }
+    ctx->opt_aov = 0;
+    const size_t bytes = (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+    for (int k = 0; k < 4; ++k) {
+        if (!(mask & (1 << k))) continue;
+        void *p = nullptr;
+        HIPCHK(ctx, hipMalloc(&p, bytes));
+        if (k == 3) ctx->d_aov_ids = (uint4 *)p; else ctx->d_aov[k] = (float4 *)p;
+        HIPCHK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->opt_aov = mask; ctx->aov_restart = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_aov(rtgl_context *ctx, int plane, void *out)
+{
+    ENTER(ctx);
+    const int idx = aov_index(plane);
+    if (idx < 0) return fail(ctx, RTGL_ERR_INVALID, "plane must be one of RTGL_AOV_ALBEDO, RTGL_AOV_NORMAL, RTGL_AOV_POSITION, RTGL_AOV_IDS");
+    if (!out) return fail(ctx, RTGL_ERR_INVALID, "out is NULL");
+    const size_t row_bytes = (size_t)ctx->width * 16;
+    if (!ctx->parts.empty()) {                          // rows from their owners, global row order
+        std::vector<uint8_t> local;
+        for (rtgl_context *part : ctx->parts) {
+            local.resize((size_t)std::max(part->local_rows, 1) * row_bytes);
+            const int rc = rtgl_read_aov(part, plane, local.data());
+            if (rc) return fail(ctx, rc, part->error);
+            for (int lr = 0; lr < part->local_rows; ++lr)
+                memcpy((uint8_t *)out + (size_t)rtgl_local_row_to_global(part, lr) * row_bytes, local.data() + (size_t)lr * row_bytes, row_bytes);
+        }
+        return RTGL_OK;
+    }
+    const void *src = aov_plane(ctx, idx);
+    if (!src) return fail(ctx, RTGL_ERR_STATE, "this plane is not enabled (option \"aov\")");
+    HIPCHK(ctx, hipMemcpyAsync(out, src, (size_t)ctx->local_rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_aov(rtgl_context *ctx, int plane)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->parts.empty()) { ctx->error = "rtgl_device_aov: a multi-device context holds its planes on every device; use rtgl_read_aov"; return nullptr; }
+    const int idx = aov_index(plane);
+    if (idx < 0) { ctx->error = "rtgl_device_aov: plane must be one RTGL_AOV_* bit"; return nullptr; }
+    if (!aov_plane(ctx, idx)) { ctx->error = "rtgl_device_aov: this plane is not enabled (option \"aov\")"; return nullptr; }
+    return aov_plane(ctx, idx);
+}
+
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
     ENTER(ctx);
@@ -1722,6 +1848,10 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
     } else if (!strcmp(key, "wf_mode")) {
         if (value != kScalar && value != kLds) return fail(ctx, RTGL_ERR_INVALID, "wf_mode must be 0 (scalar) or 1 (lds)");
         ctx->opt_wf_mode = value;
+    } else if (!strcmp(key, "aov")) {
+        if (value < 0 || value > RTGL_AOV_ALL) return fail(ctx, RTGL_ERR_INVALID, "aov must be a mask of RTGL_AOV_ALBEDO | RTGL_AOV_NORMAL | RTGL_AOV_POSITION | RTGL_AOV_IDS (0: off)");
+        const int rc = set_aov(ctx, value);
+        if (rc) return rc;
     } else if (!strcmp(key, "rng_state")) ctx->opt_rng_state = value != 0;
     else if (!strcmp(key, "counters")) ctx->opt_counters = value != 0;
     else if (!strcmp(key, "kernel_timing")) {
@@ -1753,6 +1883,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "scan_dynamic")) *value = ctx->opt_scan_dynamic;
     else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
+    else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
     else if (!strcmp(key, "counters")) *value = ctx->opt_counters;
     else if (!strcmp(key, "kernel_timing")) *value = ctx->opt_kernel_timing;
     else if (!strcmp(key, "cand_region_pairs")) *value = (int)ctx->cand_region_pairs;      // kernel 4: current capacity of one wave's candidate region
@@ -1763,6 +1894,8 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         b += (size_t)ctx->n_tri_visits * (sizeof(TriEdges) + sizeof(TriPlane) + 4 + 112) + (size_t)ctx->n_vec4 * 16 + (size_t)ctx->env_faces * ctx->env_w * ctx->env_h * ctx->env_c;
         if (ctx->d_rng) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         b += ctx->batch_capacity * 16;
+        for (int k = 0; k < 4; ++k) if (ctx->opt_aov & (1 << k)) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+        if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

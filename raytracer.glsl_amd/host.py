@@ -18,6 +18,9 @@ LIB_PATH = os.environ.get("RTGL_AMD_LIB") or os.path.join(PKG_DIR, "librtgl_amd.
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 
 KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1
+# first-hit planes (option "aov", include/rtgl_amd.h): one bit per plane
+AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS = 1, 2, 4, 8
+AOV_ALL = AOV_ALBEDO | AOV_NORMAL | AOV_POSITION | AOV_IDS
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -29,6 +32,7 @@ ABI_SYMBOLS = [
     "rtgl_bind_device_image", "rtgl_set_stream", "rtgl_get_counters", "rtgl_read_rng_state",
     "rtgl_set_option", "rtgl_get_option", "rtgl_last_frame_ms", "rtgl_last_frame_timing",
     "rtgl_accumulated_timing", "rtgl_timing_reset", "rtgl_create_multi", "rtgl_device_count", "rtgl_gather_tiles",
+    "rtgl_read_aov", "rtgl_device_aov",
 ]
 
 
@@ -102,6 +106,8 @@ def load_library() -> C.CDLL:
     L.rtgl_set_stream.argtypes = [vp, vp]
     L.rtgl_get_counters.argtypes = [vp, C.POINTER(CCounters)]
     L.rtgl_read_rng_state.argtypes = [vp, vp]
+    L.rtgl_read_aov.argtypes = [vp, i, vp]
+    L.rtgl_device_aov.argtypes = [vp, i]; L.rtgl_device_aov.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -273,6 +279,21 @@ class Context:
         self._chk(self.lib.rtgl_read_rng_state(self.h, _ptr(out)))
         return out
 
+    # --- first-hit planes
+    def set_aov(self, mask: int):
+        """Enable the planes of `mask` (AOV_* bits; 0 frees them): allocated zeroed, their running mean restarts."""
+        self.set_option("aov", mask)
+
+    def read_aov(self, plane: int) -> np.ndarray:
+        """One plane (a single AOV_* bit) as (local_rows, width, 4): int32 for AOV_IDS, float32 otherwise."""
+        out = np.zeros((self.local_rows, self.width, 4), np.int32 if plane == AOV_IDS else np.float32)
+        self._chk(self.lib.rtgl_read_aov(self.h, int(plane), _ptr(out)))
+        return out
+
+    def device_aov_ptr(self, plane: int) -> int:
+        """Device pointer of one plane (0: see the context's last error)."""
+        return int(self.lib.rtgl_device_aov(self.h, int(plane)) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -301,9 +322,17 @@ class FrameLoop:
 class HeadlessRenderer(FrameLoop):
     """FrameLoop driving a Context: the Python twin of include/rtgl/renderer.h's Renderer."""
 
-    def __init__(self, width: int, height: int, device: int = 0, seed: int = 0, **tiling):
+    def __init__(self, width: int, height: int, device: int = 0, seed: int = 0, aov: int = 0, **tiling):
         super().__init__(seed=seed)
         self.ctx = Context(width, height, device, **tiling)
+        if aov:
+            self.set_aov(aov)
+
+    def set_aov(self, mask: int):
+        self.ctx.set_aov(mask)
+
+    def read_aov(self, plane: int) -> np.ndarray:
+        return self.ctx.read_aov(plane)
 
     def set_scene(self, scene: Scene):
         self.ctx.upload_scene(scene)
