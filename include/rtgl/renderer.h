@@ -370,6 +370,31 @@ public:
         if (!m_ctx || img.size() != (size_t)m_width * rtgl_local_rows(m_ctx) * 4) return false;      // (read_aov has said why)
         return write_pfm(path, img);
     }
+    // ---- denoiser (rtgl_denoise, include/rtgl_amd.h; extension): an edge-avoiding a-trous filter over the image as it stands, guided by the
+    // first-hit planes -- set_aov(RTGL_AOV_ALBEDO | RTGL_AOV_NORMAL | RTGL_AOV_POSITION) before rendering.  nullptr: the documented defaults.
+    // The result is a snapshot in a buffer of its own; the accumulation image is not touched.  Prints and returns false on failure.
+    bool denoise(const rtgl_denoise_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_denoise(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the denoised image, RGBA32F, row 0 = bottom; empty (and a message) before the first successful denoise()
+    std::vector<float> read_denoised() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_denoised_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // ... as a PFM, exactly like save_pfm
+    bool save_denoised_pfm(const std::string &path) const
+    {
+        const std::vector<float> img = read_denoised();
+        if (!m_ctx || img.size() != (size_t)m_width * rtgl_local_rows(m_ctx) * 4) return false;      // (read_denoised has said why)
+        return write_pfm(path, img);
+    }
     // The progressive state: the accumulation image and the frame counters the running mean depends on (u_frames, src/renderer.cpp:98).
     // load_state() into a Renderer of the same size continues exactly where save_state() stopped: the next frame is mixed in with
     // weight 1 / (frames + 1) as if the process had never ended.  (u_random continues from the caller's rand() stream, which is not

@@ -187,6 +187,51 @@ int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw);    /* per local pixe
  * enabled, see rtgl_last_error.  The pointer stays valid until "aov" is set again or the context is destroyed. */
 int rtgl_read_aov(rtgl_context *ctx, int plane, void *out);
 void *rtgl_device_aov(rtgl_context *ctx, int plane);
+
+/* -- denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the accumulation image, guided by the first-hit planes,
+ * with albedo demodulation and the compact polynomial (1 - x/4)^4 in place of exp(-x).  No reference counterpart.  What a caller of a
+ * 1-spp progressive renderer needs for a usable picture after a handful of frames.  The filter uses only + - x / and compares, so it is
+ * DEFINED bit for bit (tests/denoise_mirror.py restates it in numpy): all arithmetic binary32, one rounding per operation, in exactly the
+ * order written here, no contraction, correctly rounded divide.
+ *   Inputs: the image I (RGBA32F) and the planes A (albedo), N (normal), P (position, w = t) as they are on the context's stream when the
+ *   call is enqueued, over all width x height pixels.
+ *   ew(x):  q = (x < 4) ? 1 - 0.25 x : 0;  q = q q;  q = q q;  ew = q   (a NaN x gives 0).      dot3(v) = (v.x v.x + v.y v.y) + v.z v.z.
+ *   h = [1/16, 1/4, 3/8, 1/4, 1/16].
+ *   Demodulation: per channel d = (A > 2^-10) ? A : 2^-10;  c0 = I.rgb / d when RTGL_DENOISE_DEMODULATE is set, else c0 = I.rgb.
+ *   Pass L = 0 .. passes-1, step s = 2^L, per pixel p, c the previous pass's output:
+ *     sig = sigma_color 2^-L;  ic = 1 / (sig sig);  in = 1 / (sigma_normal sigma_normal);  sp = sigma_position P(p).w;
+ *     ip = (sp > 0) ? 1 / (sp sp) : 0      (the position tolerance grows with the hit distance; on a miss, t = 0, the factor sees x = 0 and the
+ *                                           normal term separates hit from miss)
+ *     taps j = -2..2 (rows, outer), i = -2..2 (inner), q = p + (i s, j s); a tap outside the image is skipped:
+ *       w = h[j] h[i];  w = w ew(dot3(c(q) - c(p)) ic);  w = w ew(dot3(N(q).xyz - N(p).xyz) in);  w = w ew(dot3(P(q).xyz - P(p).xyz) ip)
+ *       (a term whose sigma is <= 0 is switched off: its factor is skipped and its plane never read)
+ *       only if w > 0:  acc = acc + w c(q) per channel,  ws = ws + w
+ *     c'(p) = (ws > 0) ? acc / ws : c(p)
+ *   Result: rgb = demodulating ? c d : c,  a = I.a.  passes = 0 without demodulation is the identity, bit for bit.
+ * Defaults (rtgl_denoise_defaults, and a NULL params): passes 5, sigma_color 16, sigma_normal 0.3, sigma_position 0.05, demodulate on.
+ * rtgl_denoise first submits the frames a batching context holds, then enqueues passes kernels on the context's stream and returns without
+ * waiting.  It writes the context's DENOISED buffer (and two scratch buffers; all three allocated by the first call that needs them, freed
+ * with the context) and nothing else: image, planes, RNG states and counters are only read.  The denoised buffer is a snapshot: later
+ * frames do not change or invalidate it; the next rtgl_denoise overwrites it.
+ * RTGL_ERR_INVALID: NULL context, passes > 8, a non-finite sigma, unknown flag bits, non-zero reserved.  RTGL_ERR_STATE: a plane the
+ * parameters need is not enabled (option "aov": A iff demodulating, N iff sigma_normal > 0, P iff sigma_position > 0); a plane is needed
+ * and no frame has been rendered since the planes last restarted; the context is tiled or multi-device (a strip lacks its neighbours'
+ * rows; filtering a gathered image is out of scope).  rtgl_read_denoised_f32 (synchronises; layout of rtgl_read_image_f32) and
+ * rtgl_device_denoised (torch interop; valid until the context is destroyed) return RTGL_ERR_STATE / NULL before the first successful
+ * rtgl_denoise. */
+enum { RTGL_DENOISE_DEMODULATE = 1 };
+typedef struct rtgl_denoise_params {
+    uint32_t passes;          /* 0..8 */
+    float    sigma_color;     /* <= 0: the colour term is off */
+    float    sigma_normal;    /* <= 0: the normal term is off */
+    float    sigma_position;  /* <= 0: the position term is off; relative to the hit distance */
+    uint32_t flags;           /* RTGL_DENOISE_DEMODULATE */
+    uint32_t reserved[3];     /* must be 0 */
+} rtgl_denoise_params;        /* 32 bytes */
+int rtgl_denoise_defaults(rtgl_denoise_params *out);
+int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params);
+int rtgl_read_denoised_f32(rtgl_context *ctx, float *rgba);
+void *rtgl_device_denoised(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -19,6 +19,7 @@
 #include "rt_wavefront.hpp"
 #include "rt_mfma.hpp"
 #include "rt_scan.hpp"
+#include "rt_denoise.hpp"
 
 #pragma clang fp contract(off)
 
@@ -260,6 +261,9 @@ struct rtgl_context {
     // ... and, for the ids plane only, per triangle visit its mesh and its triangle (uploaded while that plane is enabled)
     std::vector<uint32_t> h_visit_mesh, h_visit_tri;
     uint32_t *d_visit_mesh = nullptr, *d_visit_tri = nullptr; bool visit_ids_dirty = true;
+    // rtgl_denoise: two RGBA32F buffers the passes alternate between and the buffer the last pass writes, each local_rows x width records,
+    // allocated by the first call that needs them; has_denoised: a call has succeeded, so the read-out calls have something to return
+    float4 *d_dn_scratch[2] = {nullptr, nullptr}, *d_denoised = nullptr; bool has_denoised = false;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0;
@@ -453,7 +457,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
     void *ptrs[] = { ctx->d_spheres, ctx->d_materials, ctx->d_vertices, ctx->d_sphere_visits, ctx->d_edges, ctx->d_planes,
                      ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
                      ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
-                     ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri };
+                     ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
+                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -1798,6 +1803,95 @@ extern "C" void *rtgl_device_aov(rtgl_context *ctx, int plane)
     return aov_plane(ctx, idx);
 }
 
+// ---- rtgl_denoise: edge-avoiding a-trous filter guided by the first-hit planes (rt_denoise.hpp) --------
+extern "C" int rtgl_denoise_defaults(rtgl_denoise_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->passes = 5; out->sigma_color = 16.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f; out->flags = RTGL_DENOISE_DEMODULATE;
+    return RTGL_OK;
+}
+
+// one pass: 64 columns x (four rows `step` apart) per block, two LDS buffers of nine arrays of 64 + 4 step floats (rt_denoise.hpp)
+template <bool kDemod, bool kRemod>
+static void launch_atrous(rtgl_context *ctx, const AtrousArgs &a)
+{
+    const int s = a.step, wt = 64 + 4 * s;
+    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)(((a.height + 4 * s - 1) / (4 * s)) * s));
+    const size_t lds = (size_t)2 * 9 * wt * sizeof(float);
+    if (wt > 256) hipLaunchKernelGGL((atrous_kernel<kDemod, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
+    else hipLaunchKernelGGL((atrous_kernel<kDemod, kRemod, false>), grid, dim3(256), lds, ctx->stream, a);
+}
+
+extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params)
+{
+    ENTER(ctx);
+    rtgl_denoise_params P;
+    rtgl_denoise_defaults(&P);
+    if (params) P = *params;
+    if (P.passes > 8u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: passes must be 0..8");
+    if (!std::isfinite(P.sigma_color) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: the sigmas must be finite (<= 0 switches a term off)");
+    if (P.flags & ~(uint32_t)RTGL_DENOISE_DEMODULATE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: unknown flag bits");
+    if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
+                                         "render on a single-device context, or filter the gathered image yourself");
+    const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_c = P.sigma_color > 0.0f, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
+    const int need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
+    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: a first-hit plane these parameters need is not enabled (option \"aov\": albedo to demodulate, normal for sigma_normal > 0, position for sigma_position > 0)");
+    if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: no frame has been rendered since the first-hit planes last restarted");
+    const size_t n = (size_t)ctx->local_rows * ctx->width;
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: this context holds no pixels");
+    // pass k of K reads the image (k = 0) or the buffer pass k - 1 wrote, and writes the denoised buffer (k = K - 1) or scratch k & 1
+    if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
+    for (uint32_t k = 0; k < 2u && k + 1u < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
+    AtrousArgs a{};
+    a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
+    a.width = ctx->width; a.height = ctx->local_rows;
+    a.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
+    a.sigma_position = P.sigma_position;
+    a.use_color = use_c; a.use_normal = use_n; a.use_position = use_p;
+    if (P.passes == 0u) {
+        a.src = ctx->d_image; a.dst = ctx->d_denoised;
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (demod) hipLaunchKernelGGL(atrous_identity_kernel<true>, grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(atrous_identity_kernel<false>, grid, dim3(256), 0, ctx->stream, a);
+    }
+    for (uint32_t k = 0; k < P.passes; ++k) {
+        const bool first = k == 0u, last = k + 1u == P.passes;
+        a.src = first ? ctx->d_image : ctx->d_dn_scratch[(k - 1u) & 1u];
+        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[k & 1u];
+        a.step = 1 << k; a.step_log2 = (int)k;
+        const float sig = P.sigma_color * ldexpf(1.0f, -(int)k);
+        a.inv_color = use_c ? 1.0f / (sig * sig) : 0.0f;
+        const bool dm = demod && first, rm = demod && last;
+        if (dm && rm) launch_atrous<true, true>(ctx, a);
+        else if (dm) launch_atrous<true, false>(ctx, a);
+        else if (rm) launch_atrous<false, true>(ctx, a);
+        else launch_atrous<false, false>(ctx, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_denoised = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_denoised_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->has_denoised) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoised_f32: no rtgl_denoise call has succeeded on this context");
+    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_denoised, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_denoised(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_denoised) { ctx->error = "rtgl_device_denoised: no rtgl_denoise call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_denoised;
+}
+
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
     ENTER(ctx);
@@ -1896,6 +1990,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         b += ctx->batch_capacity * 16;
         for (int k = 0; k < 4; ++k) if (ctx->opt_aov & (1 << k)) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
+        for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

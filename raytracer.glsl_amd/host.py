@@ -21,6 +21,9 @@ KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1
 # first-hit planes (option "aov", include/rtgl_amd.h): one bit per plane
 AOV_ALBEDO, AOV_NORMAL, AOV_POSITION, AOV_IDS = 1, 2, 4, 8
 AOV_ALL = AOV_ALBEDO | AOV_NORMAL | AOV_POSITION | AOV_IDS
+# rtgl_denoise (include/rtgl_amd.h): flag bits and the documented defaults
+DENOISE_DEMODULATE = 1
+DENOISE_DEFAULTS = dict(passes=5, sigma_color=16.0, sigma_normal=0.3, sigma_position=0.05, demodulate=True)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -33,6 +36,7 @@ ABI_SYMBOLS = [
     "rtgl_set_option", "rtgl_get_option", "rtgl_last_frame_ms", "rtgl_last_frame_timing",
     "rtgl_accumulated_timing", "rtgl_timing_reset", "rtgl_create_multi", "rtgl_device_count", "rtgl_gather_tiles",
     "rtgl_read_aov", "rtgl_device_aov",
+    "rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised",
 ]
 
 
@@ -58,6 +62,12 @@ class CCounters(C.Structure):
 class CFrameTiming(C.Structure):
     """rtgl_frame_timing"""
     _fields_ = [("frame_ms", C.c_float), ("intersect_ms", C.c_float), ("intersect_launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CDenoiseParams(C.Structure):
+    """rtgl_denoise_params"""
+    _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 def build_library(force: bool = False) -> str:
@@ -108,6 +118,10 @@ def load_library() -> C.CDLL:
     L.rtgl_read_rng_state.argtypes = [vp, vp]
     L.rtgl_read_aov.argtypes = [vp, i, vp]
     L.rtgl_device_aov.argtypes = [vp, i]; L.rtgl_device_aov.restype = vp
+    L.rtgl_denoise_defaults.argtypes = [C.POINTER(CDenoiseParams)]
+    L.rtgl_denoise.argtypes = [vp, C.POINTER(CDenoiseParams)]
+    L.rtgl_read_denoised_f32.argtypes = [vp, vp]
+    L.rtgl_device_denoised.argtypes = [vp]; L.rtgl_device_denoised.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -294,6 +308,34 @@ class Context:
         """Device pointer of one plane (0: see the context's last error)."""
         return int(self.lib.rtgl_device_aov(self.h, int(plane)) or 0)
 
+    # --- denoiser
+    def denoise(self, passes=None, sigma_color=None, sigma_normal=None, sigma_position=None, demodulate=None):
+        """Enqueue the a-trous filter over the image as it stands (rtgl_denoise; does not wait).  An argument left at None keeps the
+        library's default (DENOISE_DEFAULTS); a sigma <= 0 switches its term off."""
+        p = CDenoiseParams()
+        self._chk(self.lib.rtgl_denoise_defaults(C.byref(p)))
+        if passes is not None:
+            p.passes = int(passes)
+        if sigma_color is not None:
+            p.sigma_color = float(sigma_color)
+        if sigma_normal is not None:
+            p.sigma_normal = float(sigma_normal)
+        if sigma_position is not None:
+            p.sigma_position = float(sigma_position)
+        if demodulate is not None:
+            p.flags = (p.flags & ~DENOISE_DEMODULATE) | (DENOISE_DEMODULATE if demodulate else 0)
+        self._chk(self.lib.rtgl_denoise(self.h, C.byref(p)))
+
+    def read_denoised(self) -> np.ndarray:
+        """The denoised buffer of the last denoise() as (local_rows, width, 4) float32, laid out like read_image()."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_denoised_f32(self.h, _ptr(out)))
+        return out
+
+    def device_denoised_ptr(self) -> int:
+        """Device pointer of the denoised buffer (0 before the first successful denoise(): see the context's last error)."""
+        return int(self.lib.rtgl_device_denoised(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -333,6 +375,15 @@ class HeadlessRenderer(FrameLoop):
 
     def read_aov(self, plane: int) -> np.ndarray:
         return self.ctx.read_aov(plane)
+
+    def denoise(self, **params):
+        self.ctx.denoise(**params)
+
+    def read_denoised(self) -> np.ndarray:
+        return self.ctx.read_denoised()
+
+    def device_denoised_ptr(self) -> int:
+        return self.ctx.device_denoised_ptr()
 
     def set_scene(self, scene: Scene):
         self.ctx.upload_scene(scene)
