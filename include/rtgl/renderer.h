@@ -380,7 +380,24 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
-    // the denoised image, RGBA32F, row 0 = bottom; empty (and a message) before the first successful denoise()
+    // ... or the variance-guided filter with its firefly clamp (rtgl_denoise_guided): the same buffer, read with read_denoised().
+    // nullptr: its defaults (passes 5, sigma_lum 4, sigma_normal 0.3, sigma_position 0.05, firefly_ratio 1, demodulate on)
+    bool denoise_guided(const rtgl_denoise_guided_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_denoise_guided(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // {mu, v0, variance after the last pass, s0} per pixel of the last denoise_guided(); empty (and a message) before the first
+    std::vector<float> read_denoise_variance() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_denoise_variance_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // the denoised image, RGBA32F, row 0 = bottom; empty (and a message) before the first successful denoise() or denoise_guided()
     std::vector<float> read_denoised() const
     {
         if (!m_ctx) return {};

@@ -232,6 +232,55 @@ int rtgl_denoise_defaults(rtgl_denoise_params *out);
 int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params);
 int rtgl_read_denoised_f32(rtgl_context *ctx, float *rgba);
 void *rtgl_device_denoised(rtgl_context *ctx);
+
+/* -- variance-guided denoiser: the filter above with the global colour tolerance replaced by a luminance tolerance that follows a per-pixel
+ * variance estimate (after SVGF, Schied et al. 2017, spatial part only), the estimate filtered along with the colour, and a firefly clamp
+ * in front.  A call of its own beside rtgl_denoise; it reads the same inputs and writes the same DENOISED buffer.  DEFINED bit for bit under
+ * the same rules (tests/denoise_guided_mirror.py restates it): binary32, only + - x / compares and selects, one rounding per operation in
+ * the order written, no contraction, correctly rounded divide, rows outer and columns inner, a tap outside the image is skipped.
+ *   ew, dot3, h, d, c0, in, ip and the normal and position factors: as above.     lum(c) = (0.25 c.r + 0.5 c.g) + 0.25 c.b.
+ *   Geometric weight of a tap q of p:  g(q) = 1;  g = g ew(dot3(N(q).xyz - N(p).xyz) in);  g = g ew(dot3(P(q).xyz - P(p).xyz) ip), ip from
+ *     P(p).w  (a term whose sigma is <= 0 is skipped).  A neighbour q = p + (i, j), |i|, |j| <= 1, is NEAR p if it is inside the image and
+ *     g(q) > 0: the clamp and the variance blur below look at near neighbours only, so that nothing reaches p across an edge of the guides.
+ *   Firefly clamp (firefly_ratio > 0), per pixel p: over its up to 8 near neighbours q = p + (i, j), j = -1..1 (outer), i = -1..1,
+ *     (i, j) != (0, 0): m = lum(c0(q)) for the first of them, then m = (lum(c0(q)) > m) ? lum(c0(q)) : m  (a NaN never replaces a number).
+ *     l = lum(c0(p));  k = firefly_ratio m;  if there is a near neighbour and l > k:  s = k / l,  c1(p) = c0(p) s per channel;  else c1(p) = c0(p).
+ *     With the clamp off c1 = c0.
+ *   Spatial variance, per pixel p: taps j = -3..3 (outer), i = -3..3, q = p + (i, j), l(q) = lum(c1(q)):
+ *       only if g(q) > 0 and l(q) - l(q) == 0 (a finite luminance):  s0 = s0 + g,  s1 = s1 + g l(q),  s2 = s2 + g (l(q) l(q))
+ *     if s0 > 0:  mu = s1 / s0;  v = s2 / s0 - mu mu;  v0 = (v > 0) ? v : 0.      else mu = 0, v0 = 0.
+ *   Pass L = 0 .. passes-1, step s = 2^L, per pixel p, c and var the previous pass's output (c1 and v0 for the first):
+ *     vg = vs / vw over p itself and its near neighbours q = p + (i, j), j = -1..1 (outer), i = -1..1, unit spacing whatever the step,
+ *       b = [1/4, 1/2, 1/4]:  w = b[j] b[i];  vs = vs + w var(q),  vw = vw + w
+ *     il = 1 / ((sigma_lum sigma_lum) vg + 2^-20)         (sigma_lum is NOT halved from pass to pass: the variance shrinks by itself)
+ *     taps j = -2..2 (outer), i = -2..2, q = p + (i s, j s):
+ *       dl = lum(c(q)) - lum(c(p));  w = h[j] h[i];  w = w ew((dl dl) il);  then the normal and the position factor as above
+ *       only if w > 0:  acc = acc + w c(q) per channel,  ws = ws + w,  va = va + (w w) var(q)
+ *     c'(p) = (ws > 0) ? acc / ws : c(p);   var'(p) = (ws > 0) ? va / (ws ws) : var(p)
+ *   Result: rgb = demodulating ? c d : c,  a = I.a.  The VARIANCE buffer holds {mu, v0, var after the last pass, s0} per pixel, in the
+ *   image's layout (variances of the demodulated luminance when demodulating).  passes = 0 with the clamp off and without demodulation is
+ *   the identity, bit for bit.
+ * Defaults (rtgl_denoise_guided_defaults, and a NULL params): passes 5, sigma_lum 4, sigma_normal 0.3, sigma_position 0.05, firefly_ratio 1,
+ * demodulate on.
+ * Like rtgl_denoise it first submits the frames a batching context holds, enqueues on the context's stream and returns without waiting; it
+ * writes the denoised buffer (the later of the two calls overwrites the earlier), the two scratch buffers and the variance buffer
+ * (allocated by the first call that needs them, freed with the context) and nothing else.
+ * RTGL_ERR_INVALID: NULL context, passes > 8, a non-finite sigma or ratio, sigma_lum <= 0, unknown flag bits, non-zero reserved.
+ * RTGL_ERR_STATE: exactly the conditions of rtgl_denoise.  rtgl_read_denoise_variance_f32 (synchronises) and rtgl_device_denoise_variance
+ * (valid until the context is destroyed) return RTGL_ERR_STATE / NULL before the first successful rtgl_denoise_guided. */
+typedef struct rtgl_denoise_guided_params {
+    uint32_t passes;          /* 0..8 */
+    float    sigma_lum;       /* > 0: luminance tolerance in standard deviations */
+    float    sigma_normal;    /* <= 0: the normal term is off */
+    float    sigma_position;  /* <= 0: the position term is off; relative to the hit distance */
+    float    firefly_ratio;   /* <= 0: clamp off; else a pixel brighter than ratio x its brightest neighbour is scaled down to that */
+    uint32_t flags;           /* RTGL_DENOISE_DEMODULATE */
+    uint32_t reserved[2];     /* must be 0 */
+} rtgl_denoise_guided_params; /* 32 bytes */
+int rtgl_denoise_guided_defaults(rtgl_denoise_guided_params *out);
+int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_params *params);
+int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba);
+void *rtgl_device_denoise_variance(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -264,6 +264,8 @@ struct rtgl_context {
     // rtgl_denoise: two RGBA32F buffers the passes alternate between and the buffer the last pass writes, each local_rows x width records,
     // allocated by the first call that needs them; has_denoised: a call has succeeded, so the read-out calls have something to return
     float4 *d_dn_scratch[2] = {nullptr, nullptr}, *d_denoised = nullptr; bool has_denoised = false;
+    // rtgl_denoise_guided: shares the three buffers above; its variance buffer {mu, v0, var, s0}, local_rows x width records
+    float4 *d_dn_variance = nullptr; uint32_t *d_dn_near = nullptr; bool has_dn_variance = false;      // (d_dn_near: one word per pixel)
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0;
@@ -458,7 +460,7 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
                      ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
                      ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
                      ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
-                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised };
+                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -1892,6 +1894,96 @@ extern "C" void *rtgl_device_denoised(rtgl_context *ctx)
     return (void *)ctx->d_denoised;
 }
 
+// ---- rtgl_denoise_guided: variance-guided a-trous filter with a firefly clamp (rt_denoise.hpp, guided_*) --------
+extern "C" int rtgl_denoise_guided_defaults(rtgl_denoise_guided_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->passes = 5; out->sigma_lum = 4.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f; out->firefly_ratio = 1.0f; out->flags = RTGL_DENOISE_DEMODULATE;
+    return RTGL_OK;
+}
+
+// one guided pass: the geometry of launch_atrous with ten arrays per LDS buffer
+template <bool kLast, bool kRemod>
+static void launch_guided(rtgl_context *ctx, const GuidedArgs &a)
+{
+    const int s = a.step, wt = 64 + 4 * s;
+    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)(((a.height + 4 * s - 1) / (4 * s)) * s));
+    const size_t lds = (size_t)2 * 10 * wt * sizeof(float);
+    if (wt > 256) hipLaunchKernelGGL((guided_kernel<kLast, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
+    else hipLaunchKernelGGL((guided_kernel<kLast, kRemod, false>), grid, dim3(256), lds, ctx->stream, a);
+}
+
+extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_params *params)
+{
+    ENTER(ctx);
+    rtgl_denoise_guided_params P;
+    rtgl_denoise_guided_defaults(&P);
+    if (params) P = *params;
+    if (P.passes > 8u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: passes must be 0..8");
+    if (!std::isfinite(P.sigma_lum) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position) || !std::isfinite(P.firefly_ratio))
+        return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: the sigmas and the firefly ratio must be finite (<= 0 switches the normal term, the position term or the clamp off)");
+    if (!(P.sigma_lum > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: sigma_lum must be > 0");
+    if (P.flags & ~(uint32_t)RTGL_DENOISE_DEMODULATE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: unknown flag bits");
+    if (P.reserved[0] || P.reserved[1]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
+                                         "render on a single-device context, or filter the gathered image yourself");
+    const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
+    const int need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
+    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: a first-hit plane these parameters need is not enabled (option \"aov\": albedo to demodulate, normal for sigma_normal > 0, position for sigma_position > 0)");
+    if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: no frame has been rendered since the first-hit planes last restarted");
+    const size_t n = (size_t)ctx->local_rows * ctx->width;
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
+    // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer); pass k of K reads scratch k & 1 and writes scratch (k + 1) & 1
+    // or, as the last, the denoised buffer
+    if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
+    if (!ctx->d_dn_variance) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_variance, n * 16));
+    if (!ctx->d_dn_near) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_near, n * 4));
+    for (uint32_t k = 0; k < 2u && k < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
+    GuidedArgs a{};
+    a.image = ctx->d_image; a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
+    a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
+    a.width = ctx->width; a.height = ctx->local_rows;
+    a.lum2 = P.sigma_lum * P.sigma_lum;
+    a.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
+    a.sigma_position = P.sigma_position;
+    a.firefly_ratio = P.firefly_ratio;
+    a.use_clamp = P.firefly_ratio > 0.0f; a.use_normal = use_n; a.use_position = use_p;
+    a.demodulate = demod; a.final_image = P.passes == 0u;
+    a.dst = P.passes == 0u ? ctx->d_denoised : ctx->d_dn_scratch[0];
+    hipLaunchKernelGGL(guided_prepare_kernel, dim3((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4)), dim3(256), kPrepLdsBytes, ctx->stream, a);
+    for (uint32_t k = 0; k < P.passes; ++k) {
+        const bool last = k + 1u == P.passes;
+        a.src = ctx->d_dn_scratch[k & 1u];
+        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[(k + 1u) & 1u];
+        a.step = 1 << k; a.step_log2 = (int)k;
+        if (last && demod) launch_guided<true, true>(ctx, a);
+        else if (last) launch_guided<true, false>(ctx, a);
+        else launch_guided<false, false>(ctx, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_denoised = true; ctx->has_dn_variance = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->has_dn_variance) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoise_variance_f32: no rtgl_denoise_guided call has succeeded on this context");
+    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_dn_variance, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_denoise_variance(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_dn_variance) { ctx->error = "rtgl_device_denoise_variance: no rtgl_denoise_guided call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_dn_variance;
+}
+
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
     ENTER(ctx);
@@ -1990,7 +2082,8 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         b += ctx->batch_capacity * 16;
         for (int k = 0; k < 4; ++k) if (ctx->opt_aov & (1 << k)) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
-        for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+        for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+        if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

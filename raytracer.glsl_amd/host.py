@@ -24,6 +24,8 @@ AOV_ALL = AOV_ALBEDO | AOV_NORMAL | AOV_POSITION | AOV_IDS
 # rtgl_denoise (include/rtgl_amd.h): flag bits and the documented defaults
 DENOISE_DEMODULATE = 1
 DENOISE_DEFAULTS = dict(passes=5, sigma_color=16.0, sigma_normal=0.3, sigma_position=0.05, demodulate=True)
+# rtgl_denoise_guided
+DENOISE_GUIDED_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, firefly_ratio=1.0, demodulate=True)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -37,6 +39,7 @@ ABI_SYMBOLS = [
     "rtgl_accumulated_timing", "rtgl_timing_reset", "rtgl_create_multi", "rtgl_device_count", "rtgl_gather_tiles",
     "rtgl_read_aov", "rtgl_device_aov",
     "rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised",
+    "rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance",
 ]
 
 
@@ -68,6 +71,12 @@ class CDenoiseParams(C.Structure):
     """rtgl_denoise_params"""
     _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class CDenoiseGuidedParams(C.Structure):
+    """rtgl_denoise_guided_params"""
+    _fields_ = [("passes", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("firefly_ratio", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 def build_library(force: bool = False) -> str:
@@ -122,6 +131,10 @@ def load_library() -> C.CDLL:
     L.rtgl_denoise.argtypes = [vp, C.POINTER(CDenoiseParams)]
     L.rtgl_read_denoised_f32.argtypes = [vp, vp]
     L.rtgl_device_denoised.argtypes = [vp]; L.rtgl_device_denoised.restype = vp
+    L.rtgl_denoise_guided_defaults.argtypes = [C.POINTER(CDenoiseGuidedParams)]
+    L.rtgl_denoise_guided.argtypes = [vp, C.POINTER(CDenoiseGuidedParams)]
+    L.rtgl_read_denoise_variance_f32.argtypes = [vp, vp]
+    L.rtgl_device_denoise_variance.argtypes = [vp]; L.rtgl_device_denoise_variance.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -336,6 +349,31 @@ class Context:
         """Device pointer of the denoised buffer (0 before the first successful denoise(): see the context's last error)."""
         return int(self.lib.rtgl_device_denoised(self.h) or 0)
 
+    def denoise_guided(self, passes=None, sigma_lum=None, sigma_normal=None, sigma_position=None, firefly_ratio=None, demodulate=None):
+        """Enqueue the variance-guided filter over the image as it stands (rtgl_denoise_guided; does not wait).  It writes the buffer
+        read_denoised() returns and the variance buffer.  An argument left at None keeps the library's default (DENOISE_GUIDED_DEFAULTS);
+        sigma_normal, sigma_position or firefly_ratio <= 0 switches that term or the clamp off."""
+        p = CDenoiseGuidedParams()
+        self._chk(self.lib.rtgl_denoise_guided_defaults(C.byref(p)))
+        if passes is not None:
+            p.passes = int(passes)
+        for name, value in (("sigma_lum", sigma_lum), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position), ("firefly_ratio", firefly_ratio)):
+            if value is not None:
+                setattr(p, name, float(value))
+        if demodulate is not None:
+            p.flags = (p.flags & ~DENOISE_DEMODULATE) | (DENOISE_DEMODULATE if demodulate else 0)
+        self._chk(self.lib.rtgl_denoise_guided(self.h, C.byref(p)))
+
+    def read_denoise_variance(self) -> np.ndarray:
+        """{mu, v0, variance after the last pass, s0} per pixel of the last denoise_guided(), (local_rows, width, 4) float32."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_denoise_variance_f32(self.h, _ptr(out)))
+        return out
+
+    def device_denoise_variance_ptr(self) -> int:
+        """Device pointer of the variance buffer (0 before the first successful denoise_guided(): see the context's last error)."""
+        return int(self.lib.rtgl_device_denoise_variance(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -378,6 +416,12 @@ class HeadlessRenderer(FrameLoop):
 
     def denoise(self, **params):
         self.ctx.denoise(**params)
+
+    def denoise_guided(self, **params):
+        self.ctx.denoise_guided(**params)
+
+    def read_denoise_variance(self) -> np.ndarray:
+        return self.ctx.read_denoise_variance()
 
     def read_denoised(self) -> np.ndarray:
         return self.ctx.read_denoised()
