@@ -412,6 +412,33 @@ public:
         if (!m_ctx || img.size() != (size_t)m_width * rtgl_local_rows(m_ctx) * 4) return false;      // (read_denoised has said why)
         return write_pfm(path, img);
     }
+    // ---- temporal accumulation (rtgl_temporal_accumulate, include/rtgl_amd.h; extension): the history of the previous view reprojected into
+    // the current one and blended with the image as it stands -- set_aov(RTGL_AOV_NORMAL | RTGL_AOV_POSITION), render every frame with
+    // reset_flag = 1, frames = 0 and call this after it.  nullptr: its defaults (max_history 32, sigma_normal 0.3, sigma_position 0.05).
+    // Prints and returns false on failure.
+    bool temporal_accumulate(const rtgl_temporal_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_temporal_accumulate(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the next temporal_accumulate() starts without history
+    bool temporal_reset()
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_temporal_reset(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
+    std::vector<float> read_temporal() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_temporal_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
     // The progressive state: the accumulation image and the frame counters the running mean depends on (u_frames, src/renderer.cpp:98).
     // load_state() into a Renderer of the same size continues exactly where save_state() stopped: the next frame is mixed in with
     // weight 1 / (frames + 1) as if the process had never ended.  (u_random continues from the caller's rand() stream, which is not

@@ -281,6 +281,69 @@ int rtgl_denoise_guided_defaults(rtgl_denoise_guided_params *out);
 int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_params *params);
 int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba);
 void *rtgl_device_denoise_variance(rtgl_context *ctx);
+
+/* -- temporal accumulation: the accumulated radiance of the previous view reprojected into the current one and blended with the current
+ * frame (the temporal half of SVGF, Schied et al. 2017; the spatial half is rtgl_denoise_guided).  No reference counterpart: the reference
+ * answers a camera move with u_reset_flag, back to 1 spp.  DEFINED bit for bit under the denoisers' rules (tests/temporal_mirror.py restates
+ * it): binary32, only + - x / compares, selects and floor (exact), one rounding per operation in the order written, no contraction,
+ * correctly rounded divide.   ew, dot3, in = 1 / (sigma_normal sigma_normal): as in rtgl_denoise.   dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   Inputs, as they are on the context's stream when the call is enqueued: the image I, the planes N and P, the context's current
+ *   rtgl_frame_params (the CURRENT camera); and from the previous successful call: its output Hp (rgb, a = n), its copies Np, Pp of the
+ *   planes, its camera.  W = width, H = height.
+ *   Camera record, built on the host per call: position, forward, up, right;  hw = (float)tan((double)camera_fov * 0.5);
+ *     asp = (float)height / (float)width;  wd = 2 hw;  ht = 2 (hw asp);  ff = dot(forward, forward), rr = dot(right, right), uu = dot(up, up);
+ *     kx = ff / (wd rr);  ky = ff / (ht uu).   The axes are taken to be mutually orthogonal, as the reference's camera makes them.
+ *   Per pixel p = (px, py):
+ *     hit = P(p).w > 0.   Hit: v = P(p).xyz - position_prev.   Miss: the pixel's own pinhole direction through the CURRENT camera,
+ *       x = ((float)px / (float)W) 2 - 1,  y = ((float)py / (float)H) 2 - 1,  v = (forward + (right wd) x) + (up ht) y per component (the
+ *       background is at infinity: translation is ignored).
+ *     f = dot(v, forward_prev);  sx = ((((dot(v, right_prev) / f) kx_prev) + 1) 0.5) W;  sy = ((((dot(v, up_prev) / f) ky_prev) + 1) 0.5) H.
+ *     There is no history unless f > 0, sx >= -1, sx < W, sy >= -1 and sy < H (a NaN fails).
+ *     x0 = floor(sx), fx = sx - x0;  y0 = floor(sy), fy = sy - y0.
+ *     Taps q = (x0 + i, y0 + j), j = 0, 1 (outer), i = 0, 1;  b = (i ? fx : 1 - fx) (j ? fy : 1 - fy);  a tap outside the image is skipped.
+ *     Static shortcut: when every field of the previous camera record compares equal to the current one's, the four taps are replaced by
+ *       the single tap q = p with b = 1: a camera at rest accumulates a plain per-pixel mean, no resampling blur.
+ *     A tap counts only if its kind matches: (Pp(q).w > 0) == hit.
+ *     Hit:  w = b;  w = w ew(dot3(Np(q).xyz - N(p).xyz) in);  w = w ew(dot3(Pp(q).xyz - P(p).xyz) ip),  sp = sigma_position P(p).w,
+ *       ip = (sp > 0) ? 1 / (sp sp) : 0   (a term whose sigma is <= 0 is skipped).     Miss:  w = b.
+ *     only if w > 0:  acc = acc + w Hp(q).rgb per channel,  na = na + w Hp(q).a,  ws = ws + w
+ *     If there is history and ws > 0:  h = acc / ws;  n = na / ws + 1;  n = (n > max_history) ? max_history : n;  al = 1 / n;
+ *       out = h + (I.rgb - h) al per channel.     Else out = I.rgb, n = 1.
+ *   Stores: {out, n} to the other history buffer; P(p) and, when the normal plane is enabled (whatever sigma_normal), N(p), as read, to the
+ *   other guide copies; the host keeps the camera record.  With sigma_normal <= 0 the normal plane need not be enabled and is then neither
+ *   read nor copied.
+ *   The first call and the first after rtgl_temporal_reset have no history (out = I.rgb, n = 1 everywhere).  The history is dropped in the
+ *   same way when this call needs Np and the previous call stored none because the normal plane was off then.
+ * Defaults (rtgl_temporal_defaults, and a NULL params): max_history 32, sigma_normal 0.3, sigma_position 0.05.
+ * Intended use: render each frame with reset_flag = 1, frames = 0, so that the image ((color + 0 x 0) / (0 + 1) = color) and the planes are that
+ * frame's own; call rtgl_temporal_accumulate after every frame; read the history, or set option "denoise_source" = 1 and denoise it.
+ * Like the denoisers the call first submits the frames a batching context holds, enqueues one kernel on the context's stream and returns
+ * without waiting.  It writes only its own buffers (two history buffers, two copies of the position plane and two of the normal plane,
+ * allocated by the first call that needs them, freed with the context): image, planes, RNG states, counters, the denoised and the
+ * variance buffer are only read.
+ * RTGL_ERR_INVALID: NULL context, a non-finite parameter, max_history < 1, non-zero flags or reserved words.  RTGL_ERR_STATE:
+ * RTGL_AOV_POSITION is not enabled; RTGL_AOV_NORMAL is not enabled while sigma_normal > 0; no frame has been rendered since the planes last
+ * restarted; the context is tiled or multi-device.  rtgl_read_temporal_f32 (synchronises; layout of rtgl_read_image_f32; a = the history
+ * length n) and rtgl_device_temporal return RTGL_ERR_STATE / NULL before the first successful rtgl_temporal_accumulate.  The two history
+ * buffers take turns: rtgl_device_temporal names the one the LATEST call wrote, so ask again after each call.
+ * Option "denoise_source": 0 (default) rtgl_denoise and rtgl_denoise_guided filter the image; 1 they take the latest history buffer wherever
+ * they take the image (the result's alpha is then the history length) and return RTGL_ERR_STATE while no rtgl_temporal_accumulate has
+ * succeeded; any other value is RTGL_ERR_INVALID.
+ * Limits: static scenes only (no motion vectors: re-uploaded geometry is caught by the position test alone); mirrors and glass reproject
+ * by their first hit; with depth of field the position is the jittered ray's hit; a NaN radiance stays in a pixel's history until a reset
+ * or a disocclusion. */
+typedef struct rtgl_temporal_params {
+    float    max_history;     /* >= 1: the history length is capped here (the blend factor is never below 1 / max_history) */
+    float    sigma_normal;    /* <= 0: the normal test is off (the normal plane is then not needed) */
+    float    sigma_position;  /* <= 0: the position test is off; relative to the current hit distance, as in rtgl_denoise */
+    uint32_t flags;           /* none defined: must be 0 */
+    uint32_t reserved[4];     /* must be 0 */
+} rtgl_temporal_params;       /* 32 bytes */
+int rtgl_temporal_defaults(rtgl_temporal_params *out);
+int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *params);
+int rtgl_temporal_reset(rtgl_context *ctx);                 /* the next rtgl_temporal_accumulate starts without history */
+int rtgl_read_temporal_f32(rtgl_context *ctx, float *rgba);
+void *rtgl_device_temporal(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads
@@ -290,7 +353,7 @@ void *rtgl_device_denoise_variance(rtgl_context *ctx);
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"
  * (cull 3: a bounce's queue is binned when at least this many rays are expected, default 131072), "mf_group_quads" (quads
  * sharing one local origin: a power of two up to 64; changing it rebuilds the broad-phase data at the next frame),
- * "rng_state", "counters", "aov" (first-hit planes, above), "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
+ * "rng_state", "counters", "aov" (first-hit planes, above), "denoise_source" (what the denoisers filter, above: 0 the image, 1 the temporal history), "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
  * event pairs around its dominant-kernel launches), "frame_batch" (1 (default) .. 16, also RTGL_AMD_FRAME_BATCH: with B > 1 rtgl_render_frame
  * only records the frame until B frames are waiting, then traces them in ONE set of launches and applies their results to the image in
  * frame order -- bit-identical to frame-by-frame, B times the rays per launch (what a rank of a multi-GPU run lacks).  Every other entry

@@ -20,6 +20,7 @@
 #include "rt_mfma.hpp"
 #include "rt_scan.hpp"
 #include "rt_denoise.hpp"
+#include "rt_temporal.hpp"
 
 #pragma clang fp contract(off)
 
@@ -266,9 +267,15 @@ struct rtgl_context {
     float4 *d_dn_scratch[2] = {nullptr, nullptr}, *d_denoised = nullptr; bool has_denoised = false;
     // rtgl_denoise_guided: shares the three buffers above; its variance buffer {mu, v0, var, s0}, local_rows x width records
     float4 *d_dn_variance = nullptr; uint32_t *d_dn_near = nullptr; bool has_dn_variance = false;      // (d_dn_near: one word per pixel)
+    // rtgl_temporal_accumulate: two history buffers {rgb, n} and two copies each of the position and the normal plane, taking turns;
+    // tm_cur: the set the latest call wrote.  has_temporal: a call has succeeded (read-out, "denoise_source"); tm_valid: the next call
+    // may reproject from set tm_cur (false after rtgl_temporal_reset); tm_has_normal: that set holds a copy of the normal plane
+    float4 *d_tm_hist[2] = {nullptr, nullptr}, *d_tm_normal[2] = {nullptr, nullptr}, *d_tm_position[2] = {nullptr, nullptr};
+    int tm_cur = 0; bool has_temporal = false, tm_valid = false, tm_has_normal = false;
+    TemporalCamera tm_camera{};
     FrameParams params{};
     bool have_params = false;
-    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0;
+    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0;
 };
 
 static int fail(rtgl_context *ctx, int code, const std::string &msg)
@@ -460,7 +467,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
                      ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
                      ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
                      ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
-                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near };
+                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near,
+                     ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -1814,6 +1822,14 @@ extern "C" int rtgl_denoise_defaults(rtgl_denoise_params *out)
     return RTGL_OK;
 }
 
+// what the two denoisers filter: the accumulation image, or (option "denoise_source" = 1) the latest history buffer of
+// rtgl_temporal_accumulate; NULL: there is none yet
+static const float4 *denoise_input(const rtgl_context *ctx)
+{
+    if (ctx->opt_denoise_source == 0) return ctx->d_image;
+    return ctx->has_temporal ? ctx->d_tm_hist[ctx->tm_cur] : nullptr;
+}
+
 // one pass: 64 columns x (four rows `step` apart) per block, two LDS buffers of nine arrays of 64 + 4 step floats (rt_denoise.hpp)
 template <bool kDemod, bool kRemod>
 static void launch_atrous(rtgl_context *ctx, const AtrousArgs &a)
@@ -1844,6 +1860,8 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
     if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: no frame has been rendered since the first-hit planes last restarted");
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: this context holds no pixels");
+    const float4 *input = denoise_input(ctx);
+    if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
     // pass k of K reads the image (k = 0) or the buffer pass k - 1 wrote, and writes the denoised buffer (k = K - 1) or scratch k & 1
     if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
     for (uint32_t k = 0; k < 2u && k + 1u < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
@@ -1854,14 +1872,14 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
     a.sigma_position = P.sigma_position;
     a.use_color = use_c; a.use_normal = use_n; a.use_position = use_p;
     if (P.passes == 0u) {
-        a.src = ctx->d_image; a.dst = ctx->d_denoised;
+        a.src = input; a.dst = ctx->d_denoised;
         const dim3 grid((unsigned)((n + 255) / 256));
         if (demod) hipLaunchKernelGGL(atrous_identity_kernel<true>, grid, dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(atrous_identity_kernel<false>, grid, dim3(256), 0, ctx->stream, a);
     }
     for (uint32_t k = 0; k < P.passes; ++k) {
         const bool first = k == 0u, last = k + 1u == P.passes;
-        a.src = first ? ctx->d_image : ctx->d_dn_scratch[(k - 1u) & 1u];
+        a.src = first ? input : ctx->d_dn_scratch[(k - 1u) & 1u];
         a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[k & 1u];
         a.step = 1 << k; a.step_log2 = (int)k;
         const float sig = P.sigma_color * ldexpf(1.0f, -(int)k);
@@ -1935,6 +1953,8 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: no frame has been rendered since the first-hit planes last restarted");
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
+    const float4 *input = denoise_input(ctx);
+    if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
     // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer); pass k of K reads scratch k & 1 and writes scratch (k + 1) & 1
     // or, as the last, the denoised buffer
     if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
@@ -1942,7 +1962,7 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     if (!ctx->d_dn_near) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_near, n * 4));
     for (uint32_t k = 0; k < 2u && k < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
     GuidedArgs a{};
-    a.image = ctx->d_image; a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
+    a.image = input; a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
     a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
     a.width = ctx->width; a.height = ctx->local_rows;
     a.lum2 = P.sigma_lum * P.sigma_lum;
@@ -1982,6 +2002,118 @@ extern "C" void *rtgl_device_denoise_variance(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->has_dn_variance) { ctx->error = "rtgl_device_denoise_variance: no rtgl_denoise_guided call has succeeded on this context"; return nullptr; }
     return (void *)ctx->d_dn_variance;
+}
+
+// ---- rtgl_temporal_accumulate: reprojected history across camera moves (rt_temporal.hpp) --------
+extern "C" int rtgl_temporal_defaults(rtgl_temporal_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->max_history = 32.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f;
+    return RTGL_OK;
+}
+
+// the camera record of include/rtgl_amd.h ("temporal accumulation"): binary32, one rounding per operation, the tangent in double
+static TemporalCamera temporal_camera(const FrameParams &P, int width, int height)
+{
+    auto dot = [](const float *a, const float *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    TemporalCamera c{};
+    for (int k = 0; k < 3; ++k) { c.pos[k] = P.cam_pos[k]; c.fwd[k] = P.cam_forward[k]; c.up[k] = P.cam_up[k]; c.right[k] = P.cam_right[k]; }
+    c.hw = (float)tan((double)P.cam_fov * 0.5);
+    c.asp = (float)height / (float)width;
+    c.wd = 2.0f * c.hw;
+    c.ht = 2.0f * (c.hw * c.asp);
+    c.ff = dot(c.fwd, c.fwd); c.rr = dot(c.right, c.right); c.uu = dot(c.up, c.up);
+    c.kx = c.ff / (c.wd * c.rr);
+    c.ky = c.ff / (c.ht * c.uu);
+    return c;
+}
+static bool temporal_camera_equal(const TemporalCamera &a, const TemporalCamera &b)
+{
+    const float *x = a.pos, *y = b.pos;                   // (a NaN field compares unequal: no shortcut then)
+    for (size_t k = 0; k < sizeof(TemporalCamera) / sizeof(float); ++k) if (!(x[k] == y[k])) return false;
+    return true;
+}
+
+template <bool kHistory, bool kStatic>
+static void launch_temporal(rtgl_context *ctx, const TemporalArgs &a, bool use_n, bool use_p)
+{
+    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
+    if (!kHistory) hipLaunchKernelGGL((temporal_kernel<false, false, false, false>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n && use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, true>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, false>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, false>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *params)
+{
+    ENTER(ctx);
+    rtgl_temporal_params P;
+    rtgl_temporal_defaults(&P);
+    if (params) P = *params;
+    if (!std::isfinite(P.max_history) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: max_history and the sigmas must be finite (a sigma <= 0 switches its test off)");
+    if (!(P.max_history >= 1.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: max_history must be >= 1");
+    if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: no flag bits are defined");
+    if (P.reserved[0] || P.reserved[1] || P.reserved[2] || P.reserved[3]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a tiled or multi-device context holds strips; a reprojected pixel may come from another strip, which is out of scope: "
+                                         "render on a single-device context");
+    const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
+    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0);
+    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0)");
+    if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: no frame has been rendered since the first-hit planes last restarted");
+    const size_t n = (size_t)ctx->local_rows * ctx->width;
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: this context holds no pixels");
+    const bool with_normal = (ctx->opt_aov & RTGL_AOV_NORMAL) != 0;      // the normal plane is copied whenever it is on, tested or not
+    for (int k = 0; k < 2; ++k) {
+        if (!ctx->d_tm_hist[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_hist[k], n * 16));
+        if (!ctx->d_tm_position[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_position[k], n * 16));
+        if (with_normal && !ctx->d_tm_normal[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_normal[k], n * 16));
+    }
+    const TemporalCamera cam = temporal_camera(ctx->params, ctx->width, ctx->height);
+    const bool history = ctx->tm_valid && !(use_n && !ctx->tm_has_normal);
+    const int from = ctx->tm_cur, to = ctx->has_temporal ? from ^ 1 : from;             // the two sets take turns
+    TemporalArgs a{};
+    a.image = ctx->d_image; a.position = ctx->d_aov[2]; a.normal = with_normal ? ctx->d_aov[1] : nullptr;
+    a.hist_prev = ctx->d_tm_hist[from]; a.position_prev = ctx->d_tm_position[from]; a.normal_prev = ctx->d_tm_normal[from];
+    a.hist_out = ctx->d_tm_hist[to]; a.position_out = ctx->d_tm_position[to]; a.normal_out = ctx->d_tm_normal[to];
+    a.width = ctx->width; a.height = ctx->local_rows;
+    a.cur = cam; a.prev = ctx->tm_camera;
+    a.max_history = P.max_history;
+    a.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
+    a.sigma_position = P.sigma_position;
+    if (!history) launch_temporal<false, false>(ctx, a, use_n, use_p);
+    else if (temporal_camera_equal(cam, ctx->tm_camera)) launch_temporal<true, true>(ctx, a, use_n, use_p);
+    else launch_temporal<true, false>(ctx, a, use_n, use_p);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->tm_cur = to; ctx->tm_camera = cam; ctx->tm_has_normal = with_normal;
+    ctx->tm_valid = true; ctx->has_temporal = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_temporal_reset(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    ctx->tm_valid = false;                                // (the latest buffer stays readable)
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_temporal_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_f32: no rtgl_temporal_accumulate call has succeeded on this context");
+    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_tm_hist[ctx->tm_cur], (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_temporal(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_temporal) { ctx->error = "rtgl_device_temporal: no rtgl_temporal_accumulate call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_tm_hist[ctx->tm_cur];
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
@@ -2038,6 +2170,9 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
         if (value < 0 || value > RTGL_AOV_ALL) return fail(ctx, RTGL_ERR_INVALID, "aov must be a mask of RTGL_AOV_ALBEDO | RTGL_AOV_NORMAL | RTGL_AOV_POSITION | RTGL_AOV_IDS (0: off)");
         const int rc = set_aov(ctx, value);
         if (rc) return rc;
+    } else if (!strcmp(key, "denoise_source")) {
+        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "denoise_source must be 0 (the accumulation image) or 1 (the latest history buffer of rtgl_temporal_accumulate)");
+        ctx->opt_denoise_source = value;
     } else if (!strcmp(key, "rng_state")) ctx->opt_rng_state = value != 0;
     else if (!strcmp(key, "counters")) ctx->opt_counters = value != 0;
     else if (!strcmp(key, "kernel_timing")) {
@@ -2070,6 +2205,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
     else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
+    else if (!strcmp(key, "denoise_source")) *value = ctx->opt_denoise_source;
     else if (!strcmp(key, "counters")) *value = ctx->opt_counters;
     else if (!strcmp(key, "kernel_timing")) *value = ctx->opt_kernel_timing;
     else if (!strcmp(key, "cand_region_pairs")) *value = (int)ctx->cand_region_pairs;      // kernel 4: current capacity of one wave's candidate region
@@ -2084,6 +2220,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
         for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
+        for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

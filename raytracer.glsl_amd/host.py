@@ -26,6 +26,8 @@ DENOISE_DEMODULATE = 1
 DENOISE_DEFAULTS = dict(passes=5, sigma_color=16.0, sigma_normal=0.3, sigma_position=0.05, demodulate=True)
 # rtgl_denoise_guided
 DENOISE_GUIDED_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, firefly_ratio=1.0, demodulate=True)
+# rtgl_temporal_accumulate
+TEMPORAL_DEFAULTS = dict(max_history=32.0, sigma_normal=0.3, sigma_position=0.05)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -40,6 +42,7 @@ ABI_SYMBOLS = [
     "rtgl_read_aov", "rtgl_device_aov",
     "rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised",
     "rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance",
+    "rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal",
 ]
 
 
@@ -77,6 +80,12 @@ class CDenoiseGuidedParams(C.Structure):
     """rtgl_denoise_guided_params"""
     _fields_ = [("passes", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
                 ("firefly_ratio", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CTemporalParams(C.Structure):
+    """rtgl_temporal_params"""
+    _fields_ = [("max_history", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
 
 
 def build_library(force: bool = False) -> str:
@@ -135,6 +144,11 @@ def load_library() -> C.CDLL:
     L.rtgl_denoise_guided.argtypes = [vp, C.POINTER(CDenoiseGuidedParams)]
     L.rtgl_read_denoise_variance_f32.argtypes = [vp, vp]
     L.rtgl_device_denoise_variance.argtypes = [vp]; L.rtgl_device_denoise_variance.restype = vp
+    L.rtgl_temporal_defaults.argtypes = [C.POINTER(CTemporalParams)]
+    L.rtgl_temporal_accumulate.argtypes = [vp, C.POINTER(CTemporalParams)]
+    L.rtgl_temporal_reset.argtypes = [vp]
+    L.rtgl_read_temporal_f32.argtypes = [vp, vp]
+    L.rtgl_device_temporal.argtypes = [vp]; L.rtgl_device_temporal.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -374,6 +388,33 @@ class Context:
         """Device pointer of the variance buffer (0 before the first successful denoise_guided(): see the context's last error)."""
         return int(self.lib.rtgl_device_denoise_variance(self.h) or 0)
 
+    # --- temporal accumulation
+    def temporal_accumulate(self, max_history=None, sigma_normal=None, sigma_position=None):
+        """Enqueue one step of the reprojected history (rtgl_temporal_accumulate; does not wait): the previous call's history carried
+        through the previous camera into the view of the current frame parameters and blended with the image as it stands.  An argument
+        left at None keeps the library's default (TEMPORAL_DEFAULTS); a sigma <= 0 switches its test off."""
+        p = CTemporalParams()
+        self._chk(self.lib.rtgl_temporal_defaults(C.byref(p)))
+        for name, value in (("max_history", max_history), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position)):
+            if value is not None:
+                setattr(p, name, float(value))
+        self._chk(self.lib.rtgl_temporal_accumulate(self.h, C.byref(p)))
+
+    def temporal_reset(self):
+        """The next temporal_accumulate() starts without history."""
+        self._chk(self.lib.rtgl_temporal_reset(self.h))
+
+    def read_temporal(self) -> np.ndarray:
+        """The history the last temporal_accumulate() wrote as (local_rows, width, 4) float32: rgb and the history length n."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_temporal_f32(self.h, _ptr(out)))
+        return out
+
+    def device_temporal_ptr(self) -> int:
+        """Device pointer of the history buffer the LATEST temporal_accumulate() wrote (two buffers take turns: ask after each call;
+        0 before the first successful call: see the context's last error)."""
+        return int(self.lib.rtgl_device_temporal(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -428,6 +469,18 @@ class HeadlessRenderer(FrameLoop):
 
     def device_denoised_ptr(self) -> int:
         return self.ctx.device_denoised_ptr()
+
+    def temporal_accumulate(self, **params):
+        self.ctx.temporal_accumulate(**params)
+
+    def temporal_reset(self):
+        self.ctx.temporal_reset()
+
+    def read_temporal(self) -> np.ndarray:
+        return self.ctx.read_temporal()
+
+    def device_temporal_ptr(self) -> int:
+        return self.ctx.device_temporal_ptr()
 
     def set_scene(self, scene: Scene):
         self.ctx.upload_scene(scene)
