@@ -439,6 +439,15 @@ public:
         if (rtgl_read_temporal_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
         return img;
     }
+    // the luminance moments {m1, m2, v, n} of the history (rtgl_set_option(context(), "temporal_moments", 1 or 2) before temporal_accumulate()), RGBA32F,
+    // row 0 = bottom; empty (and a message) unless the latest successful temporal_accumulate() stored moments
+    std::vector<float> read_temporal_moments() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_temporal_moments_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
     // The progressive state: the accumulation image and the frame counters the running mean depends on (u_frames, src/renderer.cpp:98).
     // load_state() into a Renderer of the same size continues exactly where save_state() stopped: the next frame is mixed in with
     // weight 1 / (frames + 1) as if the process had never ended.  (u_random continues from the caller's rand() stream, which is not

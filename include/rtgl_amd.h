@@ -344,6 +344,40 @@ int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *para
 int rtgl_temporal_reset(rtgl_context *ctx);                 /* the next rtgl_temporal_accumulate starts without history */
 int rtgl_read_temporal_f32(rtgl_context *ctx, float *rgba);
 void *rtgl_device_temporal(rtgl_context *ctx);
+
+/* -- temporal luminance moments: the first and second moment of each frame's luminance carried through the reprojection above with the
+ * same taps, weights and blend as the colour, so that rtgl_denoise_guided can be guided by the variance the frames themselves showed
+ * instead of one estimated from 49 neighbours of the averaged picture (SVGF's temporal variance).  Two options, both 0 by default; with
+ * both at 0 every call above does exactly what it does without them.  DEFINED bit for bit under the same rules
+ * (tests/temporal_moments_mirror.py restates it): binary32, one rounding per operation in the order written, no contraction.
+ * Option "temporal_moments": 0 off; 1, 2: rtgl_temporal_accumulate also maintains a MOMENTS record {m1, m2, v, n} per pixel, in two buffers
+ * that take turns together with the history buffers (allocated by the first call that needs them, freed with the context); any other value
+ * is RTGL_ERR_INVALID.  Per pixel p, with the quantities of the contract above:
+ *     x = I.rgb (mode 1)   or   x = I.rgb / d per channel, d = (A > 2^-10) ? A : 2^-10 from the albedo plane, as rtgl_denoise (mode 2)
+ *     l = (0.25 x.r + 0.5 x.g) + 0.25 x.b;   ll = l l
+ *   in the tap loop, wherever a tap contributes (w > 0; the tap's record Mp(q) is loaded only then):  a1 = a1 + w Mp(q).x;  a2 = a2 + w Mp(q).y
+ *   if there is history and ws > 0, al being the colour's blend factor:
+ *     h1 = a1 / ws;  h2 = a2 / ws;   m1 = h1 + (l - h1) al;   m2 = h2 + (ll - h2) al
+ *   else m1 = l, m2 = ll.
+ *     v = m2 - m1 m1;   v = (v > 0) ? v : 0   (a NaN gives 0: v is never a NaN);   the record is {m1, m2, v, n}, n the history length.
+ *   The history {out, n} is bit for bit what the call writes with the option off.  Mode 2 needs RTGL_AOV_ALBEDO enabled
+ *   (RTGL_ERR_STATE otherwise).  Setting the option to a value different from its current one acts like rtgl_temporal_reset: moments and
+ *   colour history always have the same age.  v is the biased sample variance of the frames in the history (times (n - 1) / n of the
+ *   unbiased one for a plain mean of n frames).
+ *   rtgl_read_temporal_moments_f32 (synchronises; layout of rtgl_read_image_f32) and rtgl_device_temporal_moments (the buffer the LATEST
+ *   call wrote: ask again after each call) return RTGL_ERR_STATE / NULL unless the latest successful rtgl_temporal_accumulate stored
+ *   moments; a NULL context is RTGL_ERR_INVALID / NULL.
+ * Option "denoise_variance": 0 the spatial estimate of rtgl_denoise_guided; 1 the temporal one where the history allows; any other value is
+ * RTGL_ERR_INVALID.  rtgl_denoise ignores it.  With 1, rtgl_denoise_guided changes only how v0 is chosen, M being the latest moments record
+ * at p and mu, v0s (the v0 of the contract above) and s0 computed exactly as there:
+ *     t = (M.w >= 4) and (M.x - M.x == 0) and (M.y - M.y == 0);     v0 = t ? M.z / M.w : v0s
+ *   Dividing by the history length makes v0 the variance of the history MEAN, which is what is being filtered; 4 is SVGF's threshold.  Clamp,
+ *   passes, vg, the result and the variance buffer {mu, v0, var, s0} follow from that v0, unchanged.  The call then returns
+ *   RTGL_ERR_STATE if "denoise_source" is not 1, if the latest rtgl_temporal_accumulate stored no moments, or if the stored mode does not
+ *   match the call: mode 2 iff RTGL_DENOISE_DEMODULATE is set, mode 1 iff it is not.
+ *   Limit: the firefly clamp does not rescale the v0 of a pixel it scaled down; the over-estimate only widens that pixel's tolerance. */
+int rtgl_read_temporal_moments_f32(rtgl_context *ctx, float *rgba);
+void *rtgl_device_temporal_moments(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads
@@ -353,7 +387,7 @@ void *rtgl_device_temporal(rtgl_context *ctx);
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"
  * (cull 3: a bounce's queue is binned when at least this many rays are expected, default 131072), "mf_group_quads" (quads
  * sharing one local origin: a power of two up to 64; changing it rebuilds the broad-phase data at the next frame),
- * "rng_state", "counters", "aov" (first-hit planes, above), "denoise_source" (what the denoisers filter, above: 0 the image, 1 the temporal history), "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
+ * "rng_state", "counters", "aov" (first-hit planes, above), "denoise_source" (what the denoisers filter, above: 0 the image, 1 the temporal history), "temporal_moments" and "denoise_variance" (temporal luminance moments, above), "kernel_timing" (0 off; N > 0: every N-th frame since the last rtgl_timing_reset carries HIP
  * event pairs around its dominant-kernel launches), "frame_batch" (1 (default) .. 16, also RTGL_AMD_FRAME_BATCH: with B > 1 rtgl_render_frame
  * only records the frame until B frames are waiting, then traces them in ONE set of launches and applies their results to the image in
  * frame order -- bit-identical to frame-by-frame, B times the rays per launch (what a rank of a multi-GPU run lacks).  Every other entry

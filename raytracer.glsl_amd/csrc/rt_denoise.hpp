@@ -207,6 +207,8 @@ constexpr int kPrepW0 = 72, kPrepH0 = 12, kPrepW1 = 70, kPrepH1 = 10;
 constexpr int kPrepN0 = kPrepW0 * kPrepH0, kPrepN1 = kPrepW1 * kPrepH1;
 constexpr size_t kPrepLdsBytes = (size_t)(10 * kPrepN0 + kPrepN1) * sizeof(float);
 
+// (guided_prepare_tvar_kernel below repeats this body with the temporal select added: a change here belongs there too; with every
+// history shorter than 4 the two give the same bits, which tests/test_gpu_temporal_moments.py runs)
 __global__ void __launch_bounds__(256) guided_prepare_kernel(GuidedArgs a)
 {
     extern __shared__ float seg[];                                   // 10 x [12][72], origin (x0 - 4, y0 - 4); then [10][70], origin (x0 - 3, y0 - 3)
@@ -315,6 +317,138 @@ __global__ void __launch_bounds__(256) guided_prepare_kernel(GuidedArgs a)
         const float v = s2 / s0 - mu * mu;
         v0 = (v > 0.0f) ? v : 0.0f;
     }
+    f3 c = mk(c0r[ec], c0g[ec], c0b[ec]);
+    store_through(a.variance + p, mu, v0, v0, s0);                    // (read by the last pass / the caller: rt_wavefront.hpp, store_through)
+    store_through(a.near + p, near);                                  // (read by the passes)
+    if (a.final_image) {
+        if (a.demodulate) { const f3 d = atrous_divisor(a.albedo[p]); c = mk(c.x * d.x, c.y * d.y, c.z * d.z); }
+        store_through(a.dst + p, c.x, c.y, c.z, a.image[p].w);
+    } else {
+        store_through(a.dst + p, c.x, c.y, c.z, v0);
+    }
+}
+
+struct GuidedTvarArgs {
+    GuidedArgs g;
+    const float4 *moments;    // records {m1, m2, v, n} of the latest rtgl_temporal_accumulate (rt_temporal.hpp)
+};
+
+// guided_prepare_kernel with option "denoise_variance" = 1: the same tile, staging, clamp and 7 x 7 window (mu, s0 and the spatial v0 are
+// still wanted); then v0 becomes the variance of the history mean, M.z / M.w of the pixel's moments record, where the history is at least
+// 4 long and the record's moments are finite.  One more 16-byte load per pixel and a select.  A kernel of its own beside
+// guided_prepare_kernel, not a shared body, so that the code generated for the option-off kernel stays exactly what it was.
+__global__ void __launch_bounds__(256) guided_prepare_tvar_kernel(GuidedTvarArgs ta)
+{
+    const GuidedArgs &a = ta.g;
+    extern __shared__ float seg[];                                   // 10 x [12][72], origin (x0 - 4, y0 - 4); then [10][70], origin (x0 - 3, y0 - 3)
+    float *c0r = seg, *c0g = seg + kPrepN0, *c0b = seg + 2 * kPrepN0, *l0 = seg + 3 * kPrepN0, *gn = seg + 4 * kPrepN0, *gp = seg + 7 * kPrepN0;
+    float *l1 = seg + 10 * kPrepN0;
+    const int tid = (int)threadIdx.x, lane = tid & 63, k = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int x0 = (int)blockIdx.x * 64, y0 = (int)blockIdx.y * 4;
+    // the geometric weight between the staged pixel at word e (its normal n, position pos and 1 / (sigma_position t)^2) and the one o words on
+    auto geometric = [&](int e, int o, const f3 &n, const f3 &pos, float inv_pos) {
+        float g = 1.0f;
+        if (a.use_normal) g = g * atrous_ew(atrous_dot3(gn[e + o] - n.x, gn[kPrepN0 + e + o] - n.y, gn[2 * kPrepN0 + e + o] - n.z) * a.inv_normal);
+        if (a.use_position) g = g * atrous_ew(atrous_dot3(gp[e + o] - pos.x, gp[kPrepN0 + e + o] - pos.y, gp[2 * kPrepN0 + e + o] - pos.z) * inv_pos);
+        return g;
+    };
+    for (int e = tid; e < kPrepN0; e += 256) {
+        const int cy = e / kPrepW0, cx = e - cy * kPrepW0, qx = x0 - 4 + cx, qy = y0 - 4 + cy;
+        if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) {
+            const size_t q = (size_t)qy * (size_t)a.width + (size_t)qx;
+            const float4 v = a.image[q];
+            f3 c = mk(v.x, v.y, v.z);
+            if (a.demodulate) { const f3 d = atrous_divisor(a.albedo[q]); c = mk(c.x / d.x, c.y / d.y, c.z / d.z); }
+            c0r[e] = c.x; c0g[e] = c.y; c0b[e] = c.z; l0[e] = guided_lum(c.x, c.y, c.z);
+            if (a.use_normal) { const float4 u = a.normal[q]; gn[e] = u.x; gn[kPrepN0 + e] = u.y; gn[2 * kPrepN0 + e] = u.z; }
+            if (a.use_position) { const float4 u = a.position[q]; gp[e] = u.x; gp[kPrepN0 + e] = u.y; gp[2 * kPrepN0 + e] = u.z; }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < kPrepN1; e += 256) {
+        const int cy = e / kPrepW1, cx = e - cy * kPrepW1, qx = x0 - 3 + cx, qy = y0 - 3 + cy;
+        if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) {
+            const int e0 = (cy + 1) * kPrepW0 + (cx + 1);
+            float l = l0[e0];
+            if (a.use_clamp) {
+                f3 n = mk(0.0f, 0.0f, 0.0f), pos = mk(0.0f, 0.0f, 0.0f);
+                float inv_pos = 0.0f;
+                if (a.use_normal) n = mk(gn[e0], gn[kPrepN0 + e0], gn[2 * kPrepN0 + e0]);
+                if (a.use_position) {
+                    pos = mk(gp[e0], gp[kPrepN0 + e0], gp[2 * kPrepN0 + e0]);
+                    const float sp = a.sigma_position * a.position[(size_t)qy * (size_t)a.width + (size_t)qx].w;
+                    inv_pos = (sp > 0.0f) ? 1.0f / (sp * sp) : 0.0f;
+                }
+                float m = 0.0f;
+                bool have = false;
+#pragma unroll
+                for (int j = -1; j <= 1; ++j)
+#pragma unroll
+                    for (int i = -1; i <= 1; ++i) {
+                        if (i == 0 && j == 0) continue;
+                        const int nx = qx + i, ny = qy + j, o = j * kPrepW0 + i;
+                        if (nx < 0 || nx >= a.width || ny < 0 || ny >= a.height) continue;
+                        if (!(geometric(e0, o, n, pos, inv_pos) > 0.0f)) continue;
+                        const float lq = l0[e0 + o];
+                        m = have ? (lq > m ? lq : m) : lq;
+                        have = true;
+                    }
+                const float kk = a.firefly_ratio * m;
+                if (have && l > kk) {
+                    const float s = kk / l;
+                    const f3 c = mk(c0r[e0] * s, c0g[e0] * s, c0b[e0] * s);
+                    l = guided_lum(c.x, c.y, c.z);
+                    c0r[e0] = c.x; c0g[e0] = c.y; c0b[e0] = c.z;       // (no other thread reads the colour of this pixel before the barrier)
+                }
+            }
+            l1[e] = l;
+        }
+    }
+    __syncthreads();
+    const int x = x0 + lane, y = y0 + k;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+    const int ec = (k + 4) * kPrepW0 + lane + 4;
+    const float *b = l1 + (k + 3) * kPrepW1 + lane + 3;
+    f3 n = mk(0.0f, 0.0f, 0.0f), pos = mk(0.0f, 0.0f, 0.0f);
+    float inv_pos = 0.0f;
+    if (a.use_normal) n = mk(gn[ec], gn[kPrepN0 + ec], gn[2 * kPrepN0 + ec]);
+    if (a.use_position) {
+        pos = mk(gp[ec], gp[kPrepN0 + ec], gp[2 * kPrepN0 + ec]);
+        const float sp = a.sigma_position * a.position[p].w;
+        inv_pos = (sp > 0.0f) ? 1.0f / (sp * sp) : 0.0f;
+    }
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    uint32_t near = 1u << 4;                                          // (the pixel itself always counts)
+#pragma unroll
+    for (int j = -3; j <= 3; ++j) {
+        const int qy = y + j;
+        if (qy < 0 || qy >= a.height) continue;
+#pragma unroll
+        for (int i = -3; i <= 3; ++i) {
+            const int qx = x + i;
+            // (a column outside the image was never staged: g and lq are then whatever LDS held, and `in` discards them.  No branch: the
+            // lanes at the image's edge run in lockstep with the rest of their wave, so skipping their taps would save nothing)
+            const float g = geometric(ec, j * kPrepW0 + i, n, pos, inv_pos);
+            const float lq = b[j * kPrepW1 + i];
+            const bool in = qx >= 0 && qx < a.width && g > 0.0f;
+            if (in && j >= -1 && j <= 1 && i >= -1 && i <= 1) near |= 1u << (3 * (j + 1) + (i + 1));
+            if (in && lq - lq == 0.0f) {
+                s0 = s0 + g;
+                s1 = s1 + g * lq;
+                s2 = s2 + g * (lq * lq);
+            }
+        }
+    }
+    float mu = 0.0f, v0 = 0.0f;
+    if (s0 > 0.0f) {
+        mu = s1 / s0;
+        const float v = s2 / s0 - mu * mu;
+        v0 = (v > 0.0f) ? v : 0.0f;
+    }
+    const float4 M = ta.moments[p];
+    const bool t = M.w >= 4.0f && M.x - M.x == 0.0f && M.y - M.y == 0.0f;
+    v0 = t ? M.z / M.w : v0;
     f3 c = mk(c0r[ec], c0g[ec], c0b[ec]);
     store_through(a.variance + p, mu, v0, v0, s0);                    // (read by the last pass / the caller: rt_wavefront.hpp, store_through)
     store_through(a.near + p, near);                                  // (read by the passes)

@@ -273,9 +273,12 @@ struct rtgl_context {
     float4 *d_tm_hist[2] = {nullptr, nullptr}, *d_tm_normal[2] = {nullptr, nullptr}, *d_tm_position[2] = {nullptr, nullptr};
     int tm_cur = 0; bool has_temporal = false, tm_valid = false, tm_has_normal = false;
     TemporalCamera tm_camera{};
+    // option "temporal_moments": two buffers of records {m1, m2, v, n} that take turns with the history's (set tm_cur), allocated by the
+    // first call that needs them; tm_moments: the mode (1, 2) whose records the latest successful call stored in set tm_cur, 0: none
+    float4 *d_tm_moments[2] = {nullptr, nullptr}; int tm_moments = 0;
     FrameParams params{};
     bool have_params = false;
-    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0;
+    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
 };
 
 static int fail(rtgl_context *ctx, int code, const std::string &msg)
@@ -468,7 +471,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
                      ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
                      ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
                      ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near,
-                     ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1] };
+                     ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1],
+                     ctx->d_tm_moments[0], ctx->d_tm_moments[1] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -1955,6 +1959,13 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
     const float4 *input = denoise_input(ctx);
     if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
+    const bool tvar = ctx->opt_denoise_variance == 1;
+    if (tvar) {
+        if (ctx->opt_denoise_source != 1) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and \"denoise_source\" is not: the temporal variance is that of the history");
+        if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the latest rtgl_temporal_accumulate stored no moments (option \"temporal_moments\")");
+        if (ctx->tm_moments != (demod ? 2 : 1))
+            return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the stored moments are of the other kind: RTGL_DENOISE_DEMODULATE needs \"temporal_moments\" = 2, a call without it 1");
+    }
     // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer); pass k of K reads scratch k & 1 and writes scratch (k + 1) & 1
     // or, as the last, the denoised buffer
     if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
@@ -1972,7 +1983,12 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     a.use_clamp = P.firefly_ratio > 0.0f; a.use_normal = use_n; a.use_position = use_p;
     a.demodulate = demod; a.final_image = P.passes == 0u;
     a.dst = P.passes == 0u ? ctx->d_denoised : ctx->d_dn_scratch[0];
-    hipLaunchKernelGGL(guided_prepare_kernel, dim3((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4)), dim3(256), kPrepLdsBytes, ctx->stream, a);
+    const dim3 prep_grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
+    if (tvar) {
+        GuidedTvarArgs t{};
+        t.g = a; t.moments = ctx->d_tm_moments[ctx->tm_cur];
+        hipLaunchKernelGGL(guided_prepare_tvar_kernel, prep_grid, dim3(256), kPrepLdsBytes, ctx->stream, t);
+    } else hipLaunchKernelGGL(guided_prepare_kernel, prep_grid, dim3(256), kPrepLdsBytes, ctx->stream, a);
     for (uint32_t k = 0; k < P.passes; ++k) {
         const bool last = k + 1u == P.passes;
         a.src = ctx->d_dn_scratch[k & 1u];
@@ -2046,6 +2062,24 @@ static void launch_temporal(rtgl_context *ctx, const TemporalArgs &a, bool use_n
     else hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, false>), grid, dim3(256), 0, ctx->stream, a);
 }
 
+template <bool kHistory, bool kStatic, bool kDemod>
+static void launch_temporal_moments(rtgl_context *ctx, const TemporalMomentsArgs &a, bool use_n, bool use_p)
+{
+    const dim3 grid((unsigned)((a.t.width + 63) / 64), (unsigned)((a.t.height + 3) / 4));
+    if (!kHistory) hipLaunchKernelGGL((temporal_moments_kernel<false, false, false, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n && use_p) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, true, true, kDemod>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, true, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_p) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, false, true, kDemod>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, false, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
+}
+template <bool kDemod>
+static void launch_temporal_moments(rtgl_context *ctx, const TemporalMomentsArgs &a, bool history, bool at_rest, bool use_n, bool use_p)
+{
+    if (!history) launch_temporal_moments<false, false, kDemod>(ctx, a, use_n, use_p);
+    else if (at_rest) launch_temporal_moments<true, true, kDemod>(ctx, a, use_n, use_p);
+    else launch_temporal_moments<true, false, kDemod>(ctx, a, use_n, use_p);
+}
+
 extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *params)
 {
     ENTER(ctx);
@@ -2060,8 +2094,9 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
         return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a tiled or multi-device context holds strips; a reprojected pixel may come from another strip, which is out of scope: "
                                          "render on a single-device context");
     const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0);
-    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0)");
+    const int moments = ctx->opt_temporal_moments;
+    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0) | (moments == 2 ? RTGL_AOV_ALBEDO : 0);
+    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0, albedo for \"temporal_moments\" = 2)");
     if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: no frame has been rendered since the first-hit planes last restarted");
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: this context holds no pixels");
@@ -2070,6 +2105,7 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
         if (!ctx->d_tm_hist[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_hist[k], n * 16));
         if (!ctx->d_tm_position[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_position[k], n * 16));
         if (with_normal && !ctx->d_tm_normal[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_normal[k], n * 16));
+        if (moments && !ctx->d_tm_moments[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_moments[k], n * 16));
     }
     const TemporalCamera cam = temporal_camera(ctx->params, ctx->width, ctx->height);
     const bool history = ctx->tm_valid && !(use_n && !ctx->tm_has_normal);
@@ -2083,10 +2119,19 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
     a.max_history = P.max_history;
     a.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
     a.sigma_position = P.sigma_position;
-    if (!history) launch_temporal<false, false>(ctx, a, use_n, use_p);
-    else if (temporal_camera_equal(cam, ctx->tm_camera)) launch_temporal<true, true>(ctx, a, use_n, use_p);
+    const bool at_rest = history && temporal_camera_equal(cam, ctx->tm_camera);
+    if (moments) {                                        // (a change of the option dropped the history: what set `from` holds is of this mode)
+        TemporalMomentsArgs m{};
+        m.t = a; m.albedo = moments == 2 ? ctx->d_aov[0] : nullptr;
+        m.mom_prev = ctx->d_tm_moments[from]; m.mom_out = ctx->d_tm_moments[to];
+        if (moments == 2) launch_temporal_moments<true>(ctx, m, history, at_rest, use_n, use_p);
+        else launch_temporal_moments<false>(ctx, m, history, at_rest, use_n, use_p);
+    }
+    else if (!history) launch_temporal<false, false>(ctx, a, use_n, use_p);
+    else if (at_rest) launch_temporal<true, true>(ctx, a, use_n, use_p);
     else launch_temporal<true, false>(ctx, a, use_n, use_p);
     HIPCHK(ctx, hipGetLastError());
+    ctx->tm_moments = moments;
     ctx->tm_cur = to; ctx->tm_camera = cam; ctx->tm_has_normal = with_normal;
     ctx->tm_valid = true; ctx->has_temporal = true;
     return RTGL_OK;
@@ -2114,6 +2159,23 @@ extern "C" void *rtgl_device_temporal(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->has_temporal) { ctx->error = "rtgl_device_temporal: no rtgl_temporal_accumulate call has succeeded on this context"; return nullptr; }
     return (void *)ctx->d_tm_hist[ctx->tm_cur];
+}
+
+extern "C" int rtgl_read_temporal_moments_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_moments_f32: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")");
+    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_tm_moments[ctx->tm_cur], (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_temporal_moments(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->tm_moments) { ctx->error = "rtgl_device_temporal_moments: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")"; return nullptr; }
+    return (void *)ctx->d_tm_moments[ctx->tm_cur];
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
@@ -2173,6 +2235,13 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
     } else if (!strcmp(key, "denoise_source")) {
         if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "denoise_source must be 0 (the accumulation image) or 1 (the latest history buffer of rtgl_temporal_accumulate)");
         ctx->opt_denoise_source = value;
+    } else if (!strcmp(key, "temporal_moments")) {
+        if (value < 0 || value > 2) return fail(ctx, RTGL_ERR_INVALID, "temporal_moments must be 0 (off), 1 (luminance moments of the radiance) or 2 (of the radiance divided by the albedo)");
+        if (value != ctx->opt_temporal_moments) ctx->tm_valid = false;       // moments and colour history always have the same age
+        ctx->opt_temporal_moments = value;
+    } else if (!strcmp(key, "denoise_variance")) {
+        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "denoise_variance must be 0 (the spatial estimate) or 1 (the temporal moments where the history is long enough)");
+        ctx->opt_denoise_variance = value;
     } else if (!strcmp(key, "rng_state")) ctx->opt_rng_state = value != 0;
     else if (!strcmp(key, "counters")) ctx->opt_counters = value != 0;
     else if (!strcmp(key, "kernel_timing")) {
@@ -2206,6 +2275,8 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
     else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
     else if (!strcmp(key, "denoise_source")) *value = ctx->opt_denoise_source;
+    else if (!strcmp(key, "temporal_moments")) *value = ctx->opt_temporal_moments;
+    else if (!strcmp(key, "denoise_variance")) *value = ctx->opt_denoise_variance;
     else if (!strcmp(key, "counters")) *value = ctx->opt_counters;
     else if (!strcmp(key, "kernel_timing")) *value = ctx->opt_kernel_timing;
     else if (!strcmp(key, "cand_region_pairs")) *value = (int)ctx->cand_region_pairs;      // kernel 4: current capacity of one wave's candidate region
@@ -2220,7 +2291,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
         for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
-        for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+        for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1], ctx->d_tm_moments[0], ctx->d_tm_moments[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

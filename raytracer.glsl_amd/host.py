@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised",
     "rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance",
     "rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal",
+    "rtgl_read_temporal_moments_f32", "rtgl_device_temporal_moments",
 ]
 
 
@@ -149,6 +150,8 @@ def load_library() -> C.CDLL:
     L.rtgl_temporal_reset.argtypes = [vp]
     L.rtgl_read_temporal_f32.argtypes = [vp, vp]
     L.rtgl_device_temporal.argtypes = [vp]; L.rtgl_device_temporal.restype = vp
+    L.rtgl_read_temporal_moments_f32.argtypes = [vp, vp]
+    L.rtgl_device_temporal_moments.argtypes = [vp]; L.rtgl_device_temporal_moments.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -415,6 +418,18 @@ class Context:
         0 before the first successful call: see the context's last error)."""
         return int(self.lib.rtgl_device_temporal(self.h) or 0)
 
+    def read_temporal_moments(self) -> np.ndarray:
+        """The luminance moments {m1, m2, v, n} the last temporal_accumulate() stored (option "temporal_moments" 1 or 2) as
+        (local_rows, width, 4) float32."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_temporal_moments_f32(self.h, _ptr(out)))
+        return out
+
+    def device_temporal_moments_ptr(self) -> int:
+        """Device pointer of the moments buffer the LATEST temporal_accumulate() wrote (two buffers take turns with the history's; 0 unless
+        that call stored moments: see the context's last error)."""
+        return int(self.lib.rtgl_device_temporal_moments(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -481,6 +496,12 @@ class HeadlessRenderer(FrameLoop):
 
     def device_temporal_ptr(self) -> int:
         return self.ctx.device_temporal_ptr()
+
+    def read_temporal_moments(self) -> np.ndarray:
+        return self.ctx.read_temporal_moments()
+
+    def device_temporal_moments_ptr(self) -> int:
+        return self.ctx.device_temporal_moments_ptr()
 
     def set_scene(self, scene: Scene):
         self.ctx.upload_scene(scene)
