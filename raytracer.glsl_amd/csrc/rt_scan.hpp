@@ -592,12 +592,26 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     unsigned long long c_culled = 0;                           // kCount: ray x triangle pairs the keep bits spared this wave (static launches)
     typedef const float __attribute__((address_space(4))) *ConstFloats;       // group records: uniform index => s_load
     typedef const uint32_t __attribute__((address_space(4))) *ConstWords;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef const volatile f32x4 __attribute__((address_space(4))) *ConstGroupHalf;   // half a group record (MfGroup: 32 bytes, 16-byte aligned)
     const ConstFloats groups_k = (ConstFloats)(uintptr_t)mf.groups;
     const uint32_t l_lane = (uint32_t)half * 32u + (uint32_t)col;              // this lane's row inside a tile (uint4 index)
 
     // rays of one granule as they sit in the queue: both lane halves hold the same ray
     float4 nxt_a[S], nxt_b[S];
     auto fetch_rays = [&](uint32_t g, float4 (&da)[S], float4 (&db)[S]) {
+        // a full granule (wave-uniform test; all but the queue's last one): the eight loads back to back, ONE round trip.  Under the
+        // per-set guard below every set is an EXEC-masked block of its own that waits for its two loads before the next one starts:
+        // four dependent round trips per segment.  (Unconditional loads from clamped slots + a select would do for the last granule,
+        // too, but cost every two-wave variant spilled registers.)
+        if (g * 128u + 128u <= n_rays) {
+            const uint32_t slot0 = g * 128u + (uint32_t)col;
+#pragma unroll
+            for (int s = 0; s < S; ++s) da[s] = qin.a[slot0 + (uint32_t)s * 32u];
+#pragma unroll
+            for (int s = 0; s < S; ++s) db[s] = qin.b[slot0 + (uint32_t)s * 32u];
+            return;
+        }
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const uint32_t slot = g * 128u + (uint32_t)s * 32u + (uint32_t)col;
@@ -864,14 +878,17 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
                 // nothing, not even its setup
                 Mask128 seg = m128_and(m128_shr(keep, ts0), m128_low(ts1 - ts0));
                 if (!m128_any(seg)) { ts0 = ts1; continue; }
+                // the group record first (two scalar loads): it travels beside the rays instead of behind them.  (Volatile: the compiler
+                // sinks plain loads behind the ray fetch, to their first use, where they start only when the rays have arrived.)
+                const ConstGroupHalf gp = (ConstGroupHalf)(groups_k + (size_t)grp * (sizeof(MfGroup) / 4));
+                const f32x4 g_lo = gp[0], g_hi = gp[1];
+                MfGroup G;
+                G.cx = g_lo.x; G.cy = g_lo.y; G.cz = g_lo.z; G.E = g_lo.w; G.Ml = g_hi.x; G.Pw = g_hi.y; G.P = g_hi.z; G.pad1 = 0.0f;
                 if constexpr (W == 2) {                          // nothing ray-related stays live across the tile loop: re-read the queue here
                     fetch_rays(g, nxt_a, nxt_b);
 #pragma unroll
                     for (int s = 0; s < S; ++s) prepare_ray(ray[s], nxt_a[s], nxt_b[s], wave_slot0 + (uint32_t)s * 32u + (uint32_t)col < n_rays);
                 }
-                const ConstFloats gp = groups_k + (size_t)grp * (sizeof(MfGroup) / 4);
-                MfGroup G;
-                G.cx = gp[0]; G.cy = gp[1]; G.cz = gp[2]; G.E = gp[3]; G.Ml = gp[4]; G.Pw = gp[5]; G.P = gp[6]; G.pad1 = 0.0f;
                 u32x4 Bs[S]; float ths[S];
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
@@ -890,6 +907,13 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
                 }
                 B0 = Bs[0]; B1 = Bs[1]; B2 = Bs[2]; B3 = Bs[3];
                 th0 = ths[0]; th1 = ths[1]; th2 = ths[2]; th3 = ths[3];
+#if defined(RT_SOLO_STAMPS) && RT_SOLO_STAMPS == 1
+                // the segment's set-up ends here: ray fetch (two waves per SIMD), group record, B operands and thresholds.  (The operands
+                // are pinned in front of the stamp: nothing but data flow orders the clock read against the arithmetic.)
+                asm volatile("" : "+v"(B0), "+v"(B1), "+v"(B2), "+v"(B3), "+v"(th0), "+v"(th1), "+v"(th2), "+v"(th3));
+#endif
+                RT_STAMP(ts_g1);
+                RT_STAMP_ADD(tt_group, ts_g0, ts_g1);
                 typedef const uint4 __attribute__((address_space(3))) *LdsRow;
                 const uint32_t n_kept = m128_popc(seg);
                 if (n_kept == ts1 - ts0 && debug_skip_exact != 3) {     // (debug_skip_exact = 3: timing diagnostics, every segment through the list loop)

@@ -438,8 +438,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
         if (hipMemcpy(h, ctx->d_dbg_log, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
             for (int b = 0; b < 64 && h[16 * b + 8]; ++b) {
                 const unsigned long long *d = h + 16 * b; const double tot = (double)d[0];
-                fprintf(stderr, "rtgl stamps bounce %2d: waves %llu iters %llu  cycles/wave %.0f  staging %.1f%% rays %.1f%% group+prologue %.1f%% steady %.1f%% (park %.1f%%) flush %.1f%%  cycles per tile-stage in steady %.1f  slowest wave of a launch (mean over launches) %.0f  culled items %llu at %.0f cycles\n",
-                        b, d[8], d[7], tot / d[8], 100.0 * d[1] / tot, 100.0 * d[2] / tot, 100.0 * d[3] / tot, 100.0 * d[4] / tot, 100.0 * d[5] / tot, 100.0 * d[6] / tot,
+                fprintf(stderr, "rtgl stamps bounce %2d: waves %llu iters %llu  cycles/wave %.0f  staging %.1f%% rays %.1f%% segments %.1f%% (of the wave: set-up %.1f%%, park %.1f%%) flush %.1f%%  cycles per tile-stage in steady %.1f  slowest wave of a launch (mean over launches) %.0f  culled items %llu at %.0f cycles\n",
+                        b, d[8], d[7], tot / d[8], 100.0 * d[1] / tot, 100.0 * d[2] / tot, 100.0 * d[4] / tot, 100.0 * d[3] / tot, 100.0 * d[5] / tot, 100.0 * d[6] / tot,
                         d[9] ? (double)d[4] / (double)d[9] : 0.0, (double)d[13] * (double)d[15] / (double)d[8], d[12], d[12] ? (double)d[11] / (double)d[12] : 0.0);
             }
 #if RT_SOLO_STAMPS == 3
