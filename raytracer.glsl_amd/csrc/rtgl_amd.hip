@@ -2051,33 +2051,24 @@ static bool temporal_camera_equal(const TemporalCamera &a, const TemporalCamera 
     return true;
 }
 
-template <bool kHistory, bool kStatic>
-static void launch_temporal(rtgl_context *ctx, const TemporalArgs &a, bool use_n, bool use_p)
+// kMom: option "temporal_moments"; its argument record is TemporalArgs (0) or TemporalMomentsArgs (1, 2)
+template <int kMom, bool kHistory, bool kStatic>
+static void launch_temporal(rtgl_context *ctx, const typename TemporalArgsOf<kMom>::type &a, bool use_n, bool use_p)
 {
-    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
-    if (!kHistory) hipLaunchKernelGGL((temporal_kernel<false, false, false, false>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_n && use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, true>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_n) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, false>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, true>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, false>), grid, dim3(256), 0, ctx->stream, a);
+    const TemporalArgs &t = temporal_base(a);
+    const dim3 grid((unsigned)((t.width + 63) / 64), (unsigned)((t.height + 3) / 4));
+    if (!kHistory) hipLaunchKernelGGL((temporal_kernel<false, false, false, false, kMom>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n && use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, true, kMom>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_n) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, false, kMom>), grid, dim3(256), 0, ctx->stream, a);
+    else if (use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, true, kMom>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((temporal_kernel<true, kStatic, false, false, kMom>), grid, dim3(256), 0, ctx->stream, a);
 }
-
-template <bool kHistory, bool kStatic, bool kDemod>
-static void launch_temporal_moments(rtgl_context *ctx, const TemporalMomentsArgs &a, bool use_n, bool use_p)
+template <int kMom>
+static void launch_temporal(rtgl_context *ctx, const typename TemporalArgsOf<kMom>::type &a, bool history, bool at_rest, bool use_n, bool use_p)
 {
-    const dim3 grid((unsigned)((a.t.width + 63) / 64), (unsigned)((a.t.height + 3) / 4));
-    if (!kHistory) hipLaunchKernelGGL((temporal_moments_kernel<false, false, false, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_n && use_p) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, true, true, kDemod>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_n) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, true, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
-    else if (use_p) hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, false, true, kDemod>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((temporal_moments_kernel<true, kStatic, false, false, kDemod>), grid, dim3(256), 0, ctx->stream, a);
-}
-template <bool kDemod>
-static void launch_temporal_moments(rtgl_context *ctx, const TemporalMomentsArgs &a, bool history, bool at_rest, bool use_n, bool use_p)
-{
-    if (!history) launch_temporal_moments<false, false, kDemod>(ctx, a, use_n, use_p);
-    else if (at_rest) launch_temporal_moments<true, true, kDemod>(ctx, a, use_n, use_p);
-    else launch_temporal_moments<true, false, kDemod>(ctx, a, use_n, use_p);
+    if (!history) launch_temporal<kMom, false, false>(ctx, a, use_n, use_p);
+    else if (at_rest) launch_temporal<kMom, true, true>(ctx, a, use_n, use_p);
+    else launch_temporal<kMom, true, false>(ctx, a, use_n, use_p);
 }
 
 extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *params)
@@ -2124,12 +2115,10 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
         TemporalMomentsArgs m{};
         m.t = a; m.albedo = moments == 2 ? ctx->d_aov[0] : nullptr;
         m.mom_prev = ctx->d_tm_moments[from]; m.mom_out = ctx->d_tm_moments[to];
-        if (moments == 2) launch_temporal_moments<true>(ctx, m, history, at_rest, use_n, use_p);
-        else launch_temporal_moments<false>(ctx, m, history, at_rest, use_n, use_p);
+        if (moments == 2) launch_temporal<2>(ctx, m, history, at_rest, use_n, use_p);
+        else launch_temporal<1>(ctx, m, history, at_rest, use_n, use_p);
     }
-    else if (!history) launch_temporal<false, false>(ctx, a, use_n, use_p);
-    else if (at_rest) launch_temporal<true, true>(ctx, a, use_n, use_p);
-    else launch_temporal<true, false>(ctx, a, use_n, use_p);
+    else launch_temporal<0>(ctx, a, history, at_rest, use_n, use_p);
     HIPCHK(ctx, hipGetLastError());
     ctx->tm_moments = moments;
     ctx->tm_cur = to; ctx->tm_camera = cam; ctx->tm_has_normal = with_normal;

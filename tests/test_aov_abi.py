@@ -9,9 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from resource_report import report
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rtgl_amd.h")
-CSRC = os.path.join(ROOT, "raytracer.glsl_amd", "csrc")
 
 
 def header_text():
@@ -71,19 +72,7 @@ def test_facade_aov_accessors_compile_with_the_host_compiler(tmp_path):
 
 @pytest.fixture(scope="module")
 def resource_report():
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep, cur = {}, None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 # the instances that write the planes: the last template argument (kAov) is true

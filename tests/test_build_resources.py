@@ -7,32 +7,16 @@ established).  Spills come and go with small source changes, so they are pinned 
 two-wave variants (culled bounces since round 3) may spill in their prologue only (bounded here: 2 registers shipping, 12 counting), and every variant must fit its register budget: 256 per wave with two
 waves per SIMD, the whole file (512) with one.
 """
-import os
 import re
-import subprocess
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracer.glsl_amd", "csrc")
+from resource_report import report
 
 
 @pytest.fixture(scope="module")
 def resource_report():
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    text = out.stdout + out.stderr
-    rep = {}
-    cur = None
-    for line in text.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def scan_variants(rep):

@@ -1,31 +1,16 @@
 """Resource usage of ray binning's move (rt_wavefront.hpp, sort_place_kernel; rt_scan.hpp, packet_cull_kernel's gather), from the
 compiler's own report (no GPU needed: hipcc cross-compiles).  The gather loads and stores every ray of a binned queue inside packet
 culling; it must cost that kernel neither a spill nor its five waves per SIMD."""
-import os
 import re
-import subprocess
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracer.glsl_amd", "csrc")
+from resource_report import report
 
 
 @pytest.fixture(scope="module")
 def resource_report():
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep = {}
-    cur = None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def kernel(rep, name):

@@ -10,9 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from resource_report import report
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rtgl_amd.h")
-CSRC = os.path.join(ROOT, "raytracer.glsl_amd", "csrc")
 ENTRY_POINTS = ["rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised"]
 ERR_INVALID = -1
 
@@ -107,19 +108,7 @@ def test_facade_denoise_methods_compile_with_the_host_compiler(tmp_path):
 
 @pytest.fixture(scope="module")
 def resource_report():
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep, cur = {}, None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def test_atrous_kernel_instances_spill_nothing(resource_report):

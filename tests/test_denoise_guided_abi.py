@@ -10,10 +10,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from resource_report import report
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rtgl_amd.h")
 FACADE = os.path.join(ROOT, "include", "rtgl", "renderer.h")
-CSRC = os.path.join(ROOT, "raytracer.glsl_amd", "csrc")
 ENTRY_POINTS = ["rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance"]
 DEFAULTS_TEXT = r"passes 5, sigma_lum (\d+), sigma_normal 0\.3, sigma_position 0\.05, firefly_ratio 1,\s+(?:\*\s+|//\s+)?demodulate on"
 ERR_INVALID = -1
@@ -110,21 +111,7 @@ def test_facade_methods_compile_with_the_host_compiler(tmp_path):
 
 @pytest.fixture(scope="module")
 def resource_report():
-    """The compiler's resource remarks of every kernel (`make asm`, as tests/test_denoise_abi.py does: a device-only compile of the
-    library's one translation unit, the slow part of this module; it rewrites the ignored csrc/rtgl_amd.gfx950.s and nothing else)."""
-    out =subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep, cur = {}, None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def test_guided_kernel_instances_spill_nothing(resource_report):

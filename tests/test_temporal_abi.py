@@ -10,10 +10,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from resource_report import report
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rtgl_amd.h")
 FACADE = os.path.join(ROOT, "include", "rtgl", "renderer.h")
-CSRC = os.path.join(ROOT, "raytracer.glsl_amd", "csrc")
 ENTRY_POINTS = ["rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal"]
 DEFAULTS_TEXT = r"max_history (\d+), sigma_normal 0\.3, sigma_position 0\.05"
 ERR_INVALID = -1
@@ -113,28 +114,15 @@ def test_facade_methods_compile_with_the_host_compiler(tmp_path):
 
 @pytest.fixture(scope="module")
 def resource_report():
-    """The compiler's resource remarks of every kernel (`make asm`, as tests/test_denoise_guided_abi.py does: a device-only compile of the
-    library's one translation unit, the slow part of this module; it rewrites the ignored csrc/rtgl_amd.gfx950.s and nothing else)."""
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep, cur = {}, None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def test_temporal_kernel_instances_spill_nothing(resource_report):
-    """temporal_kernel<history, static shortcut, normal test, position test>: the instance without history and all eight with it"""
+    """temporal_kernel<history, static shortcut, normal test, position test, moments mode>, the mode-0 instances (option "temporal_moments"
+    off; modes 1 and 2: tests/test_temporal_moments_abi.py): the instance without history and all eight with it"""
     found = {}
     for name, r in resource_report.items():
-        m = re.match(r"_ZN2rt15temporal_kernelILb([01])ELb([01])ELb([01])ELb([01])EEEvNS_12TemporalArgsE$", name)
+        m = re.match(r"_ZN2rt15temporal_kernelILb([01])ELb([01])ELb([01])ELb([01])ELi0EEEv", name)
         if m:
             found[tuple(int(g) for g in m.groups())] = r
     assert sorted(found) == [(0, 0, 0, 0)] + [(1, s, n, p) for s in (0, 1) for n in (0, 1) for p in (0, 1)], sorted(resource_report)

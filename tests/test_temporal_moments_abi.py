@@ -1,7 +1,7 @@
 """Temporal luminance moments (options "temporal_moments" and "denoise_variance", include/rtgl_amd.h) at the ABI level, without a GPU: the
 header, the library, the Python binding and the facade agree on the two read-out calls; the calls reject a NULL context before touching a
-device; the facade's method compiles with the host compiler; and the new kernels spill nothing and keep the occupancy of their siblings
-(compiler resource report; hipcc cross-compiles)."""
+device; the facade's method compiles with the host compiler; and the kernel instances with the options on spill nothing and keep the
+occupancy of the option-off ones (compiler resource report; hipcc cross-compiles)."""
 import ctypes as C
 import os
 import re
@@ -10,7 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_temporal_abi import CSRC, ERR_INVALID, FACADE, HEADER, ROOT, header_text
+from resource_report import report
+
+from test_temporal_abi import ERR_INVALID, FACADE, HEADER, ROOT, header_text
 
 ENTRY_POINTS = ["rtgl_read_temporal_moments_f32", "rtgl_device_temporal_moments"]
 
@@ -79,31 +81,17 @@ def test_facade_method_compiles_with_the_host_compiler(tmp_path):
 
 @pytest.fixture(scope="module")
 def resource_report():
-    """The compiler's resource remarks of every kernel (`make asm`, as tests/test_temporal_abi.py does: a device-only compile of the
-    library's one translation unit, the slow part of this module; it rewrites the ignored csrc/rtgl_amd.gfx950.s and nothing else)."""
-    out = subprocess.run(["make", "-B", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep, cur = {}, None
-    for line in (out.stdout + out.stderr).splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rep[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur:
-            rep[cur][m.group(1).strip()] = int(m.group(2))
-    return rep
+    return report()
 
 
 def test_temporal_moments_kernel_instances_spill_nothing(resource_report):
-    """temporal_moments_kernel<history, static shortcut, normal test, position test, demodulation>: the two instances without history and
-    all sixteen with it"""
+    """temporal_kernel<history, static shortcut, normal test, position test, moments mode> with mode 1 or 2 (demodulation = mode - 1): the
+    two instances without history and all sixteen with it"""
     found = {}
     for name, r in resource_report.items():
-        m = re.match(r"_ZN2rt23temporal_moments_kernelILb([01])ELb([01])ELb([01])ELb([01])ELb([01])EEEvNS_19TemporalMomentsArgsE$", name)
+        m = re.match(r"_ZN2rt15temporal_kernelILb([01])ELb([01])ELb([01])ELb([01])ELi([12])EEEv", name)
         if m:
-            found[tuple(int(g) for g in m.groups())] = r
+            found[tuple(int(g) for g in m.groups()[:4]) + (int(m.group(5)) - 1,)] = r
     want = [(0, 0, 0, 0, d) for d in (0, 1)] + [(1, s, n, p, d) for s in (0, 1) for n in (0, 1) for p in (0, 1) for d in (0, 1)]
     assert sorted(found) == sorted(want), sorted(resource_report)
     for key, r in found.items():
@@ -117,6 +105,6 @@ def test_prepare_variant_spills_nothing(resource_report):
     assert r is not None, sorted(resource_report)
     assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, r
     assert r["Occupancy"] >= 4, r                              # (by registers; its 37.4 KB of LDS are requested at launch, like its sibling's)
-    # the siblings are still there under their names
+    # the sibling and the option-off temporal instances are still there
     assert "_ZN2rt21guided_prepare_kernelENS_10GuidedArgsE" in resource_report
-    assert "_ZN2rt15temporal_kernelILb1ELb0ELb1ELb1EEEvNS_12TemporalArgsE" in resource_report
+    assert any(re.match(r"_ZN2rt15temporal_kernelILb1ELb0ELb1ELb1ELi0EEEv", name) for name in resource_report)
