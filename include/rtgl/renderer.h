@@ -423,6 +423,17 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
+    // ---- temporal clip (rtgl_temporal_clip, include/rtgl_amd.h; extension): the history temporal_accumulate() just wrote clamped into the
+    // colour box of the current frame's 7 x 7 geometric neighbourhood, the history length of a clamped pixel cut -- call it right after
+    // temporal_accumulate(), so that lighting that changed without the geometry changing does not ghost.  nullptr: its defaults
+    // (sigma_scale 2, clip_history 3, sigma_normal 0.3, sigma_position 0.05).  Prints and returns false on failure.
+    bool temporal_clip(const rtgl_temporal_clip_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_temporal_clip(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
     // the next temporal_accumulate() starts without history
     bool temporal_reset()
     {

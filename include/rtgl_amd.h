@@ -378,6 +378,56 @@ void *rtgl_device_temporal(rtgl_context *ctx);
  *   Limit: the firefly clamp does not rescale the v0 of a pixel it scaled down; the over-estimate only widens that pixel's tolerance. */
 int rtgl_read_temporal_moments_f32(rtgl_context *ctx, float *rgba);
 void *rtgl_device_temporal_moments(rtgl_context *ctx);
+
+/* -- temporal clip: the latest history clamped, in place, into a per-pixel colour box taken from the 7 x 7 geometric neighbourhood of the
+ * CURRENT frame, and the history length of a clamped pixel cut (variance clipping, Salvi 2016; the history clamp of ReLAX).
+ * rtgl_temporal_accumulate validates the history against geometry only; this call, made after it, is what notices radiance that changed
+ * without the first hit changing (a new background, the cube map switched, an edited material, the aperture, a moved light seen in a
+ * mirror).  No reference counterpart: the reference resets the image on each of these.  DEFINED bit for bit under the denoisers' rules
+ * (tests/temporal_clip_mirror.py restates it): binary32, one rounding per operation in the order written, no contraction, correctly
+ * rounded divide and CORRECTLY ROUNDED SQUARE ROOT -- the first contract of this library that takes one (IEEE 754 sqrt, what numpy's
+ * float32 sqrt gives).   ew, dot3, in = 1 / (sigma_normal sigma_normal), ip: as in rtgl_denoise.
+ *   Inputs, as they are on the context's stream when the call is enqueued: the image I (meant to be this frame's own radiance: the intended
+ *   use of rtgl_temporal_accumulate), the planes N and P, the latest history buffer Hc = {rgb, n} (the one rtgl_device_temporal names) and,
+ *   if the latest rtgl_temporal_accumulate stored moments, the latest moments buffer.
+ *   Geometric weight of a tap q of p:  g(q) = 1;  g = g ew(dot3(N(q).xyz - N(p).xyz) in);  g = g ew(dot3(P(q).xyz - P(p).xyz) ip),
+ *     sp = sigma_position P(p).w, ip = (sp > 0) ? 1 / (sp sp) : 0  (a term whose sigma is <= 0 is skipped and its plane is not read; the
+ *     position plane is always read for the kind test).
+ *   Window, per pixel p: taps j = -3..3 (outer), i = -3..3, q = p + (i, j).  A tap counts only if it is inside the image, is of p's kind,
+ *     (P(q).w > 0) == (P(p).w > 0), has g(q) > 0, and c = I(q).rgb is finite in all three channels (c.r - c.r == 0, likewise g and b).
+ *     For a tap that counts:  s0 = s0 + g;  per channel  s1 = s1 + g c,  s2 = s2 + g (c c).
+ *   Box, if s0 > 0, per channel:  mu = s1 / s0;  v = s2 / s0 - mu mu;  v = (v > 0) ? v : 0;  e = sigma_scale sqrt(v);  lo = mu - e,  hi = mu + e;
+ *     then widened so that it always holds the pixel's own sample:  lo = (I(p).c < lo) ? I(p).c : lo;  hi = (I(p).c > hi) ? I(p).c : hi
+ *     (without this a noise-free region, a miss on the cube map with DOF off, would be pulled towards its neighbourhood mean).
+ *     A pixel ALONE in its window -- no other tap counts: a 1 x 1 image, a hit whose neighbours all fail the geometric tests -- has v = 0 and
+ *     the box [I(p), I(p)]: its history is REPLACED by the frame's sample and, if it differed, its length cut.
+ *   Clamp, per channel, x = Hc(p).c:  y = (x < lo) ? lo : x;  y = (y > hi) ? hi : y;  the channel is CLIPPED if either compare was true
+ *     (a NaN x, lo or hi compares false: it clips nothing and changes nothing).
+ *   History length:  n' = (any channel clipped and n > clip_history) ? clip_history : n.     With s0 == 0 nothing changes.
+ *   Stores: {y, n'} to Hc(p), in place (a pixel reads and writes only its own record of Hc; the window reads I, N and P only); if moments
+ *   are stored, n' to the .w of the pixel's moments record, whose m1, m2 and v stay.  Nothing else is written, no buffer is allocated.
+ * Defaults (rtgl_temporal_clip_defaults, and a NULL params): sigma_scale 2, clip_history 3, sigma_normal 0.3, sigma_position 0.05.
+ * clip_history 3 puts a clipped pixel under the threshold of 4 of option "denoise_variance": rtgl_denoise_guided then takes its spatial
+ * estimate there until the history has grown back.
+ * Like its neighbours the call first submits the frames a batching context holds, enqueues one kernel on the context's stream and returns
+ * without waiting.  A second call without a new rtgl_temporal_accumulate is allowed and is the identity, bit for bit.  With
+ * "denoise_source" = 1 the denoisers filter the clipped history; the next rtgl_temporal_accumulate reprojects it.
+ * RTGL_ERR_INVALID: NULL context, a non-finite parameter, sigma_scale <= 0, clip_history < 1, non-zero flags or reserved words.
+ * RTGL_ERR_STATE: no rtgl_temporal_accumulate has succeeded; RTGL_AOV_POSITION is not enabled; RTGL_AOV_NORMAL is not enabled while
+ * sigma_normal > 0; no frame has been rendered since the planes last restarted; the context is tiled or multi-device.
+ * Limits: the box is of raw radiance, not demodulated: texture detail inside a window widens it.  m1, m2 and v of the moments are not
+ * clamped: after a change of lighting v over-estimates until the history has regrown.  The box needs I to be ONE frame's radiance: over an
+ * accumulating image it narrows as the image converges and ends up clamping the history to the image. */
+typedef struct rtgl_temporal_clip_params {
+    float    sigma_scale;     /* > 0: half width of the box in standard deviations of the neighbourhood */
+    float    clip_history;    /* >= 1: the history length a clipped pixel is cut to */
+    float    sigma_normal;    /* <= 0: the normal term of the geometric weight is off (the normal plane is then not needed) */
+    float    sigma_position;  /* <= 0: the position term is off; relative to the hit distance, as in rtgl_denoise */
+    uint32_t flags;           /* none defined: must be 0 */
+    uint32_t reserved[3];     /* must be 0 */
+} rtgl_temporal_clip_params;  /* 32 bytes */
+int rtgl_temporal_clip_defaults(rtgl_temporal_clip_params *out);
+int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_params *params);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

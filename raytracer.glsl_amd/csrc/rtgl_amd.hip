@@ -21,6 +21,7 @@
 #include "rt_scan.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
+#include "rt_temporal_clip.hpp"
 
 #pragma clang fp contract(off)
 
@@ -2165,6 +2166,62 @@ extern "C" void *rtgl_device_temporal_moments(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->tm_moments) { ctx->error = "rtgl_device_temporal_moments: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")"; return nullptr; }
     return (void *)ctx->d_tm_moments[ctx->tm_cur];
+}
+
+// ---- rtgl_temporal_clip: the latest history clamped into the current frame's neighbourhood colour box (rt_temporal_clip.hpp) --------
+extern "C" int rtgl_temporal_clip_defaults(rtgl_temporal_clip_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->sigma_scale = 2.0f; out->clip_history = 3.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f;
+    return RTGL_OK;
+}
+
+template <bool kNormal, bool kPosition>
+static void launch_temporal_clip(rtgl_context *ctx, const TemporalClipArgs &a, bool moments)
+{
+    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
+    if (moments) hipLaunchKernelGGL((temporal_clip_kernel<kNormal, kPosition, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((temporal_clip_kernel<kNormal, kPosition, false>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+extern "C" int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_params *params)
+{
+    ENTER(ctx);
+    rtgl_temporal_clip_params P;
+    rtgl_temporal_clip_defaults(&P);
+    if (params) P = *params;
+    if (!std::isfinite(P.sigma_scale) || !std::isfinite(P.clip_history) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position))
+        return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: sigma_scale, clip_history and the sigmas must be finite (a sigma <= 0 switches its term off)");
+    if (!(P.sigma_scale > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: sigma_scale must be > 0");
+    if (!(P.clip_history >= 1.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: clip_history must be >= 1");
+    if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: no flag bits are defined");
+    if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a tiled or multi-device context holds strips that lack their neighbours' rows, and has no history (rtgl_temporal_accumulate is out of scope there): "
+                                         "render on a single-device context");
+    if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no rtgl_temporal_accumulate call has succeeded on this context");
+    const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
+    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0);
+    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a first-hit plane this call needs is not enabled (option \"aov\": position always, for the kind test; normal for sigma_normal > 0)");
+    if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no frame has been rendered since the first-hit planes last restarted");
+    const size_t n = (size_t)ctx->local_rows * ctx->width;
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: this context holds no pixels");
+    TemporalClipArgs a{};
+    a.image = ctx->d_image; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = ctx->d_aov[2];
+    a.hist = ctx->d_tm_hist[ctx->tm_cur];
+    a.moments = ctx->tm_moments ? ctx->d_tm_moments[ctx->tm_cur] : nullptr;
+    a.width = ctx->width; a.height = ctx->local_rows;
+    a.sigma_scale = P.sigma_scale; a.clip_history = P.clip_history;
+    a.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
+    a.sigma_position = P.sigma_position;
+    const bool moments = ctx->tm_moments != 0;
+    if (use_n && use_p) launch_temporal_clip<true, true>(ctx, a, moments);
+    else if (use_n) launch_temporal_clip<true, false>(ctx, a, moments);
+    else if (use_p) launch_temporal_clip<false, true>(ctx, a, moments);
+    else launch_temporal_clip<false, false>(ctx, a, moments);
+    HIPCHK(ctx, hipGetLastError());
+    return RTGL_OK;
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

@@ -28,6 +28,8 @@ DENOISE_DEFAULTS = dict(passes=5, sigma_color=16.0, sigma_normal=0.3, sigma_posi
 DENOISE_GUIDED_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, firefly_ratio=1.0, demodulate=True)
 # rtgl_temporal_accumulate
 TEMPORAL_DEFAULTS = dict(max_history=32.0, sigma_normal=0.3, sigma_position=0.05)
+# rtgl_temporal_clip
+TEMPORAL_CLIP_DEFAULTS = dict(sigma_scale=2.0, clip_history=3.0, sigma_normal=0.3, sigma_position=0.05)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -44,6 +46,7 @@ ABI_SYMBOLS = [
     "rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance",
     "rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal",
     "rtgl_read_temporal_moments_f32", "rtgl_device_temporal_moments",
+    "rtgl_temporal_clip_defaults", "rtgl_temporal_clip",
 ]
 
 
@@ -87,6 +90,12 @@ class CTemporalParams(C.Structure):
     """rtgl_temporal_params"""
     _fields_ = [("max_history", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32 * 4)]
+
+
+class CTemporalClipParams(C.Structure):
+    """rtgl_temporal_clip_params"""
+    _fields_ = [("sigma_scale", C.c_float), ("clip_history", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 def build_library(force: bool = False) -> str:
@@ -152,6 +161,8 @@ def load_library() -> C.CDLL:
     L.rtgl_device_temporal.argtypes = [vp]; L.rtgl_device_temporal.restype = vp
     L.rtgl_read_temporal_moments_f32.argtypes = [vp, vp]
     L.rtgl_device_temporal_moments.argtypes = [vp]; L.rtgl_device_temporal_moments.restype = vp
+    L.rtgl_temporal_clip_defaults.argtypes = [C.POINTER(CTemporalClipParams)]
+    L.rtgl_temporal_clip.argtypes = [vp, C.POINTER(CTemporalClipParams)]
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -430,6 +441,17 @@ class Context:
         that call stored moments: see the context's last error)."""
         return int(self.lib.rtgl_device_temporal_moments(self.h) or 0)
 
+    def temporal_clip(self, sigma_scale=None, clip_history=None, sigma_normal=None, sigma_position=None):
+        """Enqueue the clamp of the latest history into the current frame's neighbourhood colour box (rtgl_temporal_clip; does not wait;
+        call it after temporal_accumulate()): where a pixel is clamped its history length is cut to clip_history.  An argument left at None
+        keeps the library's default (TEMPORAL_CLIP_DEFAULTS); a sigma <= 0 switches its term of the geometric weight off."""
+        p = CTemporalClipParams()
+        self._chk(self.lib.rtgl_temporal_clip_defaults(C.byref(p)))
+        for name, value in (("sigma_scale", sigma_scale), ("clip_history", clip_history), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position)):
+            if value is not None:
+                setattr(p, name, float(value))
+        self._chk(self.lib.rtgl_temporal_clip(self.h, C.byref(p)))
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -490,6 +512,9 @@ class HeadlessRenderer(FrameLoop):
 
     def temporal_reset(self):
         self.ctx.temporal_reset()
+
+    def temporal_clip(self, **params):
+        self.ctx.temporal_clip(**params)
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
