@@ -141,6 +141,9 @@ int rtgl_upload_materials(rtgl_context *ctx, const void *materials, uint32_t cou
 int rtgl_upload_meshes(rtgl_context *ctx, const void *meshes, uint32_t count);       /* 16 B each; set_meshes :181-185 */
 int rtgl_upload_vertices(rtgl_context *ctx, const void *vec4s, uint32_t vec4_count); /* 16 B each, 3 per triangle; set_vertices :174-179 */
 int rtgl_upload_nodes(rtgl_context *ctx, const void *nodes, uint32_t count);         /* 48 B each; set_nodes :187-191 */
+/* A node's spheres are the indices offset <= i < offset + count with the sum taken in 32-bit unsigned arithmetic, as the shader takes it
+ * (:305): a sum that wraps below offset names no sphere, an index past the sphere buffer names the all-zero sphere.  A buffer whose walk
+ * makes more than 2^20 sphere tests per ray is refused by the next rtgl_render_frame (RTGL_ERR_INVALID). */
 /* faces: 6 (or fewer) tightly packed 8-bit images in +X,-X,+Y,-Y,+Z,-Z order, channels 3 or 4;
  * replaces CubemapTexture's constructor (src/gfx/gl.cpp:241-260) + set_envmap (renderer.cpp:163-172).
  * nfaces < 6 reproduces the incomplete cube of a failed face load (lookups return black). */

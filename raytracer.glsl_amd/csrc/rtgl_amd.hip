@@ -22,6 +22,7 @@
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
 #include "rt_temporal_clip.hpp"
+#include "rt_node_walk.hpp"
 
 #pragma clang fp contract(off)
 
@@ -680,37 +681,15 @@ extern "C" int rtgl_upload_envmap(rtgl_context *ctx, const uint8_t *faces, int n
     return RTGL_OK;
 }
 
-// traverse() (:272-329) walks the node buffer identically for every ray; run that walk once here and
-// keep the sphere indices in test order.  Stack of 5 with silently dropped pushes (:113-121), nodes
-// outside the buffer are childless and empty, walk capped at 65535 pops.
+// traverse() (:272-329) walks the node buffer identically for every ray; run that walk once here (rt_node_walk.hpp holds the rules) and
+// keep the sphere indices in test order.
+static_assert(rt_node_walk::kNoSphereVisit == kNoSphere, "the walk and the sphere scan name the zero sphere alike");
 static int rebuild_sphere_visits(rtgl_context *ctx)
 {
     std::vector<uint32_t> visits;
     const size_t kMaxVisits = 1u << 20;
-    if (ctx->n_nodes > 0) {
-        uint32_t items[5] = { 0, 0, 0, 0, 0 };
-        int top = 0, pops = 0;
-        auto rd = [&](uint32_t node, int off) { uint32_t v; memcpy(&v, ctx->h_nodes.data() + (size_t)node * 48 + off, 4); return v; };
-        while (top != -1 && pops < 65535) {
-            uint32_t id = items[top--];
-            pops++;
-            uint32_t left = 0xFFFFFFFFu, right = 0xFFFFFFFFu, offset = 0, count = 0;
-            if (id < ctx->n_nodes) { left = rd(id, 32); right = rd(id, 36); offset = rd(id, 40); count = rd(id, 44); }
-            if (left != 0xFFFFFFFFu && top != 4) items[++top] = left;
-            if (right != 0xFFFFFFFFu && top != 4) items[++top] = right;
-            uint64_t end = (uint64_t)offset + count;
-            bool zero_emitted = false;
-            for (uint64_t i = offset; i < end; ++i) {
-                if (i < ctx->n_spheres) visits.push_back((uint32_t)i);
-                else {   // every out-of-range index reads the same all-zero sphere: one visit stands for the run
-                    if (!zero_emitted) visits.push_back(kNoSphere);
-                    zero_emitted = true;
-                    break;
-                }
-                if (visits.size() > kMaxVisits) return fail(ctx, RTGL_ERR_INVALID, "node buffer expands to more than 2^20 sphere tests per ray");
-            }
-        }
-    }
+    if (!rt_node_walk::walk(ctx->h_nodes.data(), ctx->n_nodes, ctx->n_spheres, kMaxVisits, visits))
+        return fail(ctx, RTGL_ERR_INVALID, "node buffer expands to more than 2^20 sphere tests per ray");
     int rc = realloc_upload(ctx, ctx->d_sphere_visits, visits.data(), visits.size() * sizeof(uint32_t));
     if (rc) return rc;
     ctx->n_sphere_visits = (uint32_t)visits.size();
