@@ -442,6 +442,32 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
+    // ---- display transform (rtgl_tonemap, include/rtgl_amd.h; extension): the image, the denoised buffer or the temporal history exposed,
+    // tone-mapped and sRGB-encoded into an RGBA8 display buffer on the device.  nullptr: its defaults (source 0, op 1, auto exposure on,
+    // exposure 1, key 0.18, white 4, adapt 1, exposure_min 2^-16, exposure_max 2^16, low_permille 100, high_permille 20).  save_to_file()
+    // stays the reference's clamp; this is the picture to look at.  Prints and returns false on failure.
+    bool tonemap(const rtgl_tonemap_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_tonemap(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the display buffer of the last tonemap(), RGBA8, row 0 = bottom unless flip; empty (and a message) before the first successful tonemap()
+    std::vector<uint8_t> read_display(bool flip = false) const
+    {
+        if (!m_ctx) return {};
+        std::vector<uint8_t> px((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_display_u8(m_ctx, px.data(), flip ? 1 : 0) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return px;
+    }
+    // the display buffer as a PNG, top row first like save_to_file()
+    bool save_display_png(const std::string &path) const
+    {
+        const std::vector<uint8_t> px = read_display(true);
+        if (px.empty()) return false;
+        return rtgl::write_png(path, px.data(), m_width, rtgl_local_rows(m_ctx), 4);
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

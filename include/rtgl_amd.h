@@ -431,6 +431,77 @@ typedef struct rtgl_temporal_clip_params {
 } rtgl_temporal_clip_params;  /* 32 bytes */
 int rtgl_temporal_clip_defaults(rtgl_temporal_clip_params *out);
 int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_params *params);
+
+/* -- display transform: one of the float buffers turned into an RGBA8 display buffer ON THE DEVICE: auto exposure from a luminance
+ * histogram, a tone curve, and the sRGB transfer function.  rtgl_read_image_u8 stays the reference's glGetTexImage (clamp, x 255, no
+ * exposure, no curve, no transfer function, the image only); this is the way out to a picture for scenes whose radiance leaves [0, 1] and
+ * for the denoised and the temporal buffers.  No reference counterpart.  DEFINED bit for bit (tests/tonemap_mirror.py restates it), and
+ * chosen so that NO TRANSCENDENTAL FUNCTION is needed: integers where the histogram is concerned, binary32 with one rounding per operation
+ * in the order written, no contraction and correctly rounded divide elsewhere, two committed tables (raytracer.glsl_amd/csrc/rt_tonemap.hpp;
+ * the committed values are the contract):
+ *     P[r], r = 0..63   = float32(2^(-r/64))
+ *     T[k], k = 1..255  = float32(D((k - 0.5) / 255)) with D the sRGB decoding of IEC 61966-2-1 evaluated in float64,
+ *                         D(v) = v / 12.92 for v <= 0.04045, ((v + 0.055) / 1.055)^2.4 above; strictly increasing.
+ *   lum(r, g, b) = (0.25 r + 0.5 g) + 0.25 b, as in rtgl_denoise_guided.     S = the source buffer, c = S(p).rgb; S(p).a is not read.
+ *   1. Histogram (flag RTGL_TONEMAP_AUTO_EXPOSURE only).  L = lum(c).  A pixel COUNTS iff L > 0: NaN, +0, -0 and negatives go to `ignored`.
+ *      Its bin is  b = clamp((bits(L) >> 20) - 888, 0, 255)  in signed integers, bits(L) the 32 bits of L: eight bins per binade, bin 0
+ *      beginning at 2^-16 (and holding everything below), bin 255 ending at 2^16 (and holding everything above, +inf included).  h[b] is
+ *      the number of counting pixels of bin b: integer sums, independent of any order.
+ *   2. Solve (same flag), in 64-bit integers:  N = sum h;  lo = N low_permille / 1000,  hi = N high_permille / 1000  (floor);  walking b
+ *      upwards with c the pixels below bin b:  kept[b] = max(0, min(c + h[b], N - hi) - max(c, lo))  -- the darkest lo and the brightest hi
+ *      pixels are left out;  K = sum kept[b],  S = sum kept[b] (2 b + 1),  m = 4 S / K (floor),  q = m / 64,  r = m % 64  (m / 64 - 16 is the
+ *      mean binary logarithm of the kept luminances, bins taken at their centres).
+ *        target = ldexp(key P[r], 16 - q)   (one binary32 multiply, then the exact scaling, rounded once if the result is subnormal);
+ *        N == 0:  target = exposure.
+ *        e = target;  if adapt < 1 and an exposure `prev` has been stored since the context was created or rtgl_tonemap_reset was called:
+ *        e = prev + (target - prev) adapt.     e = (e < exposure_min) ? exposure_min : e;  e = (e > exposure_max) ? exposure_max : e;
+ *        e is stored as `prev`.  It never leaves the device inside rtgl_tonemap.
+ *      Without the flag steps 1 and 2 are not run: e = exposure as given (not clamped); `prev` and the histogram stay as they were.
+ *   3. Map, per channel  x = c e,  then
+ *        op RTGL_TONEMAP_LINEAR:    y = x
+ *        op RTGL_TONEMAP_REINHARD:  Lx = lum(x);  s = (1 + Lx / (white white)) / (1 + Lx);  y = x s      (luminance mapped, hue kept;
+ *                                   a luminance of `white` after exposure maps to 1)
+ *        op RTGL_TONEMAP_ACES:      y = (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14)                 (Narkowicz's fit, per channel)
+ *   4. Encode, per channel:  code = the number of k in 1..255 with T[k] <= y.  This is the correctly rounded sRGB code by comparisons
+ *      alone: NaN and negatives give 0, +inf gives 255.  Alpha = 255.  The display buffer is local_rows x width RGBA8 records (bytes r, g,
+ *      b, a), rows bottom-up like the image; rtgl_read_display_u8 (synchronises) turns them over if flip != 0, as rtgl_read_image_u8 does.
+ * Defaults (rtgl_tonemap_defaults, and a NULL params): source 0, op 1, auto exposure on, exposure 1, key 0.18, white 4, adapt 1,
+ * exposure_min 2^-16, exposure_max 2^16, low_permille 100, high_permille 20.
+ * Like its neighbours the call first submits the frames a batching context holds, enqueues its kernels on the context's stream (three with
+ * auto exposure, one without) and returns without waiting; nothing but the display buffer and the call's own state is written.
+ * rtgl_read_tonemap_exposure (synchronises): the e of the latest call.  rtgl_read_tonemap_histogram (synchronises): h and, if `ignored`
+ * is not NULL, the ignored pixels, of the latest call WITH auto exposure.  rtgl_device_display: the display buffer (torch interop; valid
+ * until the context is destroyed).
+ * RTGL_ERR_INVALID: NULL context or output pointer; unknown source, op or flag bits; exposure, key, white, adapt, exposure_min or
+ * exposure_max not finite or not > 0; adapt > 1; exposure_min > exposure_max; low_permille + high_permille >= 1000; non-zero reserved.
+ * RTGL_ERR_STATE: the source buffer does not exist yet (source 1 before a denoiser call, source 2 before rtgl_temporal_accumulate); the
+ * context is tiled or multi-device (the exposure is a property of the whole picture); the read-outs before the first successful call
+ * (rtgl_device_display: NULL), rtgl_read_tonemap_histogram before the first one with auto exposure.
+ * Limits: no dithering; the histogram weighs every pixel alike, the sky with the subject. */
+enum { RTGL_TONEMAP_SOURCE_IMAGE = 0, RTGL_TONEMAP_SOURCE_DENOISED = 1, RTGL_TONEMAP_SOURCE_TEMPORAL = 2 };
+enum { RTGL_TONEMAP_LINEAR = 0, RTGL_TONEMAP_REINHARD = 1, RTGL_TONEMAP_ACES = 2 };
+enum { RTGL_TONEMAP_AUTO_EXPOSURE = 1 };
+typedef struct rtgl_tonemap_params {
+    uint32_t source;          /* RTGL_TONEMAP_SOURCE_*: the buffer to display */
+    uint32_t op;              /* RTGL_TONEMAP_LINEAR / _REINHARD / _ACES */
+    uint32_t flags;           /* bit 0: RTGL_TONEMAP_AUTO_EXPOSURE */
+    float    exposure;        /* > 0: used when auto exposure is off, and when no pixel counts */
+    float    key;             /* > 0: the value the mean kept luminance is exposed to */
+    float    white;           /* > 0: op 1, the luminance after exposure that maps to 1 */
+    float    adapt;           /* (0, 1]: the share of the way from the previous exposure to the target taken per call; 1: no memory */
+    float    exposure_min;    /* > 0 */
+    float    exposure_max;    /* >= exposure_min */
+    uint32_t low_permille;    /* the darkest share of the counting pixels left out of the mean, in 1/1000 */
+    uint32_t high_permille;   /* the brightest share left out; low_permille + high_permille < 1000 */
+    uint32_t reserved[5];     /* must be 0 */
+} rtgl_tonemap_params;        /* 64 bytes */
+int rtgl_tonemap_defaults(rtgl_tonemap_params *out);
+int rtgl_tonemap(rtgl_context *ctx, const rtgl_tonemap_params *params);
+int rtgl_tonemap_reset(rtgl_context *ctx);
+int rtgl_read_display_u8(rtgl_context *ctx, uint8_t *rgba, int flip);
+void *rtgl_device_display(rtgl_context *ctx);
+int rtgl_read_tonemap_exposure(rtgl_context *ctx, float *exposure);
+int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256], uint32_t *ignored);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -22,6 +22,7 @@
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
 #include "rt_temporal_clip.hpp"
+#include "rt_tonemap.hpp"
 #include "rt_node_walk.hpp"
 
 #pragma clang fp contract(off)
@@ -278,6 +279,12 @@ struct rtgl_context {
     // option "temporal_moments": two buffers of records {m1, m2, v, n} that take turns with the history's (set tm_cur), allocated by the
     // first call that needs them; tm_moments: the mode (1, 2) whose records the latest successful call stored in set tm_cur, 0: none
     float4 *d_tm_moments[2] = {nullptr, nullptr}; int tm_moments = 0;
+    // rtgl_tonemap: the RGBA8 display buffer and the state the kernels share (two histogram sets that take turns and the exposure,
+    // rt_tonemap.hpp), allocated by the first call.  has_display: a call has succeeded; tone_set: the set the next auto call counts in;
+    // tone_hist_set: the set the latest auto call counted in (-1: none yet); tone_prev: the state holds an exposure stored since the last
+    // rtgl_tonemap_reset; tone_auto: the latest call solved its exposure on the device, otherwise it used tone_exposure
+    uchar4 *d_display = nullptr; uint32_t *d_tone_state = nullptr;
+    bool has_display = false, tone_prev = false, tone_auto = false; int tone_set = 0, tone_hist_set = -1; float tone_exposure = 1.0f;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -474,7 +481,7 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
                      ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
                      ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near,
                      ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1],
-                     ctx->d_tm_moments[0], ctx->d_tm_moments[1] };
+                     ctx->d_tm_moments[0], ctx->d_tm_moments[1], ctx->d_display, ctx->d_tone_state };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -2203,6 +2210,132 @@ extern "C" int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_pa
     return RTGL_OK;
 }
 
+// ---- rtgl_tonemap: the display transform, float buffer -> RGBA8 (rt_tonemap.hpp) ----------------------------------------------------
+extern "C" int rtgl_tonemap_defaults(rtgl_tonemap_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->source = RTGL_TONEMAP_SOURCE_IMAGE; out->op = RTGL_TONEMAP_REINHARD; out->flags = RTGL_TONEMAP_AUTO_EXPOSURE;
+    out->exposure = 1.0f; out->key = 0.18f; out->white = 4.0f; out->adapt = 1.0f;
+    out->exposure_min = 0x1p-16f; out->exposure_max = 0x1p16f;
+    out->low_permille = 100u; out->high_permille = 20u;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_tonemap(rtgl_context *ctx, const rtgl_tonemap_params *params)
+{
+    ENTER(ctx);
+    rtgl_tonemap_params P;
+    rtgl_tonemap_defaults(&P);
+    if (params) P = *params;
+    if (P.source > RTGL_TONEMAP_SOURCE_TEMPORAL) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: source must be 0 (image), 1 (denoised) or 2 (temporal history)");
+    if (P.op > RTGL_TONEMAP_ACES) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: op must be 0 (linear), 1 (Reinhard with white point) or 2 (ACES fit)");
+    if (P.flags & ~(uint32_t)RTGL_TONEMAP_AUTO_EXPOSURE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: only flag bit 0 (auto exposure) is defined");
+    for (float v : { P.exposure, P.key, P.white, P.adapt, P.exposure_min, P.exposure_max })
+        if (!std::isfinite(v) || !(v > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: exposure, key, white, adapt, exposure_min and exposure_max must be finite and > 0");
+    if (P.adapt > 1.0f) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: adapt must be in (0, 1]");
+    if (P.exposure_min > P.exposure_max) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: exposure_min must not exceed exposure_max");
+    if ((uint64_t)P.low_permille + (uint64_t)P.high_permille >= 1000u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: low_permille + high_permille must be < 1000");
+    for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: a tiled or multi-device context holds strips, and the exposure is a property of the whole picture: render on a single-device context");
+    const float4 *src = ctx->d_image;
+    if (P.source == RTGL_TONEMAP_SOURCE_DENOISED) {
+        if (!ctx->has_denoised) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: source 1, and no rtgl_denoise or rtgl_denoise_guided call has succeeded on this context");
+        src = ctx->d_denoised;
+    } else if (P.source == RTGL_TONEMAP_SOURCE_TEMPORAL) {
+        if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: source 2, and no rtgl_temporal_accumulate call has succeeded on this context");
+        src = ctx->d_tm_hist[ctx->tm_cur];
+    }
+    const size_t n = (size_t)ctx->local_rows * ctx->width;
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: this context holds no pixels");
+    if (!ctx->d_display) HIPCHK(ctx, hipMalloc((void **)&ctx->d_display, n * 4));
+    if (!ctx->d_tone_state) {
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tone_state, kToneStateWords * 4));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_tone_state, 0, kToneStateWords * 4, ctx->stream));      // both sets start clean; from here on the solve keeps them so
+    }
+    const bool automatic = (P.flags & RTGL_TONEMAP_AUTO_EXPOSURE) != 0;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)ctx->n_cus * 8);
+    if (automatic) {
+        const int set = ctx->tone_set;
+        hipLaunchKernelGGL(tonemap_histogram_kernel, dim3(blocks), dim3(256), 0, ctx->stream, src, n, ctx->d_tone_state + set * kToneWords);
+        HIPCHK(ctx, hipGetLastError());
+        TonemapSolveArgs s{};
+        s.state = ctx->d_tone_state; s.set = set; s.use_prev = ctx->tone_prev ? 1u : 0u;
+        s.low_permille = P.low_permille; s.high_permille = P.high_permille;
+        s.exposure = P.exposure; s.key = P.key; s.adapt = P.adapt; s.exposure_min = P.exposure_min; s.exposure_max = P.exposure_max;
+        hipLaunchKernelGGL(tonemap_solve_kernel, dim3(1), dim3(64), 0, ctx->stream, s);
+        HIPCHK(ctx, hipGetLastError());
+        ctx->tone_set = set ^ 1; ctx->tone_hist_set = set; ctx->tone_prev = true;
+    }
+    TonemapMapArgs a{};
+    a.src = src; a.display = reinterpret_cast<uint32_t *>(ctx->d_display); a.n = n;
+    a.exposure_word = automatic ? ctx->d_tone_state + kToneExposureWord : nullptr;
+    a.exposure = P.exposure; a.white2 = P.white * P.white;
+    if (P.op == RTGL_TONEMAP_LINEAR) hipLaunchKernelGGL(tonemap_map_kernel<0>, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    else if (P.op == RTGL_TONEMAP_REINHARD) hipLaunchKernelGGL(tonemap_map_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(tonemap_map_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_display = true; ctx->tone_auto = automatic; ctx->tone_exposure = P.exposure;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_tonemap_reset(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    ctx->tone_prev = false;                               // (the display buffer, the histogram and the exposure stay readable)
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_display_u8(rtgl_context *ctx, uint8_t *rgba, int flip)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->has_display) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_display_u8: no rtgl_tonemap call has succeeded on this context");
+    const size_t row = (size_t)ctx->width * 4, rows = (size_t)ctx->local_rows;
+    if (!flip) {
+        HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_display, rows * row, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return RTGL_OK;
+    }
+    std::vector<uint8_t> tmp(rows * row);                 // the rows are turned over on the host: the device buffer keeps the image's order
+    HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->d_display, rows * row, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t y = 0; y < rows; ++y) memcpy(rgba + (rows - 1 - y) * row, tmp.data() + y * row, row);
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_display(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_display) { ctx->error = "rtgl_device_display: no rtgl_tonemap call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_display;
+}
+
+extern "C" int rtgl_read_tonemap_exposure(rtgl_context *ctx, float *exposure)
+{
+    ENTER(ctx);
+    if (!exposure) return fail(ctx, RTGL_ERR_INVALID, "exposure is NULL");
+    if (!ctx->has_display) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_tonemap_exposure: no rtgl_tonemap call has succeeded on this context");
+    if (!ctx->tone_auto) { *exposure = ctx->tone_exposure; return RTGL_OK; }
+    HIPCHK(ctx, hipMemcpyAsync(exposure, ctx->d_tone_state + kToneExposureWord, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256], uint32_t *ignored)
+{
+    ENTER(ctx);
+    if (!hist) return fail(ctx, RTGL_ERR_INVALID, "hist is NULL");
+    if (ctx->tone_hist_set < 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_tonemap_histogram: no rtgl_tonemap call with auto exposure has succeeded on this context");
+    uint32_t words[kToneWords];
+    HIPCHK(ctx, hipMemcpyAsync(words, ctx->d_tone_state + ctx->tone_hist_set * kToneWords, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(hist, words, kToneBins * 4);
+    if (ignored) *ignored = words[kToneBins];
+    return RTGL_OK;
+}
+
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
     ENTER(ctx);
@@ -2317,6 +2450,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
         for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1], ctx->d_tm_moments[0], ctx->d_tm_moments[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+        if (ctx->d_display) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

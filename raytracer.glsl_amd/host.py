@@ -30,6 +30,10 @@ DENOISE_GUIDED_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_
 TEMPORAL_DEFAULTS = dict(max_history=32.0, sigma_normal=0.3, sigma_position=0.05)
 # rtgl_temporal_clip
 TEMPORAL_CLIP_DEFAULTS = dict(sigma_scale=2.0, clip_history=3.0, sigma_normal=0.3, sigma_position=0.05)
+# rtgl_tonemap (source: 0 image, 1 denoised, 2 temporal history; op: 0 linear, 1 Reinhard with white point, 2 ACES fit)
+TONEMAP_DEFAULTS = dict(source=0, op=1, auto=True, exposure=1.0, key=0.18, white=4.0, adapt=1.0, exposure_min=2.0 ** -16, exposure_max=2.0 ** 16,
+                        low_permille=100, high_permille=20)
+TONEMAP_AUTO_EXPOSURE = 1
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -47,6 +51,8 @@ ABI_SYMBOLS = [
     "rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal",
     "rtgl_read_temporal_moments_f32", "rtgl_device_temporal_moments",
     "rtgl_temporal_clip_defaults", "rtgl_temporal_clip",
+    "rtgl_tonemap_defaults", "rtgl_tonemap", "rtgl_tonemap_reset", "rtgl_read_display_u8", "rtgl_device_display",
+    "rtgl_read_tonemap_exposure", "rtgl_read_tonemap_histogram",
 ]
 
 
@@ -96,6 +102,13 @@ class CTemporalClipParams(C.Structure):
     """rtgl_temporal_clip_params"""
     _fields_ = [("sigma_scale", C.c_float), ("clip_history", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class CTonemapParams(C.Structure):
+    """rtgl_tonemap_params"""
+    _fields_ = [("source", C.c_uint32), ("op", C.c_uint32), ("flags", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float),
+                ("white", C.c_float), ("adapt", C.c_float), ("exposure_min", C.c_float), ("exposure_max", C.c_float),
+                ("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
 def build_library(force: bool = False) -> str:
@@ -163,6 +176,13 @@ def load_library() -> C.CDLL:
     L.rtgl_device_temporal_moments.argtypes = [vp]; L.rtgl_device_temporal_moments.restype = vp
     L.rtgl_temporal_clip_defaults.argtypes = [C.POINTER(CTemporalClipParams)]
     L.rtgl_temporal_clip.argtypes = [vp, C.POINTER(CTemporalClipParams)]
+    L.rtgl_tonemap_defaults.argtypes = [C.POINTER(CTonemapParams)]
+    L.rtgl_tonemap.argtypes = [vp, C.POINTER(CTonemapParams)]
+    L.rtgl_tonemap_reset.argtypes = [vp]
+    L.rtgl_read_display_u8.argtypes = [vp, vp, i]
+    L.rtgl_device_display.argtypes = [vp]; L.rtgl_device_display.restype = vp
+    L.rtgl_read_tonemap_exposure.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rtgl_read_tonemap_histogram.argtypes = [vp, vp, C.POINTER(u32)]
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -452,6 +472,52 @@ class Context:
                 setattr(p, name, float(value))
         self._chk(self.lib.rtgl_temporal_clip(self.h, C.byref(p)))
 
+    # --- display transform
+    def tonemap(self, source=None, op=None, auto=None, exposure=None, key=None, white=None, adapt=None, exposure_min=None, exposure_max=None,
+                low_permille=None, high_permille=None):
+        """Enqueue the display transform (rtgl_tonemap; does not wait): the image (source 0), the denoised buffer (1) or the temporal
+        history (2) exposed, tone-mapped (op 0 linear, 1 Reinhard with white point, 2 ACES fit) and sRGB-encoded into the RGBA8 display
+        buffer.  auto: the exposure is solved on the device from a luminance histogram; otherwise `exposure` is used as given.  An
+        argument left at None keeps the library's default (TONEMAP_DEFAULTS)."""
+        p = CTonemapParams()
+        self._chk(self.lib.rtgl_tonemap_defaults(C.byref(p)))
+        for name, value in (("source", source), ("op", op), ("low_permille", low_permille), ("high_permille", high_permille)):
+            if value is not None:
+                setattr(p, name, int(value))
+        for name, value in (("exposure", exposure), ("key", key), ("white", white), ("adapt", adapt), ("exposure_min", exposure_min), ("exposure_max", exposure_max)):
+            if value is not None:
+                setattr(p, name, float(value))
+        if auto is not None:
+            p.flags = (p.flags & ~TONEMAP_AUTO_EXPOSURE) | (TONEMAP_AUTO_EXPOSURE if auto else 0)
+        self._chk(self.lib.rtgl_tonemap(self.h, C.byref(p)))
+
+    def tonemap_reset(self):
+        """The next tonemap() takes its target exposure at once, whatever `adapt`."""
+        self._chk(self.lib.rtgl_tonemap_reset(self.h))
+
+    def read_display(self, flip: bool = False) -> np.ndarray:
+        """The display buffer the last tonemap() wrote as (local_rows, width, 4) uint8, row 0 = bottom unless flip."""
+        out = np.zeros((self.local_rows, self.width, 4), np.uint8)
+        self._chk(self.lib.rtgl_read_display_u8(self.h, _ptr(out), int(flip)))
+        return out
+
+    def device_display_ptr(self) -> int:
+        """Device pointer of the RGBA8 display buffer (0 before the first successful tonemap(): see the context's last error)."""
+        return int(self.lib.rtgl_device_display(self.h) or 0)
+
+    def read_tonemap_exposure(self) -> np.float32:
+        """The exposure the last tonemap() applied."""
+        e = C.c_float()
+        self._chk(self.lib.rtgl_read_tonemap_exposure(self.h, C.byref(e)))
+        return np.float32(e.value)
+
+    def read_tonemap_histogram(self):
+        """(bins uint32[256], ignored) of the last tonemap() with auto exposure: eight bins per binade of luminance from 2^-16 to 2^16,
+        and the pixels whose luminance is not > 0."""
+        hist, ignored = np.zeros(256, np.uint32), C.c_uint32()
+        self._chk(self.lib.rtgl_read_tonemap_histogram(self.h, _ptr(hist), C.byref(ignored)))
+        return hist, int(ignored.value)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -515,6 +581,12 @@ class HeadlessRenderer(FrameLoop):
 
     def temporal_clip(self, **params):
         self.ctx.temporal_clip(**params)
+
+    def tonemap(self, **params):
+        self.ctx.tonemap(**params)
+
+    def read_display(self, flip: bool = False) -> np.ndarray:
+        return self.ctx.read_display(flip)
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
