@@ -175,7 +175,7 @@ struct MfRay {
     f3 o, d;
     float wd;        // >= |d|
     float wod;       // >= |o| |d|
-    uint32_t dyz, tail;  // bf16 pairs (d_hi.y, d_hi.z) and, by lane half, (1, d_lo.x) or (d_lo.y, d_lo.z)
+    uint32_t dyz, tail, tail_hi;  // bf16 pairs (d_hi.y, d_hi.z), (1, d_lo.x) for the lower lane half and (d_lo.y, d_lo.z) for the upper one
     uint32_t dx_hi;      // bf16(d.x) in the upper 16 bits
     bool valid;
 };

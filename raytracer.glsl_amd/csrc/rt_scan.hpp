@@ -527,6 +527,13 @@ __global__ void __launch_bounds__(64) scan_plan_base_kernel(WaveBuffers wb, uint
     if (lane == 0) store_through(wb.plan_base + n_chunks, run);
 }
 
+// the counting instances' candidate tallies, one LDS word per wave; the shipping instances declare none
+template <bool kCount, uint32_t kWaves>
+__device__ __forceinline__ unsigned long long *solo_cand_words()
+{
+    if constexpr (kCount) { __shared__ unsigned long long words[kWaves]; return words; }
+    else return nullptr;
+}
 // W = waves per SIMD.  W = 1: the wave owns the register file (256 + AGPRs) and hides its own latencies (the rays of its next item
 // travel while it scans).  W = 2: two waves share a SIMD, 256 registers each; a wave alone can issue one vector instruction per 4 cycles
 // while the SIMD executes one per 2, so the second wave's VALU work runs beside the first one's and the stream becomes bound by
@@ -556,6 +563,7 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     extern __shared__ uint4 lds_tiles[];                      // the chunk's A tiles, [quad][tile][panel][row]
     __shared__ uint2 lds_queue[kWaves * Cfg::kQueue];        // per-wave survivor queue, entry = (lane | tile in chunk << 8, 20-bit mask: bit 5 s + u = triangle u of the lane's half survived for ray set s)
     __shared__ uint32_t lds_pick;                             // the chunk the block scans next
+    unsigned long long *const lds_cand = solo_cand_words<kCount, kWaves>();   // kCount: per wave, the surviving pairs it handed over
     __shared__ uint32_t lds_ring[kWaves * 16u];              // per wave: the granules of its last 16 items (queue entries name their item by its turn in this ring)
 #ifdef RT_SOLO_STAMPS
 #if RT_SOLO_STAMPS == 3
@@ -588,8 +596,11 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     const uint32_t group_shift = (uint32_t)__builtin_ctz(mf.group_quads);
     constexpr uint32_t kQuadBytes = kMfQuadTiles * 1024;
     uint2 *queue = lds_queue + wave * Cfg::kQueue;
-    unsigned long long c_cand_lane = 0;                        // kCount: surviving pairs this lane handed over
-    unsigned long long c_culled = 0;                           // kCount: ray x triangle pairs the keep bits spared this wave (static launches)
+    // kCount: neither tally lives in vector registers (as per-lane values they cost the counting builds four over the whole item loop).
+    // The culled tally is wave-uniform, in scalar registers; the candidate tally is summed over the wave where the queue is handed
+    // over and kept in a word of LDS per wave (in scalar registers it meets the same pins at 50-70 more spilled scalar registers).
+    if (kCount && lane == 0) lds_cand[wave] = 0ull;            // surviving pairs this wave handed over (read and written by its lane 0 only)
+    unsigned long long c_culled = 0;                           // ray x triangle pairs the keep bits spared this wave (static launches)
     typedef const float __attribute__((address_space(4))) *ConstFloats;       // group records: uniform index => s_load
     typedef const uint32_t __attribute__((address_space(4))) *ConstWords;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -597,26 +608,35 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     const ConstFloats groups_k = (ConstFloats)(uintptr_t)mf.groups;
     const uint32_t l_lane = (uint32_t)half * 32u + (uint32_t)col;              // this lane's row inside a tile (uint4 index)
 
-    // rays of one granule as they sit in the queue: both lane halves hold the same ray
-    float4 nxt_a[S], nxt_b[S];
-    auto fetch_rays = [&](uint32_t g, float4 (&da)[S], float4 (&db)[S]) {
-        // a full granule (wave-uniform test; all but the queue's last one): the eight loads back to back, ONE round trip.  Under the
-        // per-set guard below every set is an EXEC-masked block of its own that waits for its two loads before the next one starts:
-        // four dependent round trips per segment.  (Unconditional loads from clamped slots + a select would do for the last granule,
-        // too, but cost every two-wave variant spilled registers.)
+    // Two waves per SIMD (kSplit): the set-up of an item is split over the lane halves.  The lower half fetches and prepares the
+    // granule's ray sets 0 and 2, the upper half sets 1 and 3 (entry j of a lane = set 2 j + half = slots 64 j + lane of the granule),
+    // and the halves hand each other the B operands and thresholds they built (v_permlane32_swap, below).  One wave per SIMD: both
+    // halves fetch and prepare all four sets (entry j = set j = slots 32 j + col), as every instance did before; split, the one-wave
+    // claiming and planned instances spilled four vector registers to AGPRs.
+    constexpr bool kSplit = W == 2;
+    constexpr int H = kSplit ? S / 2 : S;                      // ray sets a lane fetches and prepares
+    static_assert(S == 4, "a granule is four sets of 32 rays");
+    constexpr uint32_t kRayStride = kSplit ? 64u : 32u;
+    const uint32_t ray_lane = kSplit ? (uint32_t)lane : (uint32_t)col;      // entry j of this lane is slot ray_lane + j x kRayStride of the granule
+    float4 nxt_a[H], nxt_b[H];
+    auto fetch_rays = [&](uint32_t g, float4 (&da)[H], float4 (&db)[H]) {
+        // a full granule (wave-uniform test; all but the queue's last one): the loads back to back, ONE round trip.  Under the
+        // per-entry guard below every entry is an EXEC-masked block of its own that waits for its two loads before the next one
+        // starts: dependent round trips per segment.  (Unconditional loads from clamped slots + a select would do for the last
+        // granule, too, but cost every two-wave variant spilled registers.)
         if (g * 128u + 128u <= n_rays) {
-            const uint32_t slot0 = g * 128u + (uint32_t)col;
+            const uint32_t slot0 = g * 128u + ray_lane;
 #pragma unroll
-            for (int s = 0; s < S; ++s) da[s] = qin.a[slot0 + (uint32_t)s * 32u];
+            for (int j = 0; j < H; ++j) da[j] = qin.a[slot0 + (uint32_t)j * kRayStride];
 #pragma unroll
-            for (int s = 0; s < S; ++s) db[s] = qin.b[slot0 + (uint32_t)s * 32u];
+            for (int j = 0; j < H; ++j) db[j] = qin.b[slot0 + (uint32_t)j * kRayStride];
             return;
         }
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const uint32_t slot = g * 128u + (uint32_t)s * 32u + (uint32_t)col;
-            da[s] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); db[s] = da[s];
-            if (slot < n_rays) { da[s] = qin.a[slot]; db[s] = qin.b[slot]; }
+        for (int j = 0; j < H; ++j) {
+            const uint32_t slot = g * 128u + (uint32_t)j * kRayStride + ray_lane;
+            da[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); db[j] = da[j];
+            if (slot < n_rays) { da[j] = qin.a[slot]; db[j] = qin.b[slot]; }
         }
     };
     // the constants of a ray over the scan, from its queue record
@@ -629,7 +649,9 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         r.dyz = pack_bf16(r.d.y, r.d.z);
         r.dx_hi = dxy << 16;
         const f3 dl = mk(r.d.x - __uint_as_float(dxy << 16), r.d.y - __uint_as_float(dxy & 0xffff0000u), r.d.z - __uint_as_float(r.dyz & 0xffff0000u));
-        r.tail = half ? pack_bf16(dl.y, dl.z) : pack_bf16(1.0f, dl.x);
+        // the lower and the upper lane half's word.  kSplit: both, for the half that did not prepare this ray
+        if constexpr (kSplit) { r.tail = pack_bf16(1.0f, dl.x); r.tail_hi = pack_bf16(dl.y, dl.z); }
+        else { r.tail = half ? pack_bf16(dl.y, dl.z) : pack_bf16(1.0f, dl.x); r.tail_hi = r.tail; }
     };
 
     // Which chunk a block starts on.  Consecutive blocks go to consecutive XCDs (8, each with its own L2): with chunk = block mod chunks
@@ -783,7 +805,9 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         // handful of tiles each).
         uint32_t qn = 0, seq = 0, seq_flushed = 0;              // wave-uniform
         uint32_t *const ring = lds_ring + wave * 16;
-        auto flush = [&]() {
+        // (always_inline, here and on `append`: once the counting builds' hand-over grows, the compiler stops inlining `append` and calls
+        // it from every parking site -- 46 to 166 spilled vector registers and ~1 KiB of scratch per lane around the calls)
+        auto flush = [&]() __attribute__((always_inline)) {
             // Every (queue entry, ray set) with a non-empty 5-bit mask becomes one record (queue slot of the ray, storage position of
             // the lane's first triangle << 5 | mask), appended densely to the wave's region (ballot + prefix count per ray set), fire
             // and forget; the narrow phase expands the masks and maps storage position -> visit index.  What does not fit gets its
@@ -794,7 +818,12 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
                 const uint2 e = i < qn ? queue[i] : make_uint2(0u, 0u);
                 const uint32_t ln = e.x & 63u, pos5 = v_chunk_begin + ((e.x >> 8) & 127u) * kMfTileTris + 5u * (ln >> 5);
                 const uint32_t slot0 = ring[(e.x >> 16) & 15u] * 128u;
-                if (kCount) c_cand_lane += (unsigned long long)__popc(e.y);
+                if (kCount) {                                  // (the 20-bit masks of the 64 entries, bit by bit: ballots and scalar popcounts)
+                    uint32_t pairs = 0u;
+#pragma unroll
+                    for (int b = 0; b < 5 * S; ++b) pairs += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(((e.y >> b) & 1u) != 0u));
+                    if (lane == 0) lds_cand[wave] += (unsigned long long)pairs;
+                }
                 const uint32_t bits = (debug_skip_exact == 0 || debug_skip_exact == 3) ? e.y : 0u;
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
@@ -824,7 +853,7 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
             // the item after this one, if it is known already: its record (and with one wave per SIMD its rays) travel during the scan
             const uint32_t succ = k + step < hi ? k + step : kNone;
             if (succ != kNone) { item_of(succ, rec_g, rec_keep); rec_k = succ; }
-            if (kCount && cull && !dynamic && !planned && lane == 0)          // (dynamic launches count these in cull_items_kernel, planned ones in scan_plan_kernel)
+            if (kCount && cull && !dynamic && !planned)          // (dynamic launches count these in cull_items_kernel, planned ones in scan_plan_kernel)
                 c_culled += (unsigned long long)(n_tiles - m128_popc(keep)) * kMfTileTris * min(128u, n_rays - wave_slot0);
             if (!m128_any(keep)) {                             // (static, culled bounce) nothing of this chunk can be hit by this granule's rays
                 if constexpr (W == 1) { if (succ != kNone && m128_any(rec_keep)) { fetch_rays(rec_g, nxt_a, nxt_b); ray_k = succ; } }
@@ -835,11 +864,11 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
             if (lane == 0) ring[seq & 15u] = g;
             const uint32_t item_tag = (seq & 15u) << 16;
             ++seq;
-            MfRay ray[S];
+            MfRay ray[H];
             if constexpr (W == 1) {
                 if (ray_k != k) fetch_rays(g, nxt_a, nxt_b);
 #pragma unroll
-                for (int s = 0; s < S; ++s) prepare_ray(ray[s], nxt_a[s], nxt_b[s], wave_slot0 + (uint32_t)s * 32u + (uint32_t)col < n_rays);
+                for (int j = 0; j < H; ++j) prepare_ray(ray[j], nxt_a[j], nxt_b[j], wave_slot0 + (uint32_t)j * kRayStride + ray_lane < n_rays);
                 // the next item's rays travel while this one is scanned (one wave per SIMD: nothing else would hide the round trip)
                 if (succ != kNone && m128_any(rec_keep)) { fetch_rays(rec_g, nxt_a, nxt_b); ray_k = succ; }
             }
@@ -855,7 +884,7 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
             // triangle by triangle with a scalar branch each: ~40 cycles per branch, 350-400 per parking event, 17 % of a bounce.)  A
             // finite threshold means finite operands and edge values below 2^7 * 1e30 in magnitude, hence finite minima; a NaN
             // threshold passes all.
-            auto append = [&](uint32_t tile, uint32_t mask) {
+            auto append = [&](uint32_t tile, uint32_t mask) __attribute__((always_inline)) {
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(mask != 0u);
                 uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 asm volatile("" : "+v"(pre));                   // (keeps the prefix count out of a branch on "any lane active")
@@ -887,12 +916,12 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
                 if constexpr (W == 2) {                          // nothing ray-related stays live across the tile loop: re-read the queue here
                     fetch_rays(g, nxt_a, nxt_b);
 #pragma unroll
-                    for (int s = 0; s < S; ++s) prepare_ray(ray[s], nxt_a[s], nxt_b[s], wave_slot0 + (uint32_t)s * 32u + (uint32_t)col < n_rays);
+                    for (int j = 0; j < H; ++j) prepare_ray(ray[j], nxt_a[j], nxt_b[j], wave_slot0 + (uint32_t)j * kRayStride + ray_lane < n_rays);
                 }
                 u32x4 Bs[S]; float ths[S];
 #pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const MfRay &r = ray[s];
+                for (int j = 0; j < H; ++j) {
+                    const MfRay &r = ray[j];
                     const f3 ol = r.o - mk(G.cx, G.cy, G.cz);
                     const f3 cvl = cross3(r.d, ol);
                     // v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence: these are bounds, inflated by 1.001
@@ -900,10 +929,24 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
                     const float margin = mf_margin(G, ncv, no, r);
                     // empty slot: nothing survives.  Margin not finite or so large that the bf16 products could overflow (bounds NaN for
                     // non-finite vertices, huge coordinates): NaN threshold, everything survives.
-                    ths[s] = (!r.valid || debug_skip_exact == 2) ? __builtin_inff() : (margin < 1.0e30f ? -margin : __builtin_nanf(""));
-                    Bs[s].x = pack_bf16(cvl.x, cvl.y);
-                    Bs[s].y = (pack_bf16(cvl.z, 0.0f) & 0xffffu) | r.dx_hi;
-                    Bs[s].z = r.dyz; Bs[s].w = r.tail;
+                    const float th = (!r.valid || debug_skip_exact == 2) ? __builtin_inff() : (margin < 1.0e30f ? -margin : __builtin_nanf(""));
+                    const uint32_t bx = pack_bf16(cvl.x, cvl.y), by = (pack_bf16(cvl.z, 0.0f) & 0xffffu) | r.dx_hi;
+                    if constexpr (!kSplit) {
+                        Bs[j].x = bx; Bs[j].y = by; Bs[j].z = r.dyz; Bs[j].w = r.tail; ths[j] = th;
+                    } else {
+                        // The lower half built these for set 2 j, the upper half for set 2 j + 1; v_permlane32_swap of (a, b) leaves
+                        // (lower a | lower b) in a and (upper a | upper b) in b.  With a = b every lane gets the lower half's word (set 2 j)
+                        // in the first result and the upper half's (set 2 j + 1) in the second; with a = the lower half's tail word and b =
+                        // the upper half's, each half gets its own tail word of either set.
+                        const auto px = __builtin_amdgcn_permlane32_swap(bx, bx, false, false);
+                        const auto py = __builtin_amdgcn_permlane32_swap(by, by, false, false);
+                        const auto pz = __builtin_amdgcn_permlane32_swap(r.dyz, r.dyz, false, false);
+                        const auto pw = __builtin_amdgcn_permlane32_swap(r.tail, r.tail_hi, false, false);
+                        const auto pt = __builtin_amdgcn_permlane32_swap(__float_as_uint(th), __float_as_uint(th), false, false);
+                        const int s0 = 2 * j, s1 = 2 * j + 1;
+                        Bs[s0].x = px[0]; Bs[s0].y = py[0]; Bs[s0].z = pz[0]; Bs[s0].w = pw[0]; ths[s0] = __uint_as_float(pt[0]);
+                        Bs[s1].x = px[1]; Bs[s1].y = py[1]; Bs[s1].z = pz[1]; Bs[s1].w = pw[1]; ths[s1] = __uint_as_float(pt[1]);
+                    }
                 }
                 B0 = Bs[0]; B1 = Bs[1]; B2 = Bs[2]; B3 = Bs[3];
                 th0 = ths[0]; th1 = ths[1]; th2 = ths[2]; th3 = ths[3];
@@ -1048,8 +1091,8 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     if (lane == 0) store_through(wb.cand_counts + region, (uint32_t)(appended < (unsigned long long)wb.cand_region ? appended : (unsigned long long)wb.cand_region));
     if (lane == 0 && appended > (unsigned long long)*wb.cand_peak) atomicMax(wb.cand_peak, (uint32_t)(appended < 0xFFFFFFF0ull ? appended : 0xFFFFFFF0ull));   // (racy pre-check: only saves atomics)
     if (kCount) {
-        if (c_cand_lane) atomicAdd(&counters->candidates, c_cand_lane);
-        if (c_culled) atomicAdd(&counters->culled_tests, c_culled);
+        if (lane == 0 && lds_cand[wave]) atomicAdd(&counters->candidates, lds_cand[wave]);
+        if (lane == 0 && c_culled) atomicAdd(&counters->culled_tests, c_culled);
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->tri_tests, (unsigned long long)n_rays * sc.n_tri_visits);
     }
 }
