@@ -468,6 +468,48 @@ public:
         if (px.empty()) return false;
         return rtgl::write_png(path, px.data(), m_width, rtgl_local_rows(m_ctx), 4);
     }
+    // ---- error estimate (rtgl_error_estimate, include/rtgl_amd.h; extension): how noisy the accumulation image still is, per 16 x 16 tile and
+    // for the picture, from the image and the luminance snapshot the previous call left.  nullptr: its defaults (threshold 0.05, floor 0.01,
+    // quantile_permille 950, first_frames 1, flags 0) -- run() counts the frames the reference's way, so first_frames is 1.  The first call,
+    // and the first after reset_buffer() has taken effect, only takes the snapshot (summary.valid == 0).  Prints and returns false on failure.
+    bool error_estimate(const rtgl_error_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_error_estimate(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the summary of the last error_estimate() (synchronises); all zero (and a message) before the first successful one
+    rtgl_error_summary read_error_summary() const
+    {
+        rtgl_error_summary s{};
+        if (m_ctx && rtgl_read_error_summary(m_ctx, &s) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; s = rtgl_error_summary{}; }
+        return s;
+    }
+    // "render until the picture is this clean": run() in rounds of check_every frames with an error_estimate() after each, until a summary
+    // is converged at `threshold` (a relative RMSE per tile; the other parameters from `params`, nullptr: the defaults), m_quit is set or
+    // max_frames frames have been rendered by this call.  Returns the frames rendered; `summary` (if not null) receives the latest summary.
+    // The frame budget is left at the size of the last round.
+    long render_until(float threshold, long max_frames, long check_every = 16, const rtgl_error_params *params = nullptr, rtgl_error_summary *summary = nullptr)
+    {
+        rtgl_error_params p;
+        rtgl_error_defaults(&p);
+        if (params) p = *params;
+        p.threshold = threshold;
+        rtgl_error_summary s{};
+        long done = 0;
+        while (m_ctx && !m_quit && done < max_frames && check_every > 0) {
+            const long round = std::min(check_every, max_frames - done);
+            set_frame_budget(round);
+            run();
+            done += round;
+            if (!error_estimate(&p)) break;
+            s = read_error_summary();
+            if (s.valid && s.converged) break;
+        }
+        if (summary) *summary = s;
+        return done;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

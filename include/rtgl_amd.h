@@ -502,6 +502,88 @@ int rtgl_read_display_u8(rtgl_context *ctx, uint8_t *rgba, int flip);
 void *rtgl_device_display(rtgl_context *ctx);
 int rtgl_read_tonemap_exposure(rtgl_context *ctx, float *exposure);
 int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256], uint32_t *ignored);
+
+/* -- error estimate: how noisy the accumulation image still is, per 16 x 16 tile and for the whole picture, and the stop rule "render until
+ * the picture is this clean" on top of it.  No reference counterpart: the reference renders until somebody saves the image.  The image at
+ * two moments of ONE accumulation differs by a known multiple of the noise: with n and m < n real frames in it,
+ * Var(mean of n) = E[(mean_n - mean_m)^2] m / (n - m).  One squared difference per pixel is a poor estimate; the mean over a tile or over
+ * the picture is a good one.  One streaming pass over the image and a luminance SNAPSHOT of an earlier moment; the frame path is untouched.
+ * DEFINED bit for bit under the denoisers' rules (tests/error_mirror.py restates it): binary32, one rounding per operation in the order
+ * written, no contraction, correctly rounded divide, integers exact.
+ *   lum(r, g, b) = (0.25 r + 0.5 g) + 0.25 b.     W = width, H = height.
+ *   Footprint: the pixels with x < W/8*8 and y < H/8*8 (integer division).  The rest of the image is never written by a frame; it is
+ *   neither counted nor ignored.     Tiles: 16 x 16 pixels, tx = ceil(W / 16), ty = ceil(H / 16), tile row 0 is buffer row 0.
+ *   State: a snapshot plane S of one float per pixel -- the raw lum of the image when it was taken --, the snapshot's F_m and first_frames,
+ *   and an epoch kept on the host.  The snapshot is DROPPED by rtgl_error_reset, rtgl_clear_image, rtgl_write_image_f32,
+ *   rtgl_bind_device_image, any rendered frame with reset_flag != 0, and by a call whose F_n <= F_m or whose first_frames differs from the
+ *   snapshot's.  (That host-side bookkeeping is all this extension adds to those entry points.)
+ *   Per call: F_n = the `frames` of the parameters the latest frame was rendered with (frames a batching context holds are submitted
+ *   first).  The image after that frame carries the weight F_n + 1 (what the accumulation divides by); first_frames is the `frames` of the
+ *   first frame after the image was last zero -- 1 in the reference's loop, 0 for a caller who counts from 0 --, so the image holds
+ *   n = F_n + 1 - first_frames real frames and equals their mean times n / (F_n + 1).  n < 1 is RTGL_ERR_INVALID.
+ *     g_n = (float)((double)(F_n + 1) / (double)n);   m and g_m likewise from the snapshot's F_m;   c = (float)((double)m / (double)(n - m)).
+ *   Per pixel of the footprint, I the image, S the snapshot:
+ *     Ln = lum(I.rgb) g_n;  Lm = S g_m;  d = Ln - Lm;  den = ((Ln > 0) ? Ln : 0) + floor;  q = d / den;  e = q q.
+ *     The pixel COUNTS iff e - e == 0 (e is finite).  Every other pixel of the footprint goes to `ignored`.
+ *   Per tile: sum = the balanced pairwise tree over the 256 row-major indices of the tile (index = 16 row + column): adjacent pairs are
+ *     added first, then pairs of pairs, and so on, eight levels; pixels that do not count and positions outside the footprint contribute
+ *     +0.  count = the pixels that count (an integer).  mse = (sum / (float)count) c;  converged = count > 0 and mse <= threshold threshold.
+ *     A tile with count == 0 has the record {0, 0, 0, 0} and is not VALID.
+ *   Whole picture: lane t of 256 adds the tile sums t, t + 256, ... (tile index = tx row + column) in ascending order, starting from +0;
+ *     the same 256-leaf tree then combines the lanes to SUM.  N = the sum of the counts;  mse = (SUM / (float)N) c, and 0 if N == 0;
+ *     max_tile_mse = the maximum over the valid tiles, 0 if there is none;  tiles_valid, tiles_converged and
+ *     pixels_ignored = (footprint pixels) - N are integers;
+ *     converged = tiles_valid > 0 and tiles_converged 1000 >= tiles_valid quantile_permille, in 64-bit integers.
+ *   No output can be a NaN.  Sums may reach +inf: that is defined and means "not converged".
+ *   Snapshot handling: after the estimate the snapshot becomes the current image's lum with F_m = F_n; with RTGL_ERROR_KEEP_SNAPSHOT and
+ *   an existing snapshot it is left as it is.  A call without a usable snapshot takes one, writes a summary with valid = 0 and everything
+ *   else 0, zeroes the tile records and returns RTGL_OK.
+ * Defaults (rtgl_error_defaults, and a NULL params): threshold 0.05, floor 0.01, quantile_permille 950, first_frames 1, flags 0.
+ * Like its neighbours the call first submits the frames a batching context holds, enqueues its two kernels on the context's stream and
+ * returns without waiting; it writes only its own buffers (snapshot, tile records, summary), which the first call allocates and which are
+ * freed with the context: image, planes, RNG states, the denoised, temporal and display buffers are only read or not touched at all.
+ * rtgl_read_error_summary and rtgl_read_error_tiles synchronise; the latter copies tx x ty records, row by row, and stores tx and ty
+ * where the pointers are not NULL.  rtgl_device_error_tiles: the records on the device (torch interop; valid until the context is destroyed).
+ * RTGL_ERR_INVALID: NULL context or output pointer; threshold or floor not finite or not > 0; quantile_permille outside 1..1000;
+ * first_frames < 0; unknown flag bits; non-zero reserved words; n < 1; a footprint of 2^32 pixels or more.  RTGL_ERR_STATE: no frame has been rendered on this context; the
+ * context is tiled or multi-device (a strip is not the picture; out of scope, like its neighbours); the read-outs before the first
+ * successful rtgl_error_estimate (rtgl_device_error_tiles: NULL).
+ * Limits: luminance only; radiance not yet seen cannot be estimated from what has been seen, so scenes ridden with fireflies are
+ * UNDER-estimated (DESIGN.md 5.10 has figures); a tile that is all sky reads 0 and converged; single-device, untiled contexts only. */
+enum { RTGL_ERROR_KEEP_SNAPSHOT = 1 };
+typedef struct rtgl_error_params {
+    float    threshold;          /* > 0: the relative RMSE a tile must be at or below to be converged */
+    float    floor;              /* > 0: added to the luminance a difference is taken relative to */
+    uint32_t quantile_permille;  /* 1..1000: the share of the valid tiles that must be converged, in 1/1000 */
+    int32_t  first_frames;       /* >= 0: the `frames` of the first frame after the image was last zero */
+    uint32_t flags;              /* RTGL_ERROR_KEEP_SNAPSHOT */
+    uint32_t reserved[3];        /* must be 0 */
+} rtgl_error_params;             /* 32 bytes */
+typedef struct rtgl_error_summary {
+    uint32_t valid;              /* 1: an estimate; 0: the call only took a snapshot, everything below is 0 */
+    uint32_t converged;
+    int32_t  frames_now;         /* F_n */
+    int32_t  frames_snapshot;    /* F_m */
+    uint32_t tiles_valid;
+    uint32_t tiles_converged;
+    uint32_t pixels_ignored;
+    float    scale;              /* c */
+    float    mse;                /* relative MSE of the whole picture */
+    float    max_tile_mse;
+    uint32_t reserved[6];
+} rtgl_error_summary;            /* 64 bytes */
+typedef struct rtgl_error_tile {
+    float    sum;
+    float    mse;
+    uint32_t count;
+    uint32_t converged;
+} rtgl_error_tile;               /* 16 bytes */
+int rtgl_error_defaults(rtgl_error_params *out);
+int rtgl_error_estimate(rtgl_context *ctx, const rtgl_error_params *params);
+int rtgl_error_reset(rtgl_context *ctx);                    /* drops the snapshot: the next rtgl_error_estimate takes a new one */
+int rtgl_read_error_summary(rtgl_context *ctx, rtgl_error_summary *out);
+int rtgl_read_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty);
+void *rtgl_device_error_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -23,6 +23,7 @@
 #include "rt_temporal.hpp"
 #include "rt_temporal_clip.hpp"
 #include "rt_tonemap.hpp"
+#include "rt_error.hpp"
 #include "rt_node_walk.hpp"
 
 #pragma clang fp contract(off)
@@ -285,6 +286,11 @@ struct rtgl_context {
     // rtgl_tonemap_reset; tone_auto: the latest call solved its exposure on the device, otherwise it used tone_exposure
     uchar4 *d_display = nullptr; uint32_t *d_tone_state = nullptr;
     bool has_display = false, tone_prev = false, tone_auto = false; int tone_set = 0, tone_hist_set = -1; float tone_exposure = 1.0f;
+    // rtgl_error_estimate (rt_error.hpp): the luminance snapshot, the tile records and the summary, allocated by the first call.  The
+    // snapshot is usable while err_snap_epoch == err_epoch: every event that drops it (header, "error estimate") advances err_epoch.
+    // err_fm, err_first: the snapshot's `frames` and first_frames; err_rendered, err_fn: a frame has been rendered, and its `frames`
+    float *d_err_snapshot = nullptr; uint4 *d_err_tiles = nullptr; uint32_t *d_err_summary = nullptr;
+    uint64_t err_epoch = 1, err_snap_epoch = 0; int32_t err_fm = 0, err_first = 0, err_fn = 0; bool err_rendered = false, has_error = false;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -481,7 +487,8 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
                      ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
                      ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near,
                      ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1],
-                     ctx->d_tm_moments[0], ctx->d_tm_moments[1], ctx->d_display, ctx->d_tone_state };
+                     ctx->d_tm_moments[0], ctx->d_tm_moments[1], ctx->d_display, ctx->d_tone_state,
+                     ctx->d_err_snapshot, ctx->d_err_tiles, ctx->d_err_summary };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
@@ -1422,6 +1429,10 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
 static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch)
 {
     const uint32_t B = (uint32_t)batch.size();
+    for (const FrameParams &f : batch) {                 // rtgl_error_estimate: a reset frame starts a new accumulation; the latest frame's `frames`
+        if (f.reset_flag) ++ctx->err_epoch;
+        ctx->err_fn = f.frames; ctx->err_rendered = true;
+    }
     if (ctx->visits_dirty) { int rc = rebuild_sphere_visits(ctx); if (rc) return rc; }
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
     if (ctx->opt_rng_state && !ctx->d_rng)
@@ -1602,6 +1613,7 @@ extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
 {
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    ++ctx->err_epoch;                                   // (rtgl_error_estimate: another image, the snapshot is dropped)
     if (!ctx->parts.empty()) {                          // scatter the rows to their owners
         ctx->gathered = false;
         std::vector<float> local;
@@ -1625,6 +1637,7 @@ extern "C" int rtgl_clear_image(rtgl_context *ctx)
     FANOUT(ctx, rtgl_clear_image(part));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;                              // the first-hit planes' mean restarts with the next frame (their contents stay)
+    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the snapshot is dropped)
     return RTGL_OK;
 }
 
@@ -1669,6 +1682,7 @@ extern "C" int rtgl_bind_device_image(rtgl_context *ctx, void *dptr)
     ENTER(ctx);
     if (!ctx->parts.empty()) return fail(ctx, RTGL_ERR_STATE, "a multi-device context renders into its own per-device tile buffers");
     ctx->d_image = dptr ? (float4 *)dptr : ctx->d_image_own;
+    ++ctx->err_epoch;                                     // (rtgl_error_estimate: another image, the snapshot is dropped)
     return RTGL_OK;
 }
 
@@ -2336,6 +2350,105 @@ extern "C" int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256]
     return RTGL_OK;
 }
 
+// ---- rtgl_error_estimate: the noise level of the accumulation image and the stop rule (rt_error.hpp) -----------------------------------
+extern "C" int rtgl_error_defaults(rtgl_error_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->threshold = 0.05f; out->floor = 0.01f; out->quantile_permille = 950u; out->first_frames = 1;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_error_estimate(rtgl_context *ctx, const rtgl_error_params *params)
+{
+    ENTER(ctx);
+    rtgl_error_params P;
+    rtgl_error_defaults(&P);
+    if (params) P = *params;
+    for (float v : { P.threshold, P.floor })
+        if (!std::isfinite(v) || !(v > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: threshold and floor must be finite and > 0");
+    if (P.quantile_permille < 1u || P.quantile_permille > 1000u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: quantile_permille must be in 1..1000");
+    if (P.first_frames < 0) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: first_frames must be >= 0");
+    if (P.flags & ~(uint32_t)RTGL_ERROR_KEEP_SNAPSHOT) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: only flag bit 0 (keep the snapshot) is defined");
+    for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_error_estimate: a tiled or multi-device context holds strips, and the estimate is of the whole picture (out of scope): render on a single-device context");
+    if (!ctx->err_rendered) return fail(ctx, RTGL_ERR_STATE, "rtgl_error_estimate: no frame has been rendered on this context");
+    const int64_t fn = ctx->err_fn, n = fn + 1 - (int64_t)P.first_frames;
+    if (n < 1) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: the latest frame's `frames` is below first_frames: the image would hold no frame");
+    const int fw = ctx->width / 8 * 8, fh = ctx->height / 8 * 8;
+    if ((uint64_t)fw * (uint64_t)fh > 0xFFFFFFFFull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: the footprint does not fit 32-bit counts");
+    const unsigned tx = (unsigned)((ctx->width + kErrTile - 1) / kErrTile), ty = (unsigned)((ctx->height + kErrTile - 1) / kErrTile);
+    if (!ctx->d_err_tiles) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_tiles, (size_t)tx * ty * sizeof(uint4)));
+    if (!ctx->d_err_summary) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_summary, kErrSummaryWords * 4));
+    if (!ctx->d_err_snapshot) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_snapshot, (size_t)ctx->height * ctx->width * sizeof(float)));
+    // a snapshot of an earlier moment of THIS accumulation, counted the same way
+    const bool usable = ctx->err_snap_epoch == ctx->err_epoch && fn > (int64_t)ctx->err_fm && P.first_frames == ctx->err_first;
+    const bool keep = usable && (P.flags & RTGL_ERROR_KEEP_SNAPSHOT);
+    ErrorTilesArgs a{};
+    a.image = ctx->d_image; a.snapshot = ctx->d_err_snapshot; a.tiles = ctx->d_err_tiles;
+    a.width = ctx->width; a.fw = fw; a.fh = fh;
+    a.floor_ = P.floor; a.threshold = P.threshold;
+    ErrorSolveArgs s{};
+    s.tiles = ctx->d_err_tiles; s.summary = ctx->d_err_summary; s.n_tiles = tx * ty; s.valid = usable ? 1u : 0u;
+    s.footprint = (uint32_t)((uint64_t)fw * (uint64_t)fh); s.quantile_permille = P.quantile_permille;
+    if (usable) {
+        const int64_t m = (int64_t)ctx->err_fm + 1 - (int64_t)P.first_frames;      // (>= 1: the call that took the snapshot checked it)
+        a.g_n = (float)((double)(fn + 1) / (double)n);
+        a.g_m = (float)((double)((int64_t)ctx->err_fm + 1) / (double)m);
+        a.c = (float)((double)m / (double)(n - m));
+        s.c = a.c; s.frames_now = (int32_t)fn; s.frames_snapshot = ctx->err_fm;
+    }
+    const dim3 grid(tx, ty);
+    if (!usable) hipLaunchKernelGGL((error_tiles_kernel<false, false>), grid, dim3(256), 0, ctx->stream, a);
+    else if (keep) hipLaunchKernelGGL((error_tiles_kernel<true, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((error_tiles_kernel<true, false>), grid, dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(error_solve_kernel, dim3(1), dim3(256), 0, ctx->stream, s);
+    HIPCHK(ctx, hipGetLastError());
+    if (!keep) { ctx->err_snap_epoch = ctx->err_epoch; ctx->err_fm = (int32_t)fn; ctx->err_first = P.first_frames; }
+    ctx->has_error = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_error_reset(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    ++ctx->err_epoch;                                     // (the summary and the tile records of the latest call stay readable)
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_error_summary(rtgl_context *ctx, rtgl_error_summary *out)
+{
+    ENTER(ctx);
+    if (!out) return fail(ctx, RTGL_ERR_INVALID, "out is NULL");
+    if (!ctx->has_error) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_error_summary: no rtgl_error_estimate call has succeeded on this context");
+    static_assert(sizeof(rtgl_error_summary) == kErrSummaryWords * 4 && sizeof(rtgl_error_params) == 32 && sizeof(rtgl_error_tile) == sizeof(uint4), "the layouts of the header");
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_err_summary, sizeof *out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "tiles is NULL");
+    if (!ctx->has_error) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_error_tiles: no rtgl_error_estimate call has succeeded on this context");
+    const uint32_t nx = (uint32_t)((ctx->width + kErrTile - 1) / kErrTile), ny = (uint32_t)((ctx->height + kErrTile - 1) / kErrTile);
+    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_err_tiles, (size_t)nx * ny * sizeof(rtgl_error_tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tx) *tx = nx;
+    if (ty) *ty = ny;
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_error_tiles(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_error) { ctx->error = "rtgl_device_error_tiles: no rtgl_error_estimate call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_err_tiles;
+}
+
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
     ENTER(ctx);
@@ -2451,6 +2564,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
         if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
         for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1], ctx->d_tm_moments[0], ctx->d_tm_moments[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
         if (ctx->d_display) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
+        if (ctx->d_err_snapshot) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4 + (size_t)((ctx->width + 15) / 16) * ((ctx->height + 15) / 16) * 16;
         b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
         *value = (int)((b + (1u << 20) - 1) >> 20);
     }

@@ -34,6 +34,10 @@ TEMPORAL_CLIP_DEFAULTS = dict(sigma_scale=2.0, clip_history=3.0, sigma_normal=0.
 TONEMAP_DEFAULTS = dict(source=0, op=1, auto=True, exposure=1.0, key=0.18, white=4.0, adapt=1.0, exposure_min=2.0 ** -16, exposure_max=2.0 ** 16,
                         low_permille=100, high_permille=20)
 TONEMAP_AUTO_EXPOSURE = 1
+# rtgl_error_estimate
+ERROR_DEFAULTS = dict(threshold=0.05, floor=0.01, quantile_permille=950, first_frames=1, keep_snapshot=False)
+ERROR_KEEP_SNAPSHOT = 1
+ERROR_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("count", np.uint32), ("converged", np.uint32)])
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -53,6 +57,8 @@ ABI_SYMBOLS = [
     "rtgl_temporal_clip_defaults", "rtgl_temporal_clip",
     "rtgl_tonemap_defaults", "rtgl_tonemap", "rtgl_tonemap_reset", "rtgl_read_display_u8", "rtgl_device_display",
     "rtgl_read_tonemap_exposure", "rtgl_read_tonemap_histogram",
+    "rtgl_error_defaults", "rtgl_error_estimate", "rtgl_error_reset", "rtgl_read_error_summary", "rtgl_read_error_tiles",
+    "rtgl_device_error_tiles",
 ]
 
 
@@ -109,6 +115,19 @@ class CTonemapParams(C.Structure):
     _fields_ = [("source", C.c_uint32), ("op", C.c_uint32), ("flags", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float),
                 ("white", C.c_float), ("adapt", C.c_float), ("exposure_min", C.c_float), ("exposure_max", C.c_float),
                 ("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class CErrorParams(C.Structure):
+    """rtgl_error_params"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("quantile_permille", C.c_uint32), ("first_frames", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class CErrorSummary(C.Structure):
+    """rtgl_error_summary"""
+    _fields_ = [("valid", C.c_uint32), ("converged", C.c_uint32), ("frames_now", C.c_int32), ("frames_snapshot", C.c_int32),
+                ("tiles_valid", C.c_uint32), ("tiles_converged", C.c_uint32), ("pixels_ignored", C.c_uint32), ("scale", C.c_float),
+                ("mse", C.c_float), ("max_tile_mse", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
 def build_library(force: bool = False) -> str:
@@ -183,6 +202,12 @@ def load_library() -> C.CDLL:
     L.rtgl_device_display.argtypes = [vp]; L.rtgl_device_display.restype = vp
     L.rtgl_read_tonemap_exposure.argtypes = [vp, C.POINTER(C.c_float)]
     L.rtgl_read_tonemap_histogram.argtypes = [vp, vp, C.POINTER(u32)]
+    L.rtgl_error_defaults.argtypes = [C.POINTER(CErrorParams)]
+    L.rtgl_error_estimate.argtypes = [vp, C.POINTER(CErrorParams)]
+    L.rtgl_error_reset.argtypes = [vp]
+    L.rtgl_read_error_summary.argtypes = [vp, C.POINTER(CErrorSummary)]
+    L.rtgl_read_error_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.rtgl_device_error_tiles.argtypes = [vp]; L.rtgl_device_error_tiles.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -518,6 +543,52 @@ class Context:
         self._chk(self.lib.rtgl_read_tonemap_histogram(self.h, _ptr(hist), C.byref(ignored)))
         return hist, int(ignored.value)
 
+    # --- error estimate
+    def error_estimate(self, threshold=None, floor=None, quantile_permille=None, first_frames=None, keep_snapshot=None):
+        """Enqueue the error estimate of the accumulation image (rtgl_error_estimate; does not wait): the relative MSE of the luminance
+        per 16 x 16 tile and for the picture, from the image and the snapshot the previous call left, and whether `quantile_permille` of
+        the tiles are at or below `threshold` (a relative RMSE).  first_frames: the `frames` of the first frame after the image was last
+        zero.  keep_snapshot: leave an existing snapshot as it is.  The first call (and the first after anything that restarts the
+        accumulation) only takes the snapshot: its summary has valid = 0.  None keeps the library's default (ERROR_DEFAULTS)."""
+        p = CErrorParams()
+        self._chk(self.lib.rtgl_error_defaults(C.byref(p)))
+        for name, value in (("threshold", threshold), ("floor", floor)):
+            if value is not None:
+                setattr(p, name, float(value))
+        for name, value in (("quantile_permille", quantile_permille), ("first_frames", first_frames)):
+            if value is not None:
+                setattr(p, name, int(value))
+        if keep_snapshot is not None:
+            p.flags = (p.flags & ~ERROR_KEEP_SNAPSHOT) | (ERROR_KEEP_SNAPSHOT if keep_snapshot else 0)
+        self._chk(self.lib.rtgl_error_estimate(self.h, C.byref(p)))
+
+    def error_reset(self):
+        """Drop the snapshot: the next error_estimate() takes a new one."""
+        self._chk(self.lib.rtgl_error_reset(self.h))
+
+    def read_error_summary(self) -> dict:
+        """The summary of the last error_estimate() (synchronises): valid, converged, frames_now, frames_snapshot, tiles_valid,
+        tiles_converged, pixels_ignored as int, scale, mse, max_tile_mse as np.float32."""
+        s = CErrorSummary()
+        self._chk(self.lib.rtgl_read_error_summary(self.h, C.byref(s)))
+        out = {k: int(getattr(s, k)) for k in ("valid", "converged", "frames_now", "frames_snapshot", "tiles_valid", "tiles_converged", "pixels_ignored")}
+        raw = np.frombuffer(bytes(s), np.float32)                      # (the bits, not a round trip through a Python float)
+        out.update(scale=raw[7], mse=raw[8], max_tile_mse=raw[9])
+        return out
+
+    def read_error_tiles(self) -> np.ndarray:
+        """The tile records of the last error_estimate() as a structured array (ty, tx) of ERROR_TILE_DTYPE; tile row 0 = image row 0."""
+        tx, ty = (self.width + 15) // 16, (self.height + 15) // 16
+        out = np.zeros((ty, tx), ERROR_TILE_DTYPE)
+        nx, ny = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.rtgl_read_error_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
+        assert (int(nx.value), int(ny.value)) == (tx, ty)
+        return out
+
+    def device_error_tiles_ptr(self) -> int:
+        """Device pointer of the tile records (0 before the first successful error_estimate(): see the context's last error)."""
+        return int(self.lib.rtgl_device_error_tiles(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -587,6 +658,30 @@ class HeadlessRenderer(FrameLoop):
 
     def read_display(self, flip: bool = False) -> np.ndarray:
         return self.ctx.read_display(flip)
+
+    def error_estimate(self, **params):
+        self.ctx.error_estimate(**params)
+
+    def read_error_summary(self) -> dict:
+        return self.ctx.read_error_summary()
+
+    def render_until(self, threshold: float, max_frames: int, check_every: int = 16, **params):
+        """Render until the picture is this clean: frames as render_frame() makes them, an error_estimate(threshold=threshold, **params)
+        after every `check_every` of them (and after the last one), stopping at the first converged summary or after `max_frames`
+        frames.  Returns (frames rendered by this call, the latest summary).  The frames are counted the reference's way: first_frames
+        is 1 unless given."""
+        if max_frames < 1 or check_every < 1:
+            raise ValueError("render_until: max_frames and check_every must be >= 1")
+        done, summary = 0, None
+        while done < max_frames:
+            for _ in range(min(check_every, max_frames - done)):
+                self.render_frame(sync=False)
+                done += 1
+            self.ctx.error_estimate(threshold=threshold, **params)
+            summary = self.ctx.read_error_summary()
+            if summary["valid"] and summary["converged"]:
+                break
+        return done, summary
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
