@@ -587,7 +587,11 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads
- * per work item = per block's LDS-resident chunk, 1..32), "scan_waves" (waves per SIMD of the kernel-4 scan: 0 default (= 2), 1, 2), "scan_dynamic" (work distribution of the kernel-4 scan: 0 chosen by the mesh (default), 1 static, 2 dynamic), "cull" (packet culling: a granule of 128 rays skips the tiles
+ * per work item = per block's LDS-resident chunk, 1..32), "scan_waves" (waves per SIMD of the kernel-4 scan: 0 default (= 2), 1, 2), "scan_dynamic" (work distribution of the kernel-4 scan: 0 chosen by the mesh (default), 1 static turns, 2 dynamic claims, 3 planned equal-cost intervals, 4 turns + a claimed tail),
+ * "narrow_fused" (kernel 4, also RTGL_AMD_NARROW_FUSED, read when a context is created: who gives the survivors of the scan their exact test.  0: narrow_phase_kernel,
+ * launched behind every scan launch; 1 (default): every scan wave tests the records of its own candidate region when it has run out of work items, beside the waves that are still
+ * scanning, and narrow_phase_kernel is not launched.  The image is the same bit for bit -- hits merge by an atomic minimum -- on every path: single frames, "frame_batch", the
+ * strips of a rank), "cull" (packet culling: a granule of 128 rays skips the tiles
  * of 10 triangles for which every one of its rays is certified to be rejected by the reference's own test: 0 off, 1 on the camera-ray
  * bounce, 2 on every bounce with the queues as they come, 3 (default) on the camera-ray bounce and on every bounce whose queue was BINNED
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"

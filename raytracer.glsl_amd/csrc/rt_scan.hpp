@@ -18,8 +18,8 @@
 //
 // Around the stream: a block stages the A tiles of a chunk of <= 32 quads in LDS and its waves work through (granule of 128 rays,
 // chunk) items -- handed out in fixed turns or claimed from counters (scan_solo_kernel below); survivors go to a per-wave LDS queue
-// and from there, as dense records, to the wave's own region of the candidate buffer for narrow_phase_kernel (what does not fit is
-// tested in place); packet_cull_kernel certifies, per granule and quad, that every ray misses every triangle by the reference's own
+// and from there, as dense records, to the wave's own region of the candidate buffer, which the wave itself drains at its end
+// (drain_region; narrow_phase_kernel where the host asks for the separate launch; what does not fit is tested in place); packet_cull_kernel certifies, per granule and quad, that every ray misses every triangle by the reference's own
 // arithmetic (rt_mfma.hpp, MfCull) so that the scan can skip the quad.
 #pragma once
 #include <type_traits>
@@ -237,6 +237,87 @@ __device__ __forceinline__ void exact_and_merge_at(const MfView &mf, const RayQu
     TriRay tr; tr.o = mk(a.x, a.y, a.z); tr.d = mk(a.w, b.x, b.y); tr.cv = cross3(tr.d, tr.o); tr.ncv = tr.nd = 0.0f;
     const float t = tri_exact(mf.edges_s[pos], mf.planes_s[pos], tr);
     if (kEps < t && t < kInf) atomicMin(&best[slot], ((unsigned long long)__float_as_uint(t) << 32) | v);
+}
+
+// ---- tail drain of a scan wave (scan_solo_kernel, `narrow_fused`): the wave tests the n_rec records of its own candidate region,
+// exactly as narrow_phase_kernel would (mask expanded, positions behind the last triangle skipped, the same exact test and merge).
+// narrow_phase_kernel is a chain of dependent round trips per record (record -> ray and triangle -> merge) with ONE record per lane
+// in flight; here a lane takes kDrainFly records per turn: their loads are issued back to back, then their rays', then -- once per
+// set bit of the fullest mask -- the triangle records of all of them.  A turn is 64 x kDrainFly records, the mean region of C2 two
+// turns.  Every load is unconditional, from a clamped index (a guarded load is an EXEC-masked block that waits for itself before the
+// next one starts), and the triangle records are copied out before the test's early exits can make their loads dependent.
+//
+// Read-back of the records.  This wave wrote them in flush() with store_through (global_store ... sc0 sc1: written through to memory
+// at system scope, no dirty line left in the L2).  What the drain relies on: (1) the caller's s_waitcnt vmcnt(0) between the last
+// store and the first load -- nothing else is assumed to order a load behind an earlier store of the same wave; when the wait
+// returns, every one of the wave's stores has been acknowledged by the memory side; (2) the loads carry sc1 (relaxed atomic loads at agent scope): they are served by the L2, never
+// by a line of this CU's vector L1, which a write-through store does not refresh and which could hold the region's previous
+// contents had the wave read it earlier in the launch.  No other wave writes the region during the launch and no other CU reads it.
+constexpr int kDrainFly = 4;
+typedef float drain_f4 __attribute__((ext_vector_type(4)));
+static_assert(sizeof(TriEdges) == 80 && sizeof(TriPlane) == 32 && alignof(TriEdges) == 16 && alignof(TriPlane) == 16, "drain_region reads these as rows of 16 bytes");
+__device__ __forceinline__ void drain_region(const SceneView &sc, const MfView &mf, const RayQueue &qin, unsigned long long *best,
+                                             const unsigned long long *recs, uint32_t n_rec, uint32_t lane)
+{
+    constexpr int K = kDrainFly;
+    const uint32_t last_tri = sc.n_tri_visits - 1u;               // (n_rec > 0: there are triangles)
+    for (uint32_t i0 = 0; i0 < n_rec; i0 += 64u * (uint32_t)K) {
+        unsigned long long rec[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) rec[j] = __hip_atomic_load(recs + min(i0 + (uint32_t)j * 64u + lane, n_rec - 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t slot[K], pos5[K], um[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const uint32_t hi = (uint32_t)(rec[j] >> 32);
+            slot[j] = (uint32_t)rec[j]; pos5[j] = hi >> 5;
+            um[j] = i0 + (uint32_t)j * 64u + lane < n_rec ? hi & 31u : 0u;      // (behind the last record: the last record's ray, no triangle)
+        }
+        float4 a[K], b[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) a[j] = qin.a[slot[j]];
+#pragma unroll
+        for (int j = 0; j < K; ++j) b[j] = qin.b[slot[j]];
+        TriRay tr[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) { tr[j].o = mk(a[j].x, a[j].y, a[j].z); tr[j].d = mk(a[j].w, b[j].x, b[j].y); tr[j].cv = cross3(tr[j].d, tr[j].o); tr[j].ncv = tr[j].nd = 0.0f; }
+        while ((um[0] | um[1] | um[2] | um[3]) != 0u) {
+            static_assert(K == 4, "the loop condition names the masks");
+            // one set bit of each record's mask: positions first, then the 7 x 16 bytes of every triangle (TriEdges 80 B, TriPlane
+            // 32 B) and its visit index back to back, then -- the empty statements -- all of them in registers before the first test
+            // (tri_exact leaves after each failed edge: the compiler otherwise sinks the later rows' loads behind those exits)
+            bool on[K]; uint32_t p[K], v[K]; drain_f4 e[K][5], pl[K][2];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t pos = pos5[j] + (um[j] ? (uint32_t)__builtin_ctz(um[j]) : 0u);
+                on[j] = um[j] != 0u && pos < sc.n_tri_visits;                   // (padding rows behind the last triangle)
+                um[j] &= um[j] - 1u;
+                p[j] = min(pos, last_tri);
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const drain_f4 *const ep = reinterpret_cast<const drain_f4 *>(mf.edges_s + p[j]), *const pp = reinterpret_cast<const drain_f4 *>(mf.planes_s + p[j]);
+#pragma unroll
+                for (int k = 0; k < 5; ++k) e[j][k] = ep[k];
+                pl[j][0] = pp[0]; pl[j][1] = pp[1]; v[j] = mf.order[p[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) asm volatile("" : "+v"(e[j][k]));
+                asm volatile("" : "+v"(pl[j][0]), "+v"(pl[j][1]), "+v"(v[j]));
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                TriEdges T; TriPlane P;
+                T.e0x = e[j][0].x; T.e0y = e[j][0].y; T.e0z = e[j][0].z; T.e1x = e[j][0].w; T.e1y = e[j][1].x; T.e1z = e[j][1].y; T.e2x = e[j][1].z; T.e2y = e[j][1].w; T.e2z = e[j][2].x;
+                T.m0x = e[j][2].y; T.m0y = e[j][2].z; T.m0z = e[j][2].w; T.m1x = e[j][3].x; T.m1y = e[j][3].y; T.m1z = e[j][3].z; T.m2x = e[j][3].w; T.m2y = e[j][4].x; T.m2z = e[j][4].y;
+                T.bound_e = e[j][4].z; T.bound_m = e[j][4].w;
+                P.nx = pl[j][0].x; P.ny = pl[j][0].y; P.nz = pl[j][0].z; P.v0x = pl[j][0].w; P.v0y = pl[j][1].x; P.v0z = pl[j][1].y; P.material = 0; P.pad = 0;
+                const float t = tri_exact(T, P, tr[j]);
+                if (on[j] && kEps < t && t < kInf) atomicMin(&best[slot[j]], ((unsigned long long)__float_as_uint(t) << 32) | v[j]);
+            }
+        }
+    }
 }
 
 constexpr int kSoloSets = 4;                                      // 32-ray sets per wave: 512 rays per block of four waves
@@ -554,7 +635,7 @@ __device__ __forceinline__ unsigned long long *solo_cand_words()
 //     faster: 8 chunks, 32 blocks each).
 template <bool kCount, int W, int kDist>
 __global__ void __launch_bounds__(256 * W) __attribute__((amdgpu_waves_per_eu(W, W)))
-scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint32_t chunk_quads, uint32_t n_chunks, Counters *__restrict__ counters, int debug_skip_exact, int cull)
+scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint32_t chunk_quads, uint32_t n_chunks, Counters *__restrict__ counters, int debug_skip_exact, int cull, int narrow_fused)
 {
     using Cfg = SoloCfg;
     constexpr bool dynamic = kDist == 1, planned = kDist == 2, hybrid = kDist == 3;  // (a template parameter: the static form carries none of the claiming state)
@@ -1065,6 +1146,17 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         }
         flush();                                               // what the wave's last items of this chunk left in its queue
         if (!dynamic && !planned) break;                       // static: a block stays with the chunk it started on
+    }
+    // ---- tail drain (`narrow_fused`, wave-uniform): the wave has no item left -- its last flush() and the last block-wide barrier it
+    // takes are behind it -- and its region is complete: it tests its own records here, beside the matrix work of the waves that are
+    // still scanning, instead of leaving them to a narrow_phase_kernel launch that cannot start before the slowest wave has ended.
+    // Pairs that did not fit the region were tested by flush() and are not among the records.
+    if (narrow_fused) {
+        const uint32_t n_rec = (uint32_t)(appended < (unsigned long long)wb.cand_region ? appended : (unsigned long long)wb.cand_region);
+        if (n_rec) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the records' write-through stores have completed (drain_region)
+            drain_region(sc, mf, qin, best, reinterpret_cast<const unsigned long long *>(cand), n_rec, (uint32_t)lane);
+        }
     }
 #ifdef RT_SOLO_STAMPS
     if (lane == 0 && mf.dbg_log) {

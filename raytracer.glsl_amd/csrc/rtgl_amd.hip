@@ -235,6 +235,7 @@ struct rtgl_context {
     void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
     uint32_t *d_sort_hist = nullptr; uint32_t sort_bits_alloc = 0;      // two sets of bin counters, used in turns
     int sort_set = 0; uint32_t sort_set_bits = 0; bool sort_sets_clean = false;      // the set the next binned bounce counts in; false: zero both first (fresh, or a frame was abandoned half way)
+    int opt_narrow_fused = 1;                // kernel 4: 1 (default) the scan waves test their own survivors at their end (rt_scan.hpp, tail drain), 0 narrow_phase_kernel does (RTGL_AMD_NARROW_FUSED)
     int opt_sort_move = 1;                   // ray binning's move (rt_wavefront.hpp, WaveBuffers): 1 gathered by packet_cull_kernel, 0 scattered (RTGL_AMD_SORT_MOVE)
     float mesh_lo[3] = {0.0f, 0.0f, 0.0f}, mesh_hi[3] = {0.0f, 0.0f, 0.0f}, mesh_ext = 0.0f;       // box of the triangles' finite vertices (origin cells of the bin key)
     uint2 *d_cand = nullptr; uint32_t cand_regions = 0, cand_region_pairs = 0, cand_region_target = 0; bool cand_fixed = false;
@@ -416,6 +417,7 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     if (const char *k = getenv("RTGL_AMD_SCAN_WAVES")) { const int v = atoi(k); if (v >= 0 && v <= 2) ctx->opt_scan_waves = v; }   // A/B of the scan's occupancy
     if (const char *k = getenv("RTGL_AMD_FRAME_BATCH")) { const int v = atoi(k); if (v >= 1 && v <= (int)kBatchMax) ctx->opt_frame_batch = v; }
     if (const char *k = getenv("RTGL_AMD_SCAN_DYNAMIC")) { const int v = atoi(k); if (v >= 0 && v <= 4) ctx->opt_scan_dynamic = v; }   // ... and of its work distribution
+    if (const char *k = getenv("RTGL_AMD_NARROW_FUSED")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_narrow_fused = v; }   // A/B of the scan's tail drain
     if (const char *k = getenv("RTGL_AMD_SORT_MOVE")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_sort_move = v; }   // A/B of ray binning's move
     *out = ctx;
     return RTGL_OK;
@@ -1237,7 +1239,16 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
     }
     // (testing the survivors of small launches in place instead of launching the narrow phase was measured: never faster --
     // rank of eight 0.73 -> 0.76-0.85 ms)
-#define RTGL_LAUNCH_SCAN(C, WW, D) hipLaunchKernelGGL((scan_solo_kernel<C, WW, D>), dim3(blocks), dim3(256 * WW), lds, ctx->stream, sc, ctx->wb, mf, bounce, chunk_quads, chunks, ctx->d_counters, ctx->opt_debug_skip_exact, cull)
+    // "narrow_fused": every scan wave tests the records of its own region when it has run out of items (rt_scan.hpp, tail drain), and
+    // the narrow phase is not launched.  (Not the experiment above, which ran the tests inside flush(), in the middle of the item loop.)
+    // C2 +2.2 %, C5 +1.2 %, C4 +1.5 %: the scan launches grow by 109 us per C2 frame, the narrow phase's 152 us go (DESIGN.md 9 item 2;
+    // profiles/narrow_fused_c2/ab.txt).  The stamps builds keep the separate launch: their per-bounce bookkeeping lives in narrow_phase_kernel.
+#ifdef RT_SOLO_STAMPS
+    const int fused = 0;
+#else
+    const int fused = ctx->opt_narrow_fused;
+#endif
+#define RTGL_LAUNCH_SCAN(C, WW, D) hipLaunchKernelGGL((scan_solo_kernel<C, WW, D>), dim3(blocks), dim3(256 * WW), lds, ctx->stream, sc, ctx->wb, mf, bounce, chunk_quads, chunks, ctx->d_counters, ctx->opt_debug_skip_exact, cull, fused)
 #define RTGL_LAUNCH_SCAN_W(C, D) do { if (W == 2) RTGL_LAUNCH_SCAN(C, 2, D); else RTGL_LAUNCH_SCAN(C, 1, D); } while (0)
     if (dist == 1) { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 1); else RTGL_LAUNCH_SCAN_W(false, 1); }
     else if (dist == 2) { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 2); else RTGL_LAUNCH_SCAN_W(false, 2); }
@@ -1246,7 +1257,7 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
 #undef RTGL_LAUNCH_SCAN_W
 #undef RTGL_LAUNCH_SCAN
     HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(narrow_phase_kernel, dim3(blocks * waves, kNarrowSplit), dim3(256), 0, ctx->stream, sc, ctx->wb, mf, bounce, blocks * waves);
+    if (!fused) hipLaunchKernelGGL(narrow_phase_kernel, dim3(blocks * waves, kNarrowSplit), dim3(256), 0, ctx->stream, sc, ctx->wb, mf, bounce, blocks * waves);
     return RTGL_OK;
 }
 
@@ -2478,6 +2489,9 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
     } else if (!strcmp(key, "scan_dynamic")) {
         if (value < 0 || value > 4) return fail(ctx, RTGL_ERR_INVALID, "scan_dynamic must be 0 (chosen by the mesh), 1 (static turns), 2 (dynamic claims), 3 (planned: equal-cost intervals) or 4 (hybrid: turns + a claimed tail)");
         ctx->opt_scan_dynamic = value;
+    } else if (!strcmp(key, "narrow_fused")) {
+        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "narrow_fused must be 0 (narrow_phase_kernel tests the scan's survivors) or 1 (every scan wave tests its own at its end)");
+        ctx->opt_narrow_fused = value;
     } else if (!strcmp(key, "frame_batch")) {
         if (value < 1 || value > (int)kBatchMax) return fail(ctx, RTGL_ERR_INVALID, "frame_batch (consecutive frames traced in one set of launches) must be 1..16");
         ctx->opt_frame_batch = value;
@@ -2542,6 +2556,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "sort_min_rays")) *value = ctx->opt_sort_min_rays;
     else if (!strcmp(key, "scan_waves")) *value = ctx->opt_scan_waves;
     else if (!strcmp(key, "scan_dynamic")) *value = ctx->opt_scan_dynamic;
+    else if (!strcmp(key, "narrow_fused")) *value = ctx->opt_narrow_fused;
     else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
     else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
