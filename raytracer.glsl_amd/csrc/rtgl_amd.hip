@@ -25,6 +25,7 @@
 #include "rt_tonemap.hpp"
 #include "rt_error.hpp"
 #include "rt_node_walk.hpp"
+#include "rt_buffers.hpp"
 
 #pragma clang fp contract(off)
 
@@ -180,6 +181,10 @@ struct PartWorker {
     rtgl_context *part = nullptr;
 };
 
+// the ledger's allocator and deallocator: the only two calls of their kind in this file
+static int device_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+static int device_free(void *p) { return (int)hipFree(p); }
+
 struct rtgl_context {
     int device = 0;
     int width = 0, height = 0;
@@ -197,7 +202,8 @@ struct rtgl_context {
     std::vector<uint8_t> h_meshes, h_nodes, h_vertices;
     uint32_t n_meshes = 0, n_nodes = 0, n_vec4 = 0;
 
-    // device buffers
+    // device buffers: every one of them is allocated, grown and freed through `buffers` (rt_buffers.hpp), keyed by its pointer field here
+    rt_buffers::Ledger buffers{device_alloc, device_free};
     SphereRec *d_spheres = nullptr; uint32_t n_spheres = 0;
     MaterialRec *d_materials = nullptr; uint32_t n_materials = 0;
     float4 *d_vertices = nullptr;
@@ -267,6 +273,7 @@ struct rtgl_context {
     // ... and, for the ids plane only, per triangle visit its mesh and its triangle (uploaded while that plane is enabled)
     std::vector<uint32_t> h_visit_mesh, h_visit_tri;
     uint32_t *d_visit_mesh = nullptr, *d_visit_tri = nullptr; bool visit_ids_dirty = true;
+    uint32_t *d_visit_scratch = nullptr;     // rebuild_triangles: the visit list while the upload-time kernels run; freed at its end (after a failed rebuild: by the next one)
     // rtgl_denoise: two RGBA32F buffers the passes alternate between and the buffer the last pass writes, each local_rows x width records,
     // allocated by the first call that needs them; has_denoised: a call has succeeded, so the read-out calls have something to return
     float4 *d_dn_scratch[2] = {nullptr, nullptr}, *d_denoised = nullptr; bool has_denoised = false;
@@ -305,12 +312,35 @@ static int fail(rtgl_context *ctx, int code, const std::string &msg)
 #define HIPCHK(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return fail(ctx, RTGL_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
+#define RCCHK(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// typed fronts of the context's ledger; a failure is the usual RTGL_ERR_DEVICE
+static int buf_rc(rtgl_context *ctx, const char *what, int e) { return e ? fail(ctx, RTGL_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString((hipError_t)e)) : RTGL_OK; }
+template <typename T> static int buf_alloc(rtgl_context *ctx, T *&p, size_t bytes) { return buf_rc(ctx, "device allocation", ctx->buffers.allocate((void **)&p, bytes)); }
+template <typename T> static int buf_ensure(rtgl_context *ctx, T *&p, size_t bytes) { return buf_rc(ctx, "device allocation", ctx->buffers.ensure((void **)&p, bytes)); }
+template <typename T, typename C> static int buf_grow(rtgl_context *ctx, T *&p, C &capacity, size_t need, size_t bytes) { return buf_rc(ctx, "device allocation", ctx->buffers.grow((void **)&p, capacity, (C)need, bytes)); }
+template <typename... T> static int buf_release(rtgl_context *ctx, T *&...p)      // stops at the first free that fails
+{
+    int e = 0;
+    ((e = e ? e : ctx->buffers.release((void **)&p)), ...);
+    return buf_rc(ctx, "device free", e);
+}
+
+static size_t local_px(const rtgl_context *ctx) { return (size_t)std::max(ctx->local_rows, 1) * ctx->width; }      // (a tile without rows still owns one)
+
+// the context's rows of a buffer of `px_bytes` bytes per pixel, on the host when this returns
+static int read_rows(rtgl_context *ctx, void *dst, const void *src, size_t px_bytes)
+{
+    HIPCHK(ctx, hipMemcpyAsync(dst, src, (size_t)ctx->local_rows * ctx->width * px_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
 template <typename T>
 static int realloc_upload(rtgl_context *ctx, T *&dptr, const void *src, size_t bytes)
 {
-    if (dptr) { HIPCHK(ctx, hipFree(dptr)); dptr = nullptr; }
-    if (bytes == 0) return RTGL_OK;
-    HIPCHK(ctx, hipMalloc((void **)&dptr, bytes));
+    if (bytes == 0) return buf_release(ctx, dptr);
+    RCCHK(buf_alloc(ctx, dptr, bytes));
     if (src) HIPCHK(ctx, hipMemcpyAsync(dptr, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // uploads are synchronous like glBufferData
     return RTGL_OK;
@@ -404,11 +434,11 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     register_ctx_stream(ctx, device, ctx->stream);
     CCHK(hipEventCreate(&ctx->ev0));
     CCHK(hipEventCreate(&ctx->ev1));
-    size_t img_bytes = (size_t)std::max(ctx->local_rows, 1) * width * sizeof(float4);
-    CCHK(hipMalloc((void **)&ctx->d_image_own, img_bytes));
+    size_t img_bytes = local_px(ctx) * sizeof(float4);
+    if (buf_alloc(ctx, ctx->d_image_own, img_bytes)) return bail(RTGL_ERR_DEVICE);
     CCHK(hipMemsetAsync(ctx->d_image_own, 0, img_bytes, ctx->stream));
     ctx->d_image = ctx->d_image_own;
-    CCHK(hipMalloc((void **)&ctx->d_counters, 64));
+    if (buf_alloc(ctx, ctx->d_counters, 64)) return bail(RTGL_ERR_DEVICE);
     CCHK(hipMemsetAsync(ctx->d_counters, 0, 64, ctx->stream));
     CCHK(hipStreamSynchronize(ctx->stream));
 #undef CCHK
@@ -483,15 +513,7 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
             }
     }
 #endif
-    void *ptrs[] = { ctx->d_spheres, ctx->d_materials, ctx->d_vertices, ctx->d_sphere_visits, ctx->d_edges, ctx->d_planes,
-                     ctx->d_env, ctx->d_image_own, ctx->d_rng, ctx->d_counters, ctx->d_u8, ctx->d_group_bounds, ctx->d_wave, ctx->d_counts, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order,
-                     ctx->d_dbg_log, ctx->d_cand, ctx->d_keep0, ctx->d_plan, ctx->d_stage, ctx->d_sort_hist, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_keep, ctx->d_items, ctx->d_sched, ctx->d_edges_s, ctx->d_planes_s, ctx->d_batch_rad,
-                     ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids, ctx->d_visit_mesh, ctx->d_visit_tri,
-                     ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance, ctx->d_dn_near,
-                     ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1],
-                     ctx->d_tm_moments[0], ctx->d_tm_moments[1], ctx->d_display, ctx->d_tone_state,
-                     ctx->d_err_snapshot, ctx->d_err_tiles, ctx->d_err_summary };
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    ctx->buffers.release_all();
     for (hipEvent_t e : ctx->kev) (void)hipEventDestroy(e);
     if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
     if (ctx->counts_ev) (void)hipEventDestroy(ctx->counts_ev);
@@ -800,8 +822,7 @@ static int rebuild_triangles(rtgl_context *ctx)
         for (uint64_t t = start; t < end; ++t) { visit_tri.push_back((uint32_t)t); visit_mesh.push_back(m); }
     }
     ctx->h_visit_tri = visit_tri; ctx->h_visit_mesh.swap(visit_mesh); ctx->visit_ids_dirty = true;      // (the ids plane's triangle ids)
-    if (ctx->d_edges) { HIPCHK(ctx, hipFree(ctx->d_edges)); ctx->d_edges = nullptr; }
-    if (ctx->d_planes) { HIPCHK(ctx, hipFree(ctx->d_planes)); ctx->d_planes = nullptr; }
+    RCCHK(buf_release(ctx, ctx->d_edges, ctx->d_planes));
     ctx->n_tri_visits = (uint32_t)visit_tri.size();
     ctx->scene_version++;
     {
@@ -814,27 +835,20 @@ static int rebuild_triangles(rtgl_context *ctx)
         for (int a = 0; a < 3; ++a) { ctx->mesh_lo[a] = lo[a] <= hi[a] ? lo[a] : 0.0f; ctx->mesh_hi[a] = lo[a] <= hi[a] ? hi[a] : 0.0f; if (lo[a] <= hi[a]) ctx->mesh_ext = std::max(ctx->mesh_ext, hi[a] - lo[a]); }
     }
     if (ctx->n_tri_visits) {
-        uint32_t *d_visit = nullptr;
-        HIPCHK(ctx, hipMalloc((void **)&d_visit, visit_tri.size() * 4));
-        HIPCHK(ctx, hipMemcpyAsync(d_visit, visit_tri.data(), visit_tri.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_edges, (size_t)ctx->n_tri_visits * sizeof(TriEdges)));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_planes, (size_t)ctx->n_tri_visits * sizeof(TriPlane)));
+        RCCHK(buf_alloc(ctx, ctx->d_visit_scratch, visit_tri.size() * 4));
+        uint32_t *const d_visit = ctx->d_visit_scratch;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_visit_scratch, visit_tri.data(), visit_tri.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        RCCHK(buf_alloc(ctx, ctx->d_edges, (size_t)ctx->n_tri_visits * sizeof(TriEdges)));
+        RCCHK(buf_alloc(ctx, ctx->d_planes, (size_t)ctx->n_tri_visits * sizeof(TriPlane)));
         dim3 grid((ctx->n_tri_visits + 255) / 256);
         hipLaunchKernelGGL(prepare_triangles_kernel, grid, dim3(256), 0, ctx->stream, ctx->d_vertices, d_visit, ctx->n_tri_visits, ctx->d_edges, ctx->d_planes);
         HIPCHK(ctx, hipGetLastError());
-        if (ctx->d_group_bounds) { HIPCHK(ctx, hipFree(ctx->d_group_bounds)); ctx->d_group_bounds = nullptr; }
         uint32_t n_groups = (ctx->n_tri_visits + kBoundGroup - 1) / kBoundGroup;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_group_bounds, (size_t)n_groups * sizeof(float2)));
+        RCCHK(buf_alloc(ctx, ctx->d_group_bounds, (size_t)n_groups * sizeof(float2)));
         hipLaunchKernelGGL(group_bounds_kernel, dim3(n_groups), dim3(64), 0, ctx->stream, ctx->d_edges, ctx->n_tri_visits, ctx->d_group_bounds);
         HIPCHK(ctx, hipGetLastError());
         // bf16 broad-phase data: local origins, bounds, A matrices (rt_mfma.hpp)
-        if (ctx->d_mf_groups) { HIPCHK(ctx, hipFree(ctx->d_mf_groups)); ctx->d_mf_groups = nullptr; }
-        if (ctx->d_mf_A) { HIPCHK(ctx, hipFree(ctx->d_mf_A)); ctx->d_mf_A = nullptr; }
-        if (ctx->d_mf_order) { HIPCHK(ctx, hipFree(ctx->d_mf_order)); ctx->d_mf_order = nullptr; }
-        if (ctx->d_mf_cull) { HIPCHK(ctx, hipFree(ctx->d_mf_cull)); ctx->d_mf_cull = nullptr; }
-        if (ctx->d_mf_cull_node) { HIPCHK(ctx, hipFree(ctx->d_mf_cull_node)); ctx->d_mf_cull_node = nullptr; }
-        if (ctx->d_edges_s) { HIPCHK(ctx, hipFree(ctx->d_edges_s)); ctx->d_edges_s = nullptr; }
-        if (ctx->d_planes_s) { HIPCHK(ctx, hipFree(ctx->d_planes_s)); ctx->d_planes_s = nullptr; }
+        RCCHK(buf_release(ctx, ctx->d_mf_groups, ctx->d_mf_A, ctx->d_mf_order, ctx->d_mf_cull, ctx->d_mf_cull_node, ctx->d_edges_s, ctx->d_planes_s));
         // quads sharing one local origin: 32 (= a chunk: one ray set-up per work item of the scan) unless the caller chose.  Smaller
         // groups have tighter bounds and fewer survivors (C4: 89 M per frame at 8 quads against 111 M at 32), but every group of a
         // chunk costs the scan a ray set-up and a pipeline fill of its own: 28.4 against 30.0 Mpaths/s
@@ -842,23 +856,23 @@ static int rebuild_triangles(rtgl_context *ctx)
         const uint32_t group_tris = ctx->mf_group_quads * kMfQuadTris;
         ctx->n_mf_groups = (ctx->n_tri_visits + group_tris - 1) / group_tris;
         const std::vector<uint32_t> order = kd_order(ctx, visit_tri, group_tris);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_order, order.size() * 4));
+        RCCHK(buf_alloc(ctx, ctx->d_mf_order, order.size() * 4));
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_mf_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_edges_s, (size_t)ctx->n_tri_visits * sizeof(TriEdges)));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_planes_s, (size_t)ctx->n_tri_visits * sizeof(TriPlane)));
+        RCCHK(buf_alloc(ctx, ctx->d_edges_s, (size_t)ctx->n_tri_visits * sizeof(TriEdges)));
+        RCCHK(buf_alloc(ctx, ctx->d_planes_s, (size_t)ctx->n_tri_visits * sizeof(TriPlane)));
         hipLaunchKernelGGL(gather_storage_order_kernel, dim3((ctx->n_tri_visits + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_edges, ctx->d_planes, ctx->d_mf_order,
                            ctx->n_tri_visits, ctx->d_edges_s, ctx->d_planes_s);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_groups, (size_t)ctx->n_mf_groups * sizeof(MfGroup)));
+        RCCHK(buf_alloc(ctx, ctx->d_mf_groups, (size_t)ctx->n_mf_groups * sizeof(MfGroup)));
         const size_t a_bytes = ((size_t)ctx->n_mf_groups * ctx->mf_group_quads + 1) * kMfQuadTiles * 64 * sizeof(uint4);   // two K panels per tile; + one zero quad
         if (a_bytes > 0xFFFF0000ull) return fail(ctx, RTGL_ERR_INVALID, "mesh too large for the 32-bit tile offsets of the matrix-core scan");
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_A, a_bytes));
+        RCCHK(buf_alloc(ctx, ctx->d_mf_A, a_bytes));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_mf_A, 0, a_bytes, ctx->stream));
         hipLaunchKernelGGL(prepare_mfma_kernel, dim3(ctx->n_mf_groups), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
                            ctx->d_mf_order, ctx->n_tri_visits, ctx->n_mf_groups, ctx->mf_group_quads, ctx->d_mf_groups, ctx->d_mf_A, getenv("RTGL_AMD_ROW_GAMMA") ? (float)atof(getenv("RTGL_AMD_ROW_GAMMA")) : 1.220703125e-4f);
         HIPCHK(ctx, hipGetLastError());
         // packet-culling records, one per tile of the storage order (all-zero records -- unusable -- behind the last one)
         const uint32_t n_tiles_all = ctx->n_mf_groups * ctx->mf_group_quads * (uint32_t)kMfQuadTiles, n_tiles_alloc = n_tiles_all + 128u;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_cull, (size_t)n_tiles_alloc * sizeof(MfCull)));
+        RCCHK(buf_alloc(ctx, ctx->d_mf_cull, (size_t)n_tiles_alloc * sizeof(MfCull)));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_mf_cull, 0, (size_t)n_tiles_alloc * sizeof(MfCull), ctx->stream));
         hipLaunchKernelGGL(prepare_cull_kernel, dim3(n_tiles_all), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
                            ctx->d_mf_order, ctx->n_tri_visits, n_tiles_all, (uint32_t)kMfTileTris, ctx->d_mf_cull);
@@ -867,13 +881,13 @@ static int rebuild_triangles(rtgl_context *ctx)
         ctx->cull_node_shift = cull_node_shift_option();
         if (ctx->cull_node_shift) {
             const uint32_t n_nodes_all = (n_tiles_all + (1u << ctx->cull_node_shift) - 1u) >> ctx->cull_node_shift;
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_mf_cull_node, (size_t)n_nodes_all * sizeof(MfCull)));
+            RCCHK(buf_alloc(ctx, ctx->d_mf_cull_node, (size_t)n_nodes_all * sizeof(MfCull)));
             hipLaunchKernelGGL(prepare_cull_kernel, dim3(n_nodes_all), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
                                ctx->d_mf_order, ctx->n_tri_visits, n_nodes_all, (uint32_t)kMfTileTris << ctx->cull_node_shift, ctx->d_mf_cull_node);
             HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipFree(d_visit));
+        RCCHK(buf_release(ctx, ctx->d_visit_scratch));
     } else ctx->n_mf_groups = 0;
     ctx->tris_dirty = false;
     return RTGL_OK;
@@ -936,50 +950,36 @@ static void set_bin_cells(rtgl_context *ctx)
 static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_bounce, bool multi_sample)
 {
     if (ctx->counts_capacity < max_bounce + 2) {
-        if (ctx->d_counts) { HIPCHK(ctx, hipFree(ctx->d_counts)); ctx->d_counts = nullptr; }
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_counts, counts_bytes(max_bounce + 2)));                          // u32 ray counts per bounce
+        ctx->counts_capacity = 0;                            // (non-zero only while BOTH buffers are live with that capacity)
+        RCCHK(buf_alloc(ctx, ctx->d_counts, counts_bytes(max_bounce + 2)));                                     // u32 ray counts per bounce
         if (ctx->h_counts) { HIPCHK(ctx, hipHostFree(ctx->h_counts)); ctx->h_counts = nullptr; }
         HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_counts, counts_bytes(max_bounce + 2), hipHostMallocDefault));
         if (!ctx->counts_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->counts_ev, hipEventDisableTiming));
         ctx->counts_capacity = max_bounce + 2; ctx->counts_pending = ctx->counts_valid = false; ctx->est_counts.clear();
     }
-    const size_t local_px = (size_t)std::max(ctx->local_rows, 1) * ctx->width;
     if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
         const uint32_t need_regions = solo_regions(ctx);
         // (a record = one (ray, 5-triangle mask); every queue entry of the scan makes four of them)
         if (!ctx->cand_region_target) ctx->cand_region_target = std::max<uint32_t>(4096u, (uint32_t)std::min<uint64_t>(((uint64_t)n0 + need_regions - 1) / need_regions, 0xFFFFFFF0u));
         if (!ctx->d_cand || need_regions > ctx->cand_regions || ctx->cand_region_target > ctx->cand_region_pairs) {
-            if (ctx->d_cand) { HIPCHK(ctx, hipFree(ctx->d_cand)); ctx->d_cand = nullptr; }                  // (hipFree waits for the frames in flight)
             ctx->cand_regions = need_regions; ctx->cand_region_pairs = ctx->cand_region_target;
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_cand, ((size_t)need_regions * ctx->cand_region_pairs) * sizeof(uint2) + (size_t)need_regions * sizeof(uint32_t) + 256));
+            RCCHK(buf_alloc(ctx, ctx->d_cand, ((size_t)need_regions * ctx->cand_region_pairs) * sizeof(uint2) + (size_t)need_regions * sizeof(uint32_t) + 256));      // (the free waits for the frames in flight)
         }
         {                                                    // packet culling: one bit per (granule of 128 rays, tile); + 16 granules read ahead of the last one
             const uint32_t real_quads = std::min(ctx->n_mf_groups * ctx->mf_group_quads, (ctx->n_tri_visits + (uint32_t)kMfQuadTris - 1) / (uint32_t)kMfQuadTris);
             ctx->wb.keep_words = std::max(1u, (real_quads * (uint32_t)kMfQuadTiles + 31u) / 32u);
             const size_t need = ((size_t)n0 / 128 + 16) * ctx->wb.keep_words;
-            if (ctx->keep_capacity < need) {
-                if (ctx->d_keep) { HIPCHK(ctx, hipFree(ctx->d_keep)); ctx->d_keep = nullptr; }
-                HIPCHK(ctx, hipMalloc((void **)&ctx->d_keep, need * sizeof(uint32_t)));
-                ctx->keep_capacity = need;
-            }
+            RCCHK(buf_grow(ctx, ctx->d_keep, ctx->keep_capacity, need, need * sizeof(uint32_t)));
         }
         ctx->wb.keep = ctx->d_keep;
         {                                                    // work distribution of the scan: one counter per (bounce, chunk); a launch has at most max(CUs, chunks) chunks
             ctx->wb.sched_stride = std::max<uint32_t>((uint32_t)ctx->n_cus, solo_chunks(ctx));
             const size_t need = (size_t)(max_bounce + 2) * ctx->wb.sched_stride;
-            if (ctx->sched_capacity < need) {
-                if (ctx->d_sched) { HIPCHK(ctx, hipFree(ctx->d_sched)); ctx->d_sched = nullptr; }
-                HIPCHK(ctx, hipMalloc((void **)&ctx->d_sched, need * sizeof(uint32_t)));
-                ctx->sched_capacity = need;
-            }
+            RCCHK(buf_grow(ctx, ctx->d_sched, ctx->sched_capacity, need, need * sizeof(uint32_t)));
             ctx->wb.sched = ctx->d_sched;
         }
         if (ctx->opt_cull == 3) {                            // ray binning: staging queue (64-byte records of a, b, c, rng, pixel 4 B), key + rank 8 B, source slot 4 B, and the bin counters
-            if (ctx->stage_capacity < n0) {
-                if (ctx->d_stage) { HIPCHK(ctx, hipFree(ctx->d_stage)); ctx->d_stage = nullptr; }
-                HIPCHK(ctx, hipMalloc(&ctx->d_stage, (size_t)n0 * 80 + 1024));
-                ctx->stage_capacity = n0;
-            }
+            RCCHK(buf_grow(ctx, ctx->d_stage, ctx->stage_capacity, n0, (size_t)n0 * 80 + 1024));
             uint8_t *p = (uint8_t *)ctx->d_stage;
             const size_t cap = ctx->stage_capacity;
             ctx->wb.stage = (float4 *)p; p += cap * 64; ctx->wb.sort_kr = (uint2 *)p; p += cap * 8; ctx->wb.stage_pixel = (uint32_t *)p; p += cap * 4;
@@ -991,12 +991,9 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
             if (const char *e = getenv("RTGL_AMD_SORT_DB")) { const int v = atoi(e); if (v >= 2 && v <= 6) ctx->wb.sort_db = (uint32_t)v; }      // (tuning: the bins stay as many)
             ctx->wb.sort_bits = 8u + 3u * ctx->wb.sort_ob;
             ctx->wb.sort_T = ctx->wb.sort_bits - 1u - 2u * ctx->wb.sort_db;
-            if (ctx->sort_bits_alloc < ctx->wb.sort_bits) {
-                if (ctx->d_sort_hist) { HIPCHK(ctx, hipFree(ctx->d_sort_hist)); ctx->d_sort_hist = nullptr; }
-                const size_t bins = (size_t)1 << ctx->wb.sort_bits;
-                HIPCHK(ctx, hipMalloc((void **)&ctx->d_sort_hist, 2 * (bins + bins / kSortSeg) * sizeof(uint32_t)));
-                ctx->sort_bits_alloc = ctx->wb.sort_bits; ctx->sort_sets_clean = false;
-            }
+            if (ctx->sort_bits_alloc < ctx->wb.sort_bits) ctx->sort_sets_clean = false;
+            const size_t bins = (size_t)1 << ctx->wb.sort_bits;
+            RCCHK(buf_grow(ctx, ctx->d_sort_hist, ctx->sort_bits_alloc, ctx->wb.sort_bits, 2 * (bins + bins / kSortSeg) * sizeof(uint32_t)));
             ctx->wb.sort_hist = ctx->d_sort_hist; ctx->wb.sort_hist_other = ctx->d_sort_hist;      // (set per binned bounce: launch_wavefront)
             set_bin_cells(ctx);
         }
@@ -1009,12 +1006,12 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
         // diagnostics: RTGL_DEBUG_CAND_CAP=n pretends a wave's region holds n pairs only, so that the in-place fallback of the scan runs
         if (const char *cc = getenv("RTGL_DEBUG_CAND_CAP")) { ctx->wb.cand_region = std::min<uint32_t>(ctx->wb.cand_region, (uint32_t)atoi(cc)); ctx->cand_fixed = true; }
     }
-    if (ctx->wave_capacity < n0 || (multi_sample && !ctx->wave_multi)) {
-        if (ctx->d_wave) { HIPCHK(ctx, hipFree(ctx->d_wave)); ctx->d_wave = nullptr; }
+    if (multi_sample && !ctx->wave_multi) ctx->wave_capacity = 0;      // (the buffer in place lacks the per-pixel state)
+    if (ctx->wave_capacity < n0) {
         // per queue: 4 x 16 B + 4 B per ray; per-pixel state for u_samples > 1: 4 x 16 B
-        size_t q_bytes = (size_t)n0 * (68 + 8), bytes = 2 * q_bytes + 1024 + (multi_sample ? local_px * 64 : 0);
-        HIPCHK(ctx, hipMalloc(&ctx->d_wave, bytes));
-        ctx->wave_capacity = n0; ctx->wave_multi = multi_sample;
+        const size_t px = local_px(ctx), q_bytes = (size_t)n0 * (68 + 8), bytes = 2 * q_bytes + 1024 + (multi_sample ? px * 64 : 0);
+        RCCHK(buf_grow(ctx, ctx->d_wave, ctx->wave_capacity, n0, bytes));
+        ctx->wave_multi = multi_sample;
         uint8_t *p = (uint8_t *)ctx->d_wave;
         for (int q = 0; q < 2; ++q) {
             ctx->wb.q[q].a = (float4 *)p; p += (size_t)n0 * 16;
@@ -1026,10 +1023,10 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
         for (int q = 0; q < 2; ++q) { ctx->wb.q[q].pixel = (uint32_t *)p; p += (size_t)n0 * 4; }
         p = (uint8_t *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
         if (multi_sample) {
-            ctx->wb.sums = (float4 *)p; p += local_px * 16;
-            ctx->wb.cam_a = (float4 *)p; p += local_px * 16;
-            ctx->wb.cam_b = (float4 *)p; p += local_px * 16;
-            ctx->wb.pix_rng = (uint4 *)p; p += local_px * 16;
+            ctx->wb.sums = (float4 *)p; p += px * 16;
+            ctx->wb.cam_a = (float4 *)p; p += px * 16;
+            ctx->wb.cam_b = (float4 *)p; p += px * 16;
+            ctx->wb.pix_rng = (uint4 *)p; p += px * 16;
         } else ctx->wb.sums = ctx->wb.cam_a = ctx->wb.cam_b = nullptr, ctx->wb.pix_rng = nullptr;
     }
     ctx->wb.counts = ctx->d_counts;
@@ -1159,7 +1156,7 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
     if (dist == 0 || dist == 3) blocks = std::max(1u, std::min((est_gran + waves - 1u) / waves, std::max(1u, (uint32_t)ctx->n_cus / chunks))) * chunks;
     const size_t lds = std::max<size_t>(((size_t)chunk_quads * kMfQuadTiles + 4) * 1024, 96 * 1024);   // + the four rows read two trips ahead behind the last tile; > half of the CU's LDS with the static queue: one block per CU
 #ifdef RT_SOLO_STAMPS
-    if (!ctx->d_dbg_log) { HIPCHK(ctx, hipMalloc((void **)&ctx->d_dbg_log, (size_t)(2 + (2u << 22)) * 4)); HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg_log, 0, 2048 * 8 + 16 * 64 * 2 * 16 * 8, ctx->stream)); }
+    if (!ctx->d_dbg_log) { RCCHK(buf_alloc(ctx, ctx->d_dbg_log, (size_t)(2 + (2u << 22)) * 4)); HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg_log, 0, 2048 * 8 + 16 * 64 * 2 * 16 * 8, ctx->stream)); }
 #endif
     MfView mf{ctx->d_mf_groups, ctx->n_mf_groups, gq, n_quads, ctx->d_mf_A, ctx->d_dbg_log, ctx->d_mf_cull, ctx->d_edges_s, ctx->d_planes_s, ctx->d_mf_order};
     if (!ctx->solo_attr_set) {
@@ -1188,11 +1185,8 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
         bool have_bits = false;
         if (bounce == 0 && cam && camera_keep_widening(*cam, &ro_add, &sigma_add) && !getenv("RTGL_AMD_NO_CAMERA_KEEP")) {
             const size_t need = ((size_t)n0 / 128 + 16) * ctx->wb.keep_words;
-            if (ctx->keep0_capacity < need) {
-                if (ctx->d_keep0) { HIPCHK(ctx, hipFree(ctx->d_keep0)); ctx->d_keep0 = nullptr; }
-                HIPCHK(ctx, hipMalloc((void **)&ctx->d_keep0, need * sizeof(uint32_t)));
-                ctx->keep0_capacity = need; ctx->keep0_valid = false;
-            }
+            if (ctx->keep0_capacity < need) ctx->keep0_valid = false;
+            RCCHK(buf_grow(ctx, ctx->d_keep0, ctx->keep0_capacity, need, need * sizeof(uint32_t)));
             have_bits = ctx->keep0_valid && ctx->keep0_n0 == n0 && ctx->keep0_words == ctx->wb.keep_words && ctx->keep0_scene == ctx->scene_version && same_camera(ctx->keep0_params, *cam);
             ctx->wb.keep = ctx->d_keep0;
             if (!have_bits) { ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_params = *cam; }
@@ -1207,11 +1201,7 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
             const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
             const size_t off_tot = (((size_t)chunks * stride * sizeof(uint32_t)) + 255) & ~(size_t)255, off_base = (off_tot + (size_t)chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
             const size_t need = off_base + ((size_t)chunks + 1) * sizeof(unsigned long long);
-            if (ctx->plan_capacity < need) {
-                if (ctx->d_plan) { HIPCHK(ctx, hipFree(ctx->d_plan)); ctx->d_plan = nullptr; }
-                HIPCHK(ctx, hipMalloc(&ctx->d_plan, need));
-                ctx->plan_capacity = need;
-            }
+            RCCHK(buf_grow(ctx, ctx->d_plan, ctx->plan_capacity, need, need));
             ctx->wb.plan_prefix = reinterpret_cast<uint32_t *>(ctx->d_plan); ctx->wb.plan_stride = stride;
             ctx->wb.plan_total = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + off_tot);
             ctx->wb.plan_base = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + off_base);
@@ -1223,11 +1213,7 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
         // work items of the culled launch: [one count per chunk][chunks x (granules of the whole image) entries]
         const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
         const size_t head = ((size_t)ctx->wb.sched_stride * sizeof(uint32_t) + 255) & ~(size_t)255, need = head + (size_t)chunks * stride * sizeof(uint32_t);
-        if (ctx->items_capacity < need) {
-            if (ctx->d_items) { HIPCHK(ctx, hipFree(ctx->d_items)); ctx->d_items = nullptr; }
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_items, need));
-            ctx->items_capacity = need;
-        }
+        RCCHK(buf_grow(ctx, ctx->d_items, ctx->items_capacity, need, need));
         ctx->wb.item_counts = reinterpret_cast<uint32_t *>(ctx->d_items);
         ctx->wb.items = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_items) + head);
         ctx->wb.items_stride = stride;
@@ -1446,8 +1432,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     }
     if (ctx->visits_dirty) { int rc = rebuild_sphere_visits(ctx); if (rc) return rc; }
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
-    if (ctx->opt_rng_state && !ctx->d_rng)
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_rng, (size_t)std::max(ctx->local_rows, 1) * ctx->width * sizeof(uint4)));
+    if (ctx->opt_rng_state) RCCHK(buf_ensure(ctx, ctx->d_rng, local_px(ctx) * sizeof(uint4)));
     if ((ctx->opt_aov & RTGL_AOV_IDS) && ctx->visit_ids_dirty) {
         const size_t bytes = ctx->h_visit_tri.size() * sizeof(uint32_t);
         int rc = realloc_upload(ctx, ctx->d_visit_mesh, ctx->h_visit_mesh.data(), bytes);
@@ -1475,7 +1460,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     int local_disp_rows = 0;
     for (int lr = 0; lr < ctx->local_rows; ++lr) if (rtgl_local_row_to_global(ctx, lr) < im.disp_h) local_disp_rows = lr + 1;
     const uint32_t n0_frame = (uint32_t)im.disp_w * (uint32_t)local_disp_rows;
-    if ((uint64_t)n0_frame * B > 0xFFFFFFF0ull || (size_t)std::max(ctx->local_rows, 1) * ctx->width > (size_t)kBatchPixelMask) return fail(ctx, RTGL_ERR_INVALID, "frame_batch: the batch does not fit 32-bit ray slots");
+    if ((uint64_t)n0_frame * B > 0xFFFFFFF0ull || local_px(ctx) > (size_t)kBatchPixelMask) return fail(ctx, RTGL_ERR_INVALID, "frame_batch: the batch does not fit 32-bit ray slots");
     const uint32_t n0 = n0_frame * B;            // rays entering bounce 0: all frames of the batch
     uint4 *rng_out = ctx->opt_rng_state ? ctx->d_rng : nullptr;
     // first-hit planes: frames are rendered one by one while they are on (B == 1); the running mean restarts with a reset frame
@@ -1498,13 +1483,9 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if (use_wavefront && n0 > 0) { int rc = ensure_wave_buffers(ctx, n0, P.max_bounce, P.samples > 1); if (rc) return rc; }
     ctx->wb.batch_rad = nullptr; ctx->wb.batch_px = 0;
     if (B > 1) {
-        const size_t local_px = (size_t)std::max(ctx->local_rows, 1) * ctx->width, need = local_px * B;
-        if (ctx->batch_capacity < need) {
-            if (ctx->d_batch_rad) { HIPCHK(ctx, hipFree(ctx->d_batch_rad)); ctx->d_batch_rad = nullptr; }
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_batch_rad, need * sizeof(float4)));
-            ctx->batch_capacity = need;
-        }
-        ctx->wb.batch_rad = ctx->d_batch_rad; ctx->wb.batch_px = (uint32_t)local_px;
+        const size_t need = local_px(ctx) * B;
+        RCCHK(buf_grow(ctx, ctx->d_batch_rad, ctx->batch_capacity, need, need * sizeof(float4)));
+        ctx->wb.batch_rad = ctx->d_batch_rad; ctx->wb.batch_px = (uint32_t)local_px(ctx);
     }
     ctx->last_batch_frames = B;
     HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1615,9 +1596,7 @@ extern "C" int rtgl_read_image_f32(rtgl_context *ctx, float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->parts.empty()) { const int rc = multi_gather(ctx); if (rc) return rc; }
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_image, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_image, 16);
 }
 
 extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
@@ -1629,7 +1608,7 @@ extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
         ctx->gathered = false;
         std::vector<float> local;
         for (rtgl_context *part : ctx->parts) {
-            local.resize((size_t)std::max(part->local_rows, 1) * ctx->width * 4);
+            local.resize(local_px(part) * 4);
             for (int lr = 0; lr < part->local_rows; ++lr)
                 memcpy(local.data() + (size_t)lr * ctx->width * 4, rgba + (size_t)rtgl_local_row_to_global(part, lr) * ctx->width * 4, (size_t)ctx->width * 16);
             const int rc = rtgl_write_image_f32(part, local.data());
@@ -1659,13 +1638,11 @@ extern "C" int rtgl_read_image_u8(rtgl_context *ctx, uint8_t *rgba, int flip)
     if (!ctx->parts.empty()) { const int rc = multi_gather(ctx); if (rc) return rc; }
     size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return RTGL_OK;
-    if (!ctx->d_u8) HIPCHK(ctx, hipMalloc((void **)&ctx->d_u8, n * 4));
+    RCCHK(buf_ensure(ctx, ctx->d_u8, n * 4));
     hipLaunchKernelGGL(image_to_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        ctx->d_image, ctx->d_u8, ctx->width, ctx->local_rows, flip);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_u8, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_u8, 4);
 }
 
 extern "C" int rtgl_local_rows(const rtgl_context *ctx) { return ctx ? ctx->local_rows : RTGL_ERR_INVALID; }
@@ -1741,7 +1718,7 @@ extern "C" int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw)
     if (!ctx->parts.empty()) {                          // rows from their owners, global row order
         std::vector<uint32_t> local;
         for (rtgl_context *part : ctx->parts) {
-            local.resize((size_t)std::max(part->local_rows, 1) * ctx->width * 4);
+            local.resize(local_px(part) * 4);
             const int rc = rtgl_read_rng_state(part, local.data());
             if (rc) return fail(ctx, rc, part->error);
             for (int lr = 0; lr < part->local_rows; ++lr)
@@ -1750,9 +1727,7 @@ extern "C" int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw)
         return RTGL_OK;
     }
     if (!ctx->opt_rng_state || !ctx->d_rng) return fail(ctx, RTGL_ERR_STATE, "option rng_state was not enabled before rendering");
-    HIPCHK(ctx, hipMemcpyAsync(xyzw, ctx->d_rng, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, xyzw, ctx->d_rng, 16);
 }
 
 // ---- first-hit planes (option "aov") ----------------------------------------------------------------
@@ -1773,21 +1748,17 @@ static void *aov_plane(const rtgl_context *ctx, int idx) { return idx == 3 ? (vo
 static int set_aov(rtgl_context *ctx, int mask)
 {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // frames in flight may still write the old planes
-    for (int k = 0; k < 3; ++k) if (ctx->d_aov[k]) { HIPCHK(ctx, hipFree(ctx->d_aov[k])); ctx->d_aov[k] = nullptr; }
-    if (ctx->d_aov_ids) { HIPCHK(ctx, hipFree(ctx->d_aov_ids)); ctx->d_aov_ids = nullptr; }
+    RCCHK(buf_release(ctx, ctx->d_aov[0], ctx->d_aov[1], ctx->d_aov[2], ctx->d_aov_ids));
     if (!(mask & RTGL_AOV_IDS)) {
-        if (ctx->d_visit_mesh) { HIPCHK(ctx, hipFree(ctx->d_visit_mesh)); ctx->d_visit_mesh = nullptr; }
-        if (ctx->d_visit_tri) { HIPCHK(ctx, hipFree(ctx->d_visit_tri)); ctx->d_visit_tri = nullptr; }
+        RCCHK(buf_release(ctx, ctx->d_visit_mesh, ctx->d_visit_tri));
         ctx->visit_ids_dirty = true;
     }
     ctx->opt_aov = 0;
-    const size_t bytes = (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
+    const size_t bytes = local_px(ctx) * 16;
     for (int k = 0; k < 4; ++k) {
         if (!(mask & (1 << k))) continue;
-        void *p = nullptr;
-        HIPCHK(ctx, hipMalloc(&p, bytes));
-        if (k == 3) ctx->d_aov_ids = (uint4 *)p; else ctx->d_aov[k] = (float4 *)p;
-        HIPCHK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+        RCCHK(k == 3 ? buf_alloc(ctx, ctx->d_aov_ids, bytes) : buf_alloc(ctx, ctx->d_aov[k], bytes));
+        HIPCHK(ctx, hipMemsetAsync(aov_plane(ctx, k), 0, bytes, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->opt_aov = mask; ctx->aov_restart = true;
@@ -1804,7 +1775,7 @@ extern "C" int rtgl_read_aov(rtgl_context *ctx, int plane, void *out)
     if (!ctx->parts.empty()) {                          // rows from their owners, global row order
         std::vector<uint8_t> local;
         for (rtgl_context *part : ctx->parts) {
-            local.resize((size_t)std::max(part->local_rows, 1) * row_bytes);
+            local.resize(local_px(part) * 16);
             const int rc = rtgl_read_aov(part, plane, local.data());
             if (rc) return fail(ctx, rc, part->error);
             for (int lr = 0; lr < part->local_rows; ++lr)
@@ -1814,9 +1785,7 @@ extern "C" int rtgl_read_aov(rtgl_context *ctx, int plane, void *out)
     }
     const void *src = aov_plane(ctx, idx);
     if (!src) return fail(ctx, RTGL_ERR_STATE, "this plane is not enabled (option \"aov\")");
-    HIPCHK(ctx, hipMemcpyAsync(out, src, (size_t)ctx->local_rows * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, out, src, 16);
 }
 
 extern "C" void *rtgl_device_aov(rtgl_context *ctx, int plane)
@@ -1879,8 +1848,8 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
     const float4 *input = denoise_input(ctx);
     if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
     // pass k of K reads the image (k = 0) or the buffer pass k - 1 wrote, and writes the denoised buffer (k = K - 1) or scratch k & 1
-    if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
-    for (uint32_t k = 0; k < 2u && k + 1u < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_denoised, n * 16));
+    for (uint32_t k = 0; k < 2u && k + 1u < P.passes; ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], n * 16));
     AtrousArgs a{};
     a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
     a.width = ctx->width; a.height = ctx->local_rows;
@@ -1916,9 +1885,7 @@ extern "C" int rtgl_read_denoised_f32(rtgl_context *ctx, float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->has_denoised) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoised_f32: no rtgl_denoise call has succeeded on this context");
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_denoised, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_denoised, 16);
 }
 
 extern "C" void *rtgl_device_denoised(rtgl_context *ctx)
@@ -1980,10 +1947,10 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     }
     // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer); pass k of K reads scratch k & 1 and writes scratch (k + 1) & 1
     // or, as the last, the denoised buffer
-    if (!ctx->d_denoised) HIPCHK(ctx, hipMalloc((void **)&ctx->d_denoised, n * 16));
-    if (!ctx->d_dn_variance) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_variance, n * 16));
-    if (!ctx->d_dn_near) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_near, n * 4));
-    for (uint32_t k = 0; k < 2u && k < P.passes; ++k) if (!ctx->d_dn_scratch[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dn_scratch[k], n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_denoised, n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_variance, n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_near, n * 4));
+    for (uint32_t k = 0; k < 2u && k < P.passes; ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], n * 16));
     GuidedArgs a{};
     a.image = input; a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
     a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
@@ -2020,9 +1987,7 @@ extern "C" int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->has_dn_variance) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoise_variance_f32: no rtgl_denoise_guided call has succeeded on this context");
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_dn_variance, (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_dn_variance, 16);
 }
 
 extern "C" void *rtgl_device_denoise_variance(rtgl_context *ctx)
@@ -2105,10 +2070,10 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: this context holds no pixels");
     const bool with_normal = (ctx->opt_aov & RTGL_AOV_NORMAL) != 0;      // the normal plane is copied whenever it is on, tested or not
     for (int k = 0; k < 2; ++k) {
-        if (!ctx->d_tm_hist[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_hist[k], n * 16));
-        if (!ctx->d_tm_position[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_position[k], n * 16));
-        if (with_normal && !ctx->d_tm_normal[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_normal[k], n * 16));
-        if (moments && !ctx->d_tm_moments[k]) HIPCHK(ctx, hipMalloc((void **)&ctx->d_tm_moments[k], n * 16));
+        RCCHK(buf_ensure(ctx, ctx->d_tm_hist[k], n * 16));
+        RCCHK(buf_ensure(ctx, ctx->d_tm_position[k], n * 16));
+        if (with_normal) RCCHK(buf_ensure(ctx, ctx->d_tm_normal[k], n * 16));
+        if (moments) RCCHK(buf_ensure(ctx, ctx->d_tm_moments[k], n * 16));
     }
     const TemporalCamera cam = temporal_camera(ctx->params, ctx->width, ctx->height);
     const bool history = ctx->tm_valid && !(use_n && !ctx->tm_has_normal);
@@ -2150,9 +2115,7 @@ extern "C" int rtgl_read_temporal_f32(rtgl_context *ctx, float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_f32: no rtgl_temporal_accumulate call has succeeded on this context");
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_tm_hist[ctx->tm_cur], (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_tm_hist[ctx->tm_cur], 16);
 }
 
 extern "C" void *rtgl_device_temporal(rtgl_context *ctx)
@@ -2167,9 +2130,7 @@ extern "C" int rtgl_read_temporal_moments_f32(rtgl_context *ctx, float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_moments_f32: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")");
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_tm_moments[ctx->tm_cur], (size_t)ctx->local_rows * ctx->width * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return RTGL_OK;
+    return read_rows(ctx, rgba, ctx->d_tm_moments[ctx->tm_cur], 16);
 }
 
 extern "C" void *rtgl_device_temporal_moments(rtgl_context *ctx)
@@ -2274,9 +2235,9 @@ extern "C" int rtgl_tonemap(rtgl_context *ctx, const rtgl_tonemap_params *params
     }
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: this context holds no pixels");
-    if (!ctx->d_display) HIPCHK(ctx, hipMalloc((void **)&ctx->d_display, n * 4));
+    RCCHK(buf_ensure(ctx, ctx->d_display, n * 4));
     if (!ctx->d_tone_state) {
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tone_state, kToneStateWords * 4));
+        RCCHK(buf_alloc(ctx, ctx->d_tone_state, kToneStateWords * 4));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_tone_state, 0, kToneStateWords * 4, ctx->stream));      // both sets start clean; from here on the solve keeps them so
     }
     const bool automatic = (P.flags & RTGL_TONEMAP_AUTO_EXPOSURE) != 0;
@@ -2318,14 +2279,9 @@ extern "C" int rtgl_read_display_u8(rtgl_context *ctx, uint8_t *rgba, int flip)
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     if (!ctx->has_display) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_display_u8: no rtgl_tonemap call has succeeded on this context");
     const size_t row = (size_t)ctx->width * 4, rows = (size_t)ctx->local_rows;
-    if (!flip) {
-        HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_display, rows * row, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return RTGL_OK;
-    }
+    if (!flip) return read_rows(ctx, rgba, ctx->d_display, 4);
     std::vector<uint8_t> tmp(rows * row);                 // the rows are turned over on the host: the device buffer keeps the image's order
-    HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->d_display, rows * row, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    RCCHK(read_rows(ctx, tmp.data(), ctx->d_display, 4));
     for (size_t y = 0; y < rows; ++y) memcpy(rgba + (rows - 1 - y) * row, tmp.data() + y * row, row);
     return RTGL_OK;
 }
@@ -2390,9 +2346,9 @@ extern "C" int rtgl_error_estimate(rtgl_context *ctx, const rtgl_error_params *p
     const int fw = ctx->width / 8 * 8, fh = ctx->height / 8 * 8;
     if ((uint64_t)fw * (uint64_t)fh > 0xFFFFFFFFull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: the footprint does not fit 32-bit counts");
     const unsigned tx = (unsigned)((ctx->width + kErrTile - 1) / kErrTile), ty = (unsigned)((ctx->height + kErrTile - 1) / kErrTile);
-    if (!ctx->d_err_tiles) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_tiles, (size_t)tx * ty * sizeof(uint4)));
-    if (!ctx->d_err_summary) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_summary, kErrSummaryWords * 4));
-    if (!ctx->d_err_snapshot) HIPCHK(ctx, hipMalloc((void **)&ctx->d_err_snapshot, (size_t)ctx->height * ctx->width * sizeof(float)));
+    RCCHK(buf_ensure(ctx, ctx->d_err_tiles, (size_t)tx * ty * sizeof(uint4)));
+    RCCHK(buf_ensure(ctx, ctx->d_err_summary, kErrSummaryWords * 4));
+    RCCHK(buf_ensure(ctx, ctx->d_err_snapshot, (size_t)ctx->height * ctx->width * sizeof(float)));
     // a snapshot of an earlier moment of THIS accumulation, counted the same way
     const bool usable = ctx->err_snap_epoch == ctx->err_epoch && fn > (int64_t)ctx->err_fm && P.first_frames == ctx->err_first;
     const bool keep = usable && (P.flags & RTGL_ERROR_KEEP_SNAPSHOT);
@@ -2566,23 +2522,7 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "counters")) *value = ctx->opt_counters;
     else if (!strcmp(key, "kernel_timing")) *value = ctx->opt_kernel_timing;
     else if (!strcmp(key, "cand_region_pairs")) *value = (int)ctx->cand_region_pairs;      // kernel 4: current capacity of one wave's candidate region
-    else if (!strcmp(key, "device_mbytes")) {                                              // device memory held by this context (MiB, rounded up)
-        size_t b = (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
-        b += (size_t)ctx->wave_capacity * (68 + 8) * 2 + (ctx->wave_multi ? (size_t)std::max(ctx->local_rows, 1) * ctx->width * 64 : 0);
-        b += ((size_t)ctx->cand_regions * ctx->cand_region_pairs) * 8 + (size_t)ctx->cand_regions * 4;
-        b += (size_t)ctx->n_tri_visits * (sizeof(TriEdges) + sizeof(TriPlane) + 4 + 112) + (size_t)ctx->n_vec4 * 16 + (size_t)ctx->env_faces * ctx->env_w * ctx->env_h * ctx->env_c;
-        if (ctx->d_rng) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
-        b += ctx->batch_capacity * 16;
-        for (int k = 0; k < 4; ++k) if (ctx->opt_aov & (1 << k)) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
-        if (ctx->d_visit_tri) b += ctx->h_visit_tri.size() * 8;
-        for (const float4 *buf : { ctx->d_dn_scratch[0], ctx->d_dn_scratch[1], ctx->d_denoised, ctx->d_dn_variance }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
-        if (ctx->d_dn_near) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
-        for (const float4 *buf : { ctx->d_tm_hist[0], ctx->d_tm_hist[1], ctx->d_tm_normal[0], ctx->d_tm_normal[1], ctx->d_tm_position[0], ctx->d_tm_position[1], ctx->d_tm_moments[0], ctx->d_tm_moments[1] }) if (buf) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 16;
-        if (ctx->d_display) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4;
-        if (ctx->d_err_snapshot) b += (size_t)std::max(ctx->local_rows, 1) * ctx->width * 4 + (size_t)((ctx->width + 15) / 16) * ((ctx->height + 15) / 16) * 16;
-        b += ctx->stage_capacity * 76 + (ctx->sort_bits_alloc ? ((size_t)8 << ctx->sort_bits_alloc) : 0);
-        *value = (int)((b + (1u << 20) - 1) >> 20);
-    }
+    else if (!strcmp(key, "device_mbytes")) *value = (int)((ctx->buffers.total_bytes() + (1u << 20) - 1) >> 20);      // device memory held by this context: the ledger's sum (MiB, rounded up)
     else return fail(ctx, RTGL_ERR_INVALID, std::string("unknown option ") + key);
     return RTGL_OK;
 }
