@@ -26,6 +26,7 @@
 #include "rt_error.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_buffers.hpp"
+#include "rt_scan_launch.hpp"
 
 #pragma clang fp contract(off)
 
@@ -453,7 +454,7 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     return RTGL_OK;
 }
 
-static int flush_pending_noexcept(rtgl_context *ctx);
+static int flush_pending(rtgl_context *ctx);
 extern "C" int rtgl_create(rtgl_context **out, int width, int height, int device)
 {
     return rtgl_create_tiled(out, width, height, device, 0, 1, 8);
@@ -464,7 +465,7 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
     if (!ctx) return;
     // frames a batching context still holds back are submitted, not dropped (a caller that only ever called rtgl_render_frame and then
     // reads a bound device image after destroying the context would otherwise lose up to frame_batch - 1 frames)
-    if (!ctx->pending.empty() && hipSetDevice(ctx->device) == hipSuccess && flush_pending_noexcept(ctx) != RTGL_OK)
+    if (!ctx->pending.empty() && hipSetDevice(ctx->device) == hipSuccess && flush_pending(ctx) != RTGL_OK)
         fprintf(stderr, "rtgl_destroy: %zu batched frame(s) could not be submitted: %s\n", ctx->pending.size(), ctx->error.c_str());
     unregister_ctx_stream(ctx);
     for (auto &w : ctx->workers) {
@@ -525,7 +526,6 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
 
 extern "C" const char *rtgl_last_error(const rtgl_context *ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
-static int flush_pending(rtgl_context *ctx);
 #define ENTER_NOFLUSH(ctx) do { if (!(ctx)) return RTGL_ERR_INVALID; HIPCHK(ctx, hipSetDevice((ctx)->device)); } while (0)
 // every entry point but rtgl_render_frame / rtgl_set_frame_params first submits the frames a batching context is still holding back
 #define ENTER(ctx) do { ENTER_NOFLUSH(ctx); if (!(ctx)->pending.empty()) { const int rcf_ = flush_pending(ctx); if (rcf_) return rcf_; } } while (0)
@@ -902,9 +902,9 @@ static void kev_mark(rtgl_context *ctx)
 }
 
 // ---- bounce-wavefront pipeline: buffers + launches ------------------------------------------------
-// kernel 4 launches at most max(CUs, chunks) blocks of four waves; each wave owns one region of the candidate buffer
-static uint32_t solo_chunks(const rtgl_context *ctx);
-static uint32_t solo_regions(const rtgl_context *ctx) { return std::max<uint32_t>((uint32_t)ctx->n_cus, solo_chunks(ctx)) * 8u; }   // (8 waves per block with two waves per SIMD)
+// the scan launch policy (rt_scan_launch.hpp): what it needs to know of the device, the mesh and the options
+static_assert(rt_scan_launch::kQuadTris == (uint32_t)kMfQuadTris && rt_scan_launch::kQuadTiles == (uint32_t)kMfQuadTiles && rt_scan_launch::kRaysPerWave == SoloCfg::kRaysPerWave, "rt_scan_launch.hpp");
+static rt_scan_launch::Setup scan_setup(const rtgl_context *ctx) { return {(uint32_t)ctx->n_cus, rt_scan_launch::real_quads(ctx->n_mf_groups, ctx->mf_group_quads, ctx->n_tri_visits), (uint32_t)ctx->opt_mf_chunk_quads, ctx->opt_scan_waves, ctx->opt_scan_dynamic, ctx->opt_cull}; }
 
 static size_t counts_bytes(uint32_t capacity) { return (size_t)(capacity + 1u) * sizeof(uint32_t); }      // ray counts per bounce + the fullest candidate region
 
@@ -958,26 +958,19 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
         ctx->counts_capacity = max_bounce + 2; ctx->counts_pending = ctx->counts_valid = false; ctx->est_counts.clear();
     }
     if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
-        const uint32_t need_regions = solo_regions(ctx);
+        const rt_scan_launch::Capacity scan = rt_scan_launch::capacity(scan_setup(ctx));
+        const uint32_t need_regions = scan.regions;
         // (a record = one (ray, 5-triangle mask); every queue entry of the scan makes four of them)
         if (!ctx->cand_region_target) ctx->cand_region_target = std::max<uint32_t>(4096u, (uint32_t)std::min<uint64_t>(((uint64_t)n0 + need_regions - 1) / need_regions, 0xFFFFFFF0u));
         if (!ctx->d_cand || need_regions > ctx->cand_regions || ctx->cand_region_target > ctx->cand_region_pairs) {
             ctx->cand_regions = need_regions; ctx->cand_region_pairs = ctx->cand_region_target;
             RCCHK(buf_alloc(ctx, ctx->d_cand, ((size_t)need_regions * ctx->cand_region_pairs) * sizeof(uint2) + (size_t)need_regions * sizeof(uint32_t) + 256));      // (the free waits for the frames in flight)
         }
-        {                                                    // packet culling: one bit per (granule of 128 rays, tile); + 16 granules read ahead of the last one
-            const uint32_t real_quads = std::min(ctx->n_mf_groups * ctx->mf_group_quads, (ctx->n_tri_visits + (uint32_t)kMfQuadTris - 1) / (uint32_t)kMfQuadTris);
-            ctx->wb.keep_words = std::max(1u, (real_quads * (uint32_t)kMfQuadTiles + 31u) / 32u);
-            const size_t need = ((size_t)n0 / 128 + 16) * ctx->wb.keep_words;
-            RCCHK(buf_grow(ctx, ctx->d_keep, ctx->keep_capacity, need, need * sizeof(uint32_t)));
-        }
-        ctx->wb.keep = ctx->d_keep;
-        {                                                    // work distribution of the scan: one counter per (bounce, chunk); a launch has at most max(CUs, chunks) chunks
-            ctx->wb.sched_stride = std::max<uint32_t>((uint32_t)ctx->n_cus, solo_chunks(ctx));
-            const size_t need = (size_t)(max_bounce + 2) * ctx->wb.sched_stride;
-            RCCHK(buf_grow(ctx, ctx->d_sched, ctx->sched_capacity, need, need * sizeof(uint32_t)));
-            ctx->wb.sched = ctx->d_sched;
-        }
+        // packet culling: the keep bits of the queue being scanned; work distribution of the scan: one counter per (bounce, chunk)
+        const size_t need_keep = scan.keep_count(n0), need_sched = (size_t)(max_bounce + 2) * scan.sched_stride;
+        RCCHK(buf_grow(ctx, ctx->d_keep, ctx->keep_capacity, need_keep, need_keep * sizeof(uint32_t)));
+        RCCHK(buf_grow(ctx, ctx->d_sched, ctx->sched_capacity, need_sched, need_sched * sizeof(uint32_t)));
+        ctx->wb.keep_words = scan.keep_words; ctx->wb.keep = ctx->d_keep; ctx->wb.sched_stride = scan.sched_stride; ctx->wb.sched = ctx->d_sched;
         if (ctx->opt_cull == 3) {                            // ray binning: staging queue (64-byte records of a, b, c, rng, pixel 4 B), key + rank 8 B, source slot 4 B, and the bin counters
             RCCHK(buf_grow(ctx, ctx->d_stage, ctx->stage_capacity, n0, (size_t)n0 * 80 + 1024));
             uint8_t *p = (uint8_t *)ctx->d_stage;
@@ -1085,24 +1078,6 @@ static void launch_intersect(rtgl_context *ctx, const SceneView &sc, uint32_t n0
 #undef RTGL_LAUNCH_ISECT
 }
 
-// kernel 4: one block per CU (forced by the LDS request), persistent over the ray blocks of its triangle chunk
-static uint32_t solo_chunks(const rtgl_context *ctx)
-{
-    const uint32_t n_quads = ctx->n_mf_groups * ctx->mf_group_quads;
-    const uint32_t real_quads = std::min(n_quads, (ctx->n_tri_visits + (uint32_t)kMfQuadTris - 1) / (uint32_t)kMfQuadTris);
-    const uint32_t chunk_quads = std::min((uint32_t)ctx->opt_mf_chunk_quads, std::max(real_quads, 1u));
-    return (real_quads + chunk_quads - 1) / chunk_quads;
-}
-
-// work distribution of the scan (rt_scan.hpp): "scan_dynamic" 0 = by the mesh (hybrid; dynamic from 1,024 quads = 41k triangles on: few
-// blocks per chunk), 1 = static turns, 2 = dynamic claims, 3 = planned (equal-cost intervals of the item line, no atomics), 4 = hybrid
-// (turns + a claimed tail).  Returns the kernel's kDist: 0 static, 1 dynamic, 2 planned, 3 hybrid.
-static int solo_dynamic(const rtgl_context *ctx)
-{
-    const uint32_t real_quads = std::min(ctx->n_mf_groups * ctx->mf_group_quads, (ctx->n_tri_visits + (uint32_t)kMfQuadTris - 1) / (uint32_t)kMfQuadTris);
-    return ctx->opt_scan_dynamic ? ctx->opt_scan_dynamic - 1 : (real_quads >= 1024u ? 1 : 3);
-}
-
 // may the camera-ray keep bits computed for frame `a` serve frame `b`?  Same camera; then the rays differ by the jitter of camera_ray (:187-195)
 // only: origins by at most 2 |aperture|, unit directions by at most 2 |aperture| / (|focal| - |aperture|)
 static bool same_camera(const FrameParams &a, const FrameParams &b)
@@ -1123,104 +1098,75 @@ static bool camera_keep_widening(const FrameParams &P, float *ro_add, float *sig
     return true;
 }
 
+// the sixteen instances of the scan, [counters][W - 1][dist]: one table for the attribute loop and for the launch
+using ScanKernel = decltype(&scan_solo_kernel<false, 1, 0>);
+#define RTGL_SCAN_DISTS(C, WW) {scan_solo_kernel<C, WW, 0>, scan_solo_kernel<C, WW, 1>, scan_solo_kernel<C, WW, 2>, scan_solo_kernel<C, WW, 3>}
+static const ScanKernel kScanKernels[2][2][4] = {{RTGL_SCAN_DISTS(false, 1), RTGL_SCAN_DISTS(false, 2)}, {RTGL_SCAN_DISTS(true, 1), RTGL_SCAN_DISTS(true, 2)}};
+#undef RTGL_SCAN_DISTS
+
+// kernel 4: one block per CU (forced by the LDS request), persistent over the ray blocks of its triangle chunk
 static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_t n0, uint32_t bounce, bool binned, const FrameParams *cam)
 {
-    const uint32_t gq = ctx->mf_group_quads, n_quads = ctx->n_mf_groups * gq;
-    const uint32_t real_quads = std::min(n_quads, (ctx->n_tri_visits + (uint32_t)kMfQuadTris - 1) / (uint32_t)kMfQuadTris);
-    using Cfg = SoloCfg;
-    // Two waves per SIMD run the steady stream 1.5x faster (47 against 70 cycles per product).  Until the item loop moved into scalar
-    // registers small launches were better off with one wave per SIMD (half as many rays per block); measured since: two waves win or tie
-    // everywhere (C2 3.394 against 3.434 ms, a rank of eight 0.686 against 0.713 ms).  "scan_waves" = 0 / 2: two, 1: one.
-    const uint32_t est = estimate_rays(ctx, n0, bounce);
-    const uint32_t W = ctx->opt_scan_waves == 1 ? 1u : 2u;
-    const uint32_t waves = 4u * W;
-    const uint32_t est_gran = (est + Cfg::kRaysPerWave - 1u) / Cfg::kRaysPerWave;
-    // A launch has (granules x chunks) work items for its waves, claimed dynamically (rt_scan.hpp).  Late bounces (and every bounce of a
-    // rank that owns an eighth of the image) have few granules: cut the triangle range finer, down to 4 quads per chunk, until there are
-    // three items per wave (each item pays its ray and group set-up again, ~20 % at 8 quads, so only as far as needed -- thresholds of 1, 2,
-    // 4, 8 items per wave measured: 2-4 are best for a rank of four or eight, none matters at N = 1; never more chunks than CUs)
-    uint32_t chunk_quads = std::min((uint32_t)ctx->opt_mf_chunk_quads, std::max(real_quads, 1u));
+    // 1. how this launch is cut (rt_scan_launch.hpp)
+    const rt_scan_launch::Setup setup = scan_setup(ctx);
     const uint64_t items_per_wave = getenv("RTGL_AMD_ITEMS_PER_WAVE") ? (uint64_t)std::max(1, atoi(getenv("RTGL_AMD_ITEMS_PER_WAVE"))) : 3ull;      // (tuning; C2: bounce 5's launch 98 -> 89 us with three, bounces 6 and 7 +2 us each; a rank of four or eight, C4, C5: the same with two and three)
-    while (chunk_quads > 4u && (uint64_t)est_gran * ((real_quads + chunk_quads - 1) / chunk_quads) < items_per_wave * (uint32_t)ctx->n_cus * waves
-           && (real_quads + chunk_quads / 2 - 1) / (chunk_quads / 2) <= (uint32_t)ctx->n_cus)
-        chunk_quads /= 2u;
-    const uint32_t chunks = (real_quads + chunk_quads - 1) / chunk_quads;
-    // (auto: the camera-ray bounce of a small mesh keeps its fixed turns -- almost every item is empty there and a claimed tail only adds
-    // round trips: 74 us against 168 on C2; the binned bounces take the hybrid form: 660 -> 589, 553 -> 499 us)
-    const int cull = ctx->opt_cull == 2 || (ctx->opt_cull >= 1 && bounce == 0) || (ctx->opt_cull == 3 && binned);
-    // (unculled launches have items of equal cost: fixed turns are balanced there and a claimed tail only adds round trips)
-    const int dist = (ctx->opt_scan_dynamic == 0 && (bounce == 0 || !cull) && solo_dynamic(ctx) == 3) ? 0 : solo_dynamic(ctx), dynamic = dist == 1;
-    // one block per CU (forced by the LDS request); fewer when there is not an item per wave.  Static: the same number of blocks on
-    // every chunk.
-    uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)est_gran * chunks + waves - 1) / waves, (uint64_t)ctx->n_cus));
-    if (dist == 0 || dist == 3) blocks = std::max(1u, std::min((est_gran + waves - 1u) / waves, std::max(1u, (uint32_t)ctx->n_cus / chunks))) * chunks;
-    const size_t lds = std::max<size_t>(((size_t)chunk_quads * kMfQuadTiles + 4) * 1024, 96 * 1024);   // + the four rows read two trips ahead behind the last tile; > half of the CU's LDS with the static queue: one block per CU
+    const rt_scan_launch::Launch L = rt_scan_launch::launch(setup, items_per_wave, n0, estimate_rays(ctx, n0, bounce), bounce, binned);
+
+    // 2. the buffers it names
 #ifdef RT_SOLO_STAMPS
     if (!ctx->d_dbg_log) { RCCHK(buf_alloc(ctx, ctx->d_dbg_log, (size_t)(2 + (2u << 22)) * 4)); HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg_log, 0, 2048 * 8 + 16 * 64 * 2 * 16 * 8, ctx->stream)); }
 #endif
-    MfView mf{ctx->d_mf_groups, ctx->n_mf_groups, gq, n_quads, ctx->d_mf_A, ctx->d_dbg_log, ctx->d_mf_cull, ctx->d_edges_s, ctx->d_planes_s, ctx->d_mf_order};
+    MfView mf{ctx->d_mf_groups, ctx->n_mf_groups, ctx->mf_group_quads, ctx->n_mf_groups * ctx->mf_group_quads, ctx->d_mf_A, ctx->d_dbg_log, ctx->d_mf_cull, ctx->d_edges_s, ctx->d_planes_s, ctx->d_mf_order};
     if (!ctx->solo_attr_set) {
         // allow the whole LDS of a CU (160 KB) minus the kernel's static share as dynamic shared memory.  The attribute belongs to the
         // (function, device) pair, so it is raised once per context -- a context is bound to one device -- not once per process.
-        for (const void *fn : {reinterpret_cast<const void *>(&scan_solo_kernel<false, 1, 0>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 1, 0>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 2, 0>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 2, 0>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 1, 1>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 1, 1>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 2, 1>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 2, 1>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 1, 2>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 1, 2>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 2, 2>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 2, 2>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 1, 3>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 1, 3>),
-                               reinterpret_cast<const void *>(&scan_solo_kernel<false, 2, 3>), reinterpret_cast<const void *>(&scan_solo_kernel<true, 2, 3>)}) {
+        for (const auto &by_w : kScanKernels) for (const auto &by_dist : by_w) for (const ScanKernel k : by_dist) {
+            const void *fn = reinterpret_cast<const void *>(k);
             hipFuncAttributes fattr;
             HIPCHK(ctx, hipFuncGetAttributes(&fattr, fn));
             HIPCHK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - fattr.sharedSizeBytes)));
         }
         ctx->solo_attr_set = true;
     }
-    // packet culling pays where the 128 rays of a granule are coherent: the camera rays, and every queue that was binned (option "cull":
-    // 0 never, 1 bounce 0, 2 every bounce as the queues come, 3 (default) bounce 0 and the binned bounces)
-
-    if (cull) {
+    float ro_add = 0.0f, sigma_add = 0.0f; bool have_bits = false;
+    if (L.cull) {
         // camera-ray bounce of a single frame: the bits of an earlier frame of the same camera, image and scene, if there are any
-        float ro_add = 0.0f, sigma_add = 0.0f;
-        bool have_bits = false;
         if (bounce == 0 && cam && camera_keep_widening(*cam, &ro_add, &sigma_add) && !getenv("RTGL_AMD_NO_CAMERA_KEEP")) {
-            const size_t need = ((size_t)n0 / 128 + 16) * ctx->wb.keep_words;
+            const size_t need = rt_scan_launch::capacity(setup).keep_count(n0);
             if (ctx->keep0_capacity < need) ctx->keep0_valid = false;
             RCCHK(buf_grow(ctx, ctx->d_keep0, ctx->keep0_capacity, need, need * sizeof(uint32_t)));
             have_bits = ctx->keep0_valid && ctx->keep0_n0 == n0 && ctx->keep0_words == ctx->wb.keep_words && ctx->keep0_scene == ctx->scene_version && same_camera(ctx->keep0_params, *cam);
             ctx->wb.keep = ctx->d_keep0;
             if (!have_bits) { ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_params = *cam; }
         } else { ctx->wb.keep = ctx->d_keep; ro_add = sigma_add = 0.0f; }
+        if (L.dist == 2) {
+            RCCHK(buf_grow(ctx, ctx->d_plan, ctx->plan_capacity, L.plan_need, L.plan_need));
+            ctx->wb.plan_prefix = reinterpret_cast<uint32_t *>(ctx->d_plan); ctx->wb.plan_stride = L.stride;
+            ctx->wb.plan_total = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + L.plan_off_tot);
+            ctx->wb.plan_base = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + L.plan_off_base);
+        }
+        if (L.dist == 1) {
+            RCCHK(buf_grow(ctx, ctx->d_items, ctx->items_capacity, L.items_need, L.items_need));
+            ctx->wb.item_counts = reinterpret_cast<uint32_t *>(ctx->d_items);
+            ctx->wb.items = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_items) + L.items_head);
+            ctx->wb.items_stride = L.stride;
+        }
+    }
+
+    // 3. the launches
+    if (L.cull) {
         // (a binned queue is always culled here, and never from kept bits: bounce >= 1.  Under RTGL_AMD_SORT_MOVE = 1 this launch is what
         // moves its rays out of the staging queue)
         if (!have_bits)
-        hipLaunchKernelGGL(packet_cull_kernel, dim3(std::max(1u, std::min((est_gran + 3u) / 4u, 8192u))), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
+        hipLaunchKernelGGL(packet_cull_kernel, dim3(L.cull_blocks), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, setup.real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
                            ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt_sort_move == 1));
-        if (dist == 2) {
-            // planned: cost prefix sums per chunk [chunks x stride u32][chunks totals u32][chunks + 1 starts u64]
-            const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
-            const size_t off_tot = (((size_t)chunks * stride * sizeof(uint32_t)) + 255) & ~(size_t)255, off_base = (off_tot + (size_t)chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
-            const size_t need = off_base + ((size_t)chunks + 1) * sizeof(unsigned long long);
-            RCCHK(buf_grow(ctx, ctx->d_plan, ctx->plan_capacity, need, need));
-            ctx->wb.plan_prefix = reinterpret_cast<uint32_t *>(ctx->d_plan); ctx->wb.plan_stride = stride;
-            ctx->wb.plan_total = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + off_tot);
-            ctx->wb.plan_base = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(ctx->d_plan) + off_base);
-            if (ctx->opt_counters) hipLaunchKernelGGL(scan_plan_kernel<true>, dim3(chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, chunk_quads, real_quads, ctx->d_counters);
-            else hipLaunchKernelGGL(scan_plan_kernel<false>, dim3(chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, chunk_quads, real_quads, ctx->d_counters);
-            hipLaunchKernelGGL(scan_plan_base_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->wb, chunks);
+        if (L.dist == 2) {
+            hipLaunchKernelGGL(ctx->opt_counters ? scan_plan_kernel<true> : scan_plan_kernel<false>, dim3(L.chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
+            hipLaunchKernelGGL(scan_plan_base_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->wb, L.chunks);
         }
-        if (dynamic) {
-        // work items of the culled launch: [one count per chunk][chunks x (granules of the whole image) entries]
-        const uint32_t stride = n0 / Cfg::kRaysPerWave + 1u;
-        const size_t head = ((size_t)ctx->wb.sched_stride * sizeof(uint32_t) + 255) & ~(size_t)255, need = head + (size_t)chunks * stride * sizeof(uint32_t);
-        RCCHK(buf_grow(ctx, ctx->d_items, ctx->items_capacity, need, need));
-        ctx->wb.item_counts = reinterpret_cast<uint32_t *>(ctx->d_items);
-        ctx->wb.items = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->d_items) + head);
-        ctx->wb.items_stride = stride;
-        HIPCHK(ctx, hipMemsetAsync(ctx->wb.item_counts, 0, (size_t)chunks * sizeof(uint32_t), ctx->stream));
-        const dim3 igrid(std::max(1u, std::min((est_gran + 255u) / 256u, 1024u)), chunks);
-        if (ctx->opt_counters) hipLaunchKernelGGL(cull_items_kernel<true>, igrid, dim3(256), 0, ctx->stream, ctx->wb, bounce, chunk_quads, real_quads, ctx->d_counters);
-        else hipLaunchKernelGGL(cull_items_kernel<false>, igrid, dim3(256), 0, ctx->stream, ctx->wb, bounce, chunk_quads, real_quads, ctx->d_counters);
+        if (L.dist == 1) {
+            HIPCHK(ctx, hipMemsetAsync(ctx->wb.item_counts, 0, (size_t)L.chunks * sizeof(uint32_t), ctx->stream));
+            hipLaunchKernelGGL(ctx->opt_counters ? cull_items_kernel<true> : cull_items_kernel<false>, dim3(L.items_grid_x, L.items_grid_y), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
         }
     }
     // (testing the survivors of small launches in place instead of launching the narrow phase was measured: never faster --
@@ -1234,16 +1180,9 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
 #else
     const int fused = ctx->opt_narrow_fused;
 #endif
-#define RTGL_LAUNCH_SCAN(C, WW, D) hipLaunchKernelGGL((scan_solo_kernel<C, WW, D>), dim3(blocks), dim3(256 * WW), lds, ctx->stream, sc, ctx->wb, mf, bounce, chunk_quads, chunks, ctx->d_counters, ctx->opt_debug_skip_exact, cull, fused)
-#define RTGL_LAUNCH_SCAN_W(C, D) do { if (W == 2) RTGL_LAUNCH_SCAN(C, 2, D); else RTGL_LAUNCH_SCAN(C, 1, D); } while (0)
-    if (dist == 1) { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 1); else RTGL_LAUNCH_SCAN_W(false, 1); }
-    else if (dist == 2) { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 2); else RTGL_LAUNCH_SCAN_W(false, 2); }
-    else if (dist == 3) { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 3); else RTGL_LAUNCH_SCAN_W(false, 3); }
-    else { if (ctx->opt_counters) RTGL_LAUNCH_SCAN_W(true, 0); else RTGL_LAUNCH_SCAN_W(false, 0); }
-#undef RTGL_LAUNCH_SCAN_W
-#undef RTGL_LAUNCH_SCAN
+    hipLaunchKernelGGL(kScanKernels[ctx->opt_counters != 0][L.W - 1][L.dist], dim3(L.blocks), dim3(256 * L.W), L.lds, ctx->stream, sc, ctx->wb, mf, bounce, L.chunk_quads, L.chunks, ctx->d_counters, ctx->opt_debug_skip_exact, L.cull, fused);
     HIPCHK(ctx, hipGetLastError());
-    if (!fused) hipLaunchKernelGGL(narrow_phase_kernel, dim3(blocks * waves, kNarrowSplit), dim3(256), 0, ctx->stream, sc, ctx->wb, mf, bounce, blocks * waves);
+    if (!fused) hipLaunchKernelGGL(narrow_phase_kernel, dim3(L.blocks * L.waves, kNarrowSplit), dim3(256), 0, ctx->stream, sc, ctx->wb, mf, bounce, L.blocks * L.waves);
     return RTGL_OK;
 }
 
@@ -1269,7 +1208,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
         if (!n_counts) HIPCHK(ctx, hipMemsetAsync(ctx->d_counts, 0, counts_bytes(ctx->counts_capacity), ctx->stream));
         // the scan launches' work counters (rt_scan.hpp): cleared by the first threads of generate_rays_kernel where there are enough of them
         uint32_t n_sched = 0u;
-        if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->d_sched && (solo_dynamic(ctx) == 1 || solo_dynamic(ctx) == 3)) {
+        if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->d_sched && rt_scan_launch::uses_claim_counters(rt_scan_launch::mesh_dist(scan_setup(ctx)))) {      // (the mesh-level choice, not a launch's dist)
             const size_t words = (size_t)(P.max_bounce + 2) * ctx->wb.sched_stride;
             if (words <= (size_t)gen_grid.x * 256u && !getenv("RTGL_AMD_SCHED_FILL")) n_sched = (uint32_t)words;      // (the variable: measurement of the fill launch this replaces)
             else HIPCHK(ctx, hipMemsetAsync(ctx->d_sched, 0, words * sizeof(uint32_t), ctx->stream));
@@ -1383,7 +1322,6 @@ static bool batch_compatible(const FrameParams &a, const FrameParams &b)
     return a.samples == b.samples && a.max_bounce == b.max_bounce && a.use_envmap == b.use_envmap && memcmp(a.background, b.background, sizeof a.background) == 0;
 }
 
-static int flush_pending_noexcept(rtgl_context *ctx) { return flush_pending(ctx); }
 static int flush_pending(rtgl_context *ctx)
 {
     if (ctx->pending.empty()) return RTGL_OK;
