@@ -301,8 +301,8 @@ static int find_closest_mesh(const oracle_scene *sc, v3 o, v3 d, hit_t *hit, ora
     for (uint32_t i = 0; i < sc->n_meshes; i++) {
         uint32_t start = rdu(sc->meshes + (size_t)i * 16);
         uint32_t size = rdu(sc->meshes + (size_t)i * 16 + 4);
-        uint64_t end64 = (uint64_t)start + size;
-        uint32_t end = end64 > n_tris ? n_tris : (uint32_t)end64;
+        uint32_t bound = start + size;                  /* uint32 like the shader's `offset + count` (:341): the sum may wrap */
+        uint32_t end = bound > n_tris ? n_tris : bound; /* past the buffer: all-zero vertices, the edge tests (> 0) never pass */
         for (uint32_t v = start; v < end; v++) {
             const uint8_t *p = sc->vertices + (size_t)v * 48;
             v3 v0 = V(rdf(p), rdf(p + 4), rdf(p + 8));

@@ -25,6 +25,7 @@
 #include "rt_tonemap.hpp"
 #include "rt_error.hpp"
 #include "rt_node_walk.hpp"
+#include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
 #include "rt_scan_launch.hpp"
 
@@ -38,7 +39,9 @@ using namespace rt;
 
 // ---- upload-time preparation -------------------------------------------------------------------
 // One thread per triangle visit.  visit_tri[k] = triangle index tested k-th by the reference's
-// mesh loops (find_closest_mesh :336-341: meshes in order, triangles start..start+size-1 each).
+// mesh loops (find_closest_mesh :336-341: meshes in order, each over [start, start + size) with the sum taken in 32 bits as the
+// shader takes it -- a sum that wraps ends the loop early or empties it -- and without the indices past the vertex buffer, whose
+// all-zero triangles no ray can hit: rt_mesh_visits.hpp).
 __global__ void __launch_bounds__(256) prepare_triangles_kernel(const float4 *__restrict__ vertices,
                                                                 const uint32_t *__restrict__ visit_tri, uint32_t n_visits,
                                                                 TriEdges *__restrict__ edges, TriPlane *__restrict__ planes)
@@ -814,13 +817,7 @@ static int rebuild_triangles(rtgl_context *ctx)
 {
     std::vector<uint32_t> visit_tri, visit_mesh;
     uint32_t n_tris = ctx->n_vec4 / 3;   // to_triangles() drops a trailing partial triangle (src/renderer.h:34-48)
-    for (uint32_t m = 0; m < ctx->n_meshes; ++m) {
-        uint32_t start, size;
-        memcpy(&start, ctx->h_meshes.data() + (size_t)m * 16, 4);
-        memcpy(&size, ctx->h_meshes.data() + (size_t)m * 16 + 4, 4);
-        uint64_t end = std::min<uint64_t>((uint64_t)start + size, n_tris);
-        for (uint64_t t = start; t < end; ++t) { visit_tri.push_back((uint32_t)t); visit_mesh.push_back(m); }
-    }
+    rt_mesh_visits::expand(ctx->h_meshes.data(), ctx->n_meshes, n_tris, visit_mesh, visit_tri);      // the shader's 32-bit loop bounds
     ctx->h_visit_tri = visit_tri; ctx->h_visit_mesh.swap(visit_mesh); ctx->visit_ids_dirty = true;      // (the ids plane's triangle ids)
     RCCHK(buf_release(ctx, ctx->d_edges, ctx->d_planes));
     ctx->n_tri_visits = (uint32_t)visit_tri.size();

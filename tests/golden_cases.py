@@ -86,7 +86,45 @@ def build_cases(sc):
     add("camera_moved", lambda: sc.scene_mesh(20, 10, env_size=32), 96, 64,
         frame_sequence(sc, P2.replace(camera_position=(4.0, 3.0, -28.0), camera_forward=(-0.19611613, -0.0, 0.98058068),
                                       camera_right=(-0.98058068, 0.0, -0.19611613), camera_fov=float(sc.radians_f32(50.0))), 2))
+    # --- mesh records as the shader reads them: `offset + count` in 32 bits (:341), starts and ends past the buffer, gaps, zero sizes,
+    #     overlaps in descending order, no records at all, one triangle per record
+    for name in mesh_record_sets(400):
+        add("meshrec_" + name, lambda name=name: scene_mesh_records(sc, name), 48, 32, frame_sequence(sc, P2.replace(use_dof=0, max_bounce=3), 2))
     return C
+
+
+# ---------------------------------------------------------------------------------- mesh records
+
+def mesh_record_sets(n):
+    """name -> [(start, size)] over a vertex buffer of n triangles.  The first three wrap to a bound at or below their start: the
+    shader's loop runs zero times, a 64-bit bound clamped to the buffer would visit start .. n - 1."""
+    T = 1 << 32
+    return {
+        "wrap_all_ones": [(5, T - 1)],
+        "wrap_below_start": [(100, T - 50)],
+        "wrap_to_zero": [(7, T - 7)],
+        "wrap_far_start": [(0xFFFFFFF0, 0x20)],
+        "wrap_to_n": [(T - 10, n + 10)],
+        "wrap_then_whole": [(3, T - 1), (0, n)],
+        "start_past_buffer": [(n + 5, 20), (50, 200)],
+        "zero_sizes_and_gaps": [(0, 0), (10, 50), (60, 0), (100, 37), (n - 1, 1), (200, 0)],
+        "reversed_overlap": [(300, 100), (150, 200), (0, 200), (100, 100)],
+        "no_records": [],
+        "single_triangles_134": [(3 * i, 1) for i in range(134)],
+    }
+
+
+def mesh_records(recs):
+    out = np.zeros((len(recs), 4), np.uint32)
+    for i, (start, size) in enumerate(recs):
+        out[i, 0], out[i, 1] = start, size
+    return out
+
+
+def scene_mesh_records(sc, name):
+    s = sc.scene_mesh(20, 10, env_size=16)
+    s.meshes = mesh_records(mesh_record_sets(s.n_triangles)[name])
+    return s
 
 
 # ---------------------------------------------------------------------------------- extra scenes

@@ -11,6 +11,7 @@ import pytest
 
 import golden_cases as gc
 import raytracer_glsl_amd
+from mesh_fuzz_inputs import spans as mesh_spans
 from test_oracle_golden import CASE_FILES, load_case
 
 pytestmark = pytest.mark.gpu
@@ -171,11 +172,10 @@ def test_planes_match_the_oracles_first_hit(name, rt, oracle):
         uv = np.linalg.solve(M, np.stack([(rel * a).sum(1), (rel * b).sum(1)], axis=-1)[..., None])[..., 0]
         assert (uv > -1e-4).all() and (uv.sum(axis=1) < 1 + 1e-4).all(), "hit point outside the named triangle"
         # the mesh: the first one that lists the triangle (hits merge by visit index, and a mesh's visits come before the next one's)
-        meshes = np.asarray(scene.meshes, np.uint32).reshape(-1, 4).astype(np.int64)
         n_tris = V.shape[0] // 3
         first_mesh = np.full(n_tris, -1, np.int64)
-        for m in range(meshes.shape[0] - 1, -1, -1):
-            first_mesh[meshes[m, 0]:min(meshes[m, 0] + meshes[m, 1], n_tris)] = m
+        for m, a, b in reversed(mesh_spans(scene.meshes, n_tris)):      # the shader's 32-bit loop bounds (tests/mesh_fuzz_inputs.py)
+            first_mesh[a:b] = m
         assert (obj[tri] == first_mesh[prim[tri]]).all()
         if name == "mesh_two_meshes_overlap":
             assert (obj[tri] == 1).any(), "the second mesh's own triangles are never reported"

@@ -58,7 +58,7 @@ def gpu_run(rt, scene, frames, W, H, options, init="zeros", batch=False):
     return img, seeds, cnt
 
 
-def differences(got, want, W, H):
+def differences(got, want, W, H, counters=("paths", "segments", "env_lookups")):
     """[] when `got` equals the oracle's `want` under the module's rule, else what differs"""
     (img_g, seeds_g, cnt_g), (img_o, seeds_o, cnt_o) = got, want
     out = []
@@ -71,18 +71,18 @@ def differences(got, want, W, H):
         s = int((seeds_g[:dh, :dw] != seeds_o[:dh, :dw]).any(axis=-1).sum())
         if s:
             out.append(f"rng states {s}")
-        for k in ("paths", "segments", "env_lookups"):
+        for k in counters:
             if cnt_g[k] != cnt_o[k]:
                 out.append(f"{k} {cnt_g[k]} != {cnt_o[k]}")
     return out
 
 
-def check_case(rt, oracle, key, scene, frames, W, H, variants, init="zeros", batch_options=None):
+def check_case(rt, oracle, key, scene, frames, W, H, variants, init="zeros", batch_options=None, counters=("paths", "segments", "env_lookups")):
     """number of differing runs of one case; one printed line each"""
     want = oracle_run(oracle, key, scene, frames, W, H, init)
     bad = 0
     for options in variants:
-        d = differences(gpu_run(rt, scene, frames, W, H, options, init), want, W, H)
+        d = differences(gpu_run(rt, scene, frames, W, H, options, init), want, W, H, counters)
         if d:
             bad += 1
             print("case", key, dict(options), ":", "; ".join(d), "|", W, "x", H, "spheres", scene.spheres.shape[0], "nodes", scene.nodes.shape[0],
