@@ -591,7 +591,10 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
  * "narrow_fused" (kernel 4, also RTGL_AMD_NARROW_FUSED, read when a context is created: who gives the survivors of the scan their exact test.  0: narrow_phase_kernel,
  * launched behind every scan launch; 1 (default): every scan wave tests the records of its own candidate region when it has run out of work items, beside the waves that are still
  * scanning, and narrow_phase_kernel is not launched.  The image is the same bit for bit -- hits merge by an atomic minimum -- on every path: single frames, "frame_batch", the
- * strips of a rank), "cull" (packet culling: a granule of 128 rays skips the tiles
+ * strips of a rank), "camera_lean" (kernel 4, also RTGL_AMD_CAMERA_LEAN, read when a context is created: the camera-ray bounce of a frame that is culled from the keep
+ * bits an earlier frame left -- same camera, image and scene, a single frame of one sample, "aov" off.  1 (default): ray generation stores only what the scan reads (origin,
+ * direction, hit key) and the shade launch of that bounce rebuilds each camera ray from its queue slot instead of loading it; 0: every
+ * camera ray travels through the queue in full.  Every other frame runs as with 0.  The image is the same bit for bit), "cull" (packet culling: a granule of 128 rays skips the tiles
  * of 10 triangles for which every one of its rays is certified to be rejected by the reference's own test: 0 off, 1 on the camera-ray
  * bounce, 2 on every bounce with the queues as they come, 3 (default) on the camera-ray bounce and on every bounce whose queue was BINNED
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"
@@ -606,7 +609,9 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
  * per frame and for scenes without triangles frames are rendered one by one; rtgl_destroy submits frames that are still waiting;
  * rtgl_device_image returns NULL when that submission fails) */
 int rtgl_set_option(rtgl_context *ctx, const char *key, int value);
-int rtgl_get_option(rtgl_context *ctx, const char *key, int *value);   /* also "kernel_in_use": the variant the last frame ran */
+/* rtgl_get_option also answers read-only keys: "kernel_in_use" (the variant the last frame ran); "camera_lean_frames" (the frames of this
+ * context that took the lean camera bounce, option "camera_lean": tells a taken path from a fallback) */
+int rtgl_get_option(rtgl_context *ctx, const char *key, int *value);
 /* elapsed GPU milliseconds of the last rtgl_render_frame (HIP events on the context's stream) */
 int rtgl_last_frame_ms(rtgl_context *ctx, float *ms);
 /* Per-kernel GPU time of the last frame, from HIP events recorded around every launch of the dominant

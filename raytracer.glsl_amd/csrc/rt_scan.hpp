@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) p
                 ro = fmaxf(ro, __builtin_amdgcn_sqrtf(dot3(eo, eo))); sigma = fmaxf(sigma, __builtin_amdgcn_sqrtf(dot3(ed, ed)));
             }
         // (ro_add, sigma_add: the camera-ray bits are kept for the frames that follow while the camera stands still; their rays differ from
-        // this frame's by the depth-of-field jitter only, which the host bounds -- rtgl_amd.hip, camera_keep_valid)
+        // this frame's by the depth-of-field jitter only, which the host bounds -- rt_camera_keep.hpp, widening)
         pk.ro = full_reduce<true>(ro) * 1.0001f + 1e-30f + ro_add; pk.sigma = full_reduce<true>(sigma) * 1.0001f + 2e-6f + sigma_add;
         usable = !__any(!usable) && (Dl > 0.25f);
         pk.On = __builtin_amdgcn_sqrtf(dot3(pk.O, pk.O)) * 1.0001f + pk.ro;

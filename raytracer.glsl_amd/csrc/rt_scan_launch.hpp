@@ -36,6 +36,10 @@ inline Capacity capacity(const Setup &s)
 inline int mesh_dist(const Setup &s) { return s.scan_dynamic ? s.scan_dynamic - 1 : (s.real_quads >= 1024u ? 1 : 3); }
 inline bool uses_claim_counters(int dist) { return dist == 1 || dist == 3; }
 
+// packet culling pays where the 128 rays of a granule are coherent: the camera rays, and every queue that was binned (option "cull":
+// 0 never, 1 bounce 0, 2 every bounce as the queues come, 3 (default) bounce 0 and the binned bounces)
+inline bool culls(const Setup &s, uint32_t bounce, bool binned) { return s.cull == 2 || (s.cull >= 1 && bounce == 0) || (s.cull == 3 && binned); }
+
 struct Launch {
     uint32_t W, waves, est_gran, chunk_quads, chunks, blocks;      // waves per SIMD and per block; granules of 128 rays expected in the queue
     int cull, dist; size_t lds;                                    // packet culling runs; the kernel's kDist; dynamic shared memory of the scan
@@ -64,9 +68,7 @@ inline Launch launch(const Setup &s, uint64_t items_per_wave, uint32_t n0, uint3
         chunk_quads /= 2u;
     const uint32_t chunks = (s.real_quads + chunk_quads - 1) / chunk_quads;
     L.chunk_quads = chunk_quads; L.chunks = L.items_grid_y = chunks;
-    // packet culling pays where the 128 rays of a granule are coherent: the camera rays, and every queue that was binned (option "cull":
-    // 0 never, 1 bounce 0, 2 every bounce as the queues come, 3 (default) bounce 0 and the binned bounces)
-    L.cull = s.cull == 2 || (s.cull >= 1 && bounce == 0) || (s.cull == 3 && binned);
+    L.cull = culls(s, bounce, binned);
     // (auto: the camera-ray bounce of a small mesh keeps its fixed turns -- almost every item is empty there and a claimed tail only adds
     // round trips: 74 us against 168 on C2; the binned bounces take the hybrid form: 660 -> 589, 553 -> 499 us)
     // (unculled launches have items of equal cost: fixed turns are balanced there and a claimed tail only adds round trips)

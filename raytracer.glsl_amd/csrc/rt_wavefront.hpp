@@ -198,11 +198,35 @@ __device__ __forceinline__ void aov_write(const SceneView &sc, const AovView &ao
 }
 
 // ---- queue 0 ---------------------------------------------------------------------------------------
+// queue order = 8x8 pixel blocks, row-major over blocks: neighbouring lanes start as neighbouring pixels.  The pixel of slot `idx` of a
+// frame's stretch of queue 0; false: the slot holds no ray (rows past the dispatch footprint come last in every strip order).  One
+// definition for ray generation and for the camera form of shade, which rebuilds the ray from its slot.
+__device__ __forceinline__ bool camera_slot_pixel(const ImageView &im, uint32_t idx, int &px, int &py, int &lrow)
+{
+    const uint32_t blocks_x = im.disp_w >> 3;
+    const uint32_t blk = idx >> 6, in = idx & 63u;
+    const uint32_t bx = blk % blocks_x, by = blk / blocks_x;
+    px = (int)(bx * 8u + (in & 7u)); lrow = (int)(by * 8u + (in >> 3)); py = 0;
+    if (lrow >= im.local_rows) return false;
+    py = local_to_global_row(im, lrow);
+    return py < im.disp_h;
+}
+// sample 0 of a pixel: the generator's seed and the camera ray it draws
+__device__ __forceinline__ void camera_slot_ray(const FrameParams &P, const ImageView &im, int px, int py, PathState &s)
+{
+    s.rng.x = (uint32_t)px; s.rng.y = (uint32_t)py; s.rng.z = (uint32_t)P.random;
+    s.rng.w = (uint32_t)px + (uint32_t)py + (uint32_t)P.random;
+    camera_ray(P, px, py, im.width, im.height, s.rng, s.o, s.d);
+}
+
 // sample 0: camera rays from scratch.  sample > 0: same camera ray, RNG continued (:556-559).
 // Frame batching: the launch of frame f of a batch writes slots [slot_off, slot_off + n0) with pixel_tag = f << 28; only the first stores
 // the batch's ray count (count0 = rays of all its frames; 0: leave the count alone).  A single frame: slot_off = pixel_tag = 0, count0 = n0.
+// Lean camera bounce (option "camera_lean"; rtgl_amd.hip, launch_wavefront): a camera ray is a pure function of the uniforms and its
+// slot, so the shade launch of bounce 0 (shade_camera_kernel) rebuilds origin, direction, generator state and pixel index instead of
+// loading them, and this kernel stores only what the scan reads: `a`, `b` and the hit key (lean != 0; sample 0 of a single frame only).
 __global__ void __launch_bounds__(256) generate_rays_kernel(FrameParams P, ImageView im, WaveBuffers wb, uint32_t sample, uint32_t n0, Counters *counters, uint32_t n_counts,
-                                                            uint32_t slot_off, uint32_t pixel_tag, uint32_t count0, uint32_t n_sched)
+                                                            uint32_t slot_off, uint32_t pixel_tag, uint32_t count0, uint32_t n_sched, uint32_t lean)
 {
     // the ray counts of the bounces (and the word behind them) start at zero: cleared here rather than by a memset launch of their own
     // (n_counts = 0: the host has done it); nothing touches them before the first shade kernel
@@ -215,19 +239,18 @@ __global__ void __launch_bounds__(256) generate_rays_kernel(FrameParams P, Image
         if (count0) store_through(wb.counts, count0);
         if (counters) atomicAdd(&counters->paths, (unsigned long long)n0);
     }
-    const uint32_t blocks_x = im.disp_w >> 3;
-    const uint32_t blk = idx >> 6, in = idx & 63u;
-    const uint32_t bx = blk % blocks_x, by = blk / blocks_x;
-    const int px = (int)(bx * 8u + (in & 7u)), lrow = (int)(by * 8u + (in >> 3));
-    if (lrow >= im.local_rows) return;
-    const int py = local_to_global_row(im, lrow);
-    if (py >= im.disp_h) return;      // rows past the dispatch footprint come last in every strip order
+    int px, py, lrow;
+    if (!camera_slot_pixel(im, idx, px, py, lrow)) return;
     PathState s;
     s.pixel = (uint32_t)lrow * (uint32_t)im.width + (uint32_t)px;
     if (sample == 0u) {
-        s.rng.x = (uint32_t)px; s.rng.y = (uint32_t)py; s.rng.z = (uint32_t)P.random;
-        s.rng.w = (uint32_t)px + (uint32_t)py + (uint32_t)P.random;
-        camera_ray(P, px, py, im.width, im.height, s.rng, s.o, s.d);
+        camera_slot_ray(P, im, px, py, s);
+        if (lean) {
+            store_through(wb.q[0].a + (slot_off + idx), s.o.x, s.o.y, s.o.z, s.d.x);
+            store_through(wb.q[0].b + (slot_off + idx), s.d.y, s.d.z, 1.0f, 1.0f);
+            store_through(wb.best[0] + (slot_off + idx), 0xFFFFFFFFFFFFFFFFull);
+            return;
+        }
         if (P.samples > 1u) {
             store_through(wb.cam_a + s.pixel, s.o.x, s.o.y, s.o.z, s.d.x);
             store_through(wb.cam_b + s.pixel, s.d.y, s.d.z, 0.0f, 0.0f);
@@ -757,9 +780,11 @@ __device__ __forceinline__ uint32_t ray_bin_key(const WaveBuffers &wb, f3 o, f3 
 }
 
 // kAov: the launch of bounce 0 of sample 0 while option "aov" is on; it also writes the first-hit planes
-template <bool kCount, bool kSort, bool kAov>
-__global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
-                                                    uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
+// kCamera: the lean camera bounce (generate_rays_kernel) -- bounce 0 of a single frame of one sample.  The ray is rebuilt from its slot
+// with ray generation's own instructions instead of loaded; the hit key is all it reads of the queue.
+template <bool kCount, bool kSort, bool kAov, bool kCamera>
+__device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
+                                           uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
 {
     const uint32_t n_rays = wb.counts[bounce];
     const RayQueue qin = (bounce & 1u) ? wb.q[1] : wb.q[0];
@@ -774,11 +799,16 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
     __shared__ float4 s_rec[kSort ? 4 * 64 * 4 : 1];
     for (uint32_t blk = blockIdx.x; blk * 256u < n_rays; blk += gridDim.x) {      // grid-stride, see intersect_kernel
     const uint32_t slot = blk * 256u + threadIdx.x;
-    const bool valid = slot < n_rays;
+    int cam_px = 0, cam_py = 0, cam_lrow = 0;
+    const bool valid = slot < n_rays && (!kCamera || camera_slot_pixel(im, slot, cam_px, cam_py, cam_lrow));
     bool alive = false;
     PathState s;
     if (valid) {
-        s = load_ray(qin, slot, bounce == 0u);
+        if (kCamera) {
+            camera_slot_ray(P, im, cam_px, cam_py, s);
+            s.thr = mk(1.0f, 1.0f, 1.0f); s.rad = mk(0.0f, 0.0f, 0.0f);
+            s.pixel = (uint32_t)cam_lrow * (uint32_t)im.width + (uint32_t)cam_px;
+        } else s = load_ray(qin, slot, bounce == 0u);
         const unsigned long long key = best_in[slot];
         Hit h; h.t = kInf; h.material = 0; h.point = h.normal = mk(0.0f, 0.0f, 0.0f);
         uint32_t sphere_id = kNoSphere;
@@ -853,12 +883,30 @@ __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P,
             if (i < parts) { const float4 v = s_rec[wave * 256u + i]; store_through(wb.stage + 4u * wave_base + i, v.x, v.y, v.z, v.w); }
         }
     }
+    // (the camera form is launched with a block per 256 slots of queue 0 -- its length is known on the host -- and makes one pass: what
+    // the loop keeps live from pass to pass cost it 38 to 62 spilled scalar registers and half its waves per SIMD)
+    if (kCamera) break;
     __syncthreads();                                                              // s_cnt is rewritten by the next batch
     }
     if (kCount) {
         atomicAdd(&counters->env_lookups, c_env);
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->segments, (unsigned long long)n_rays);
     }
+}
+
+template <bool kCount, bool kSort, bool kAov>
+__global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
+                                                    uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
+{
+    shade_body<kCount, kSort, kAov, false>(sc, P, im, wb, bounce, rng_out, counters, aov);
+}
+// the shade launch of a lean camera bounce (bounce 0; no first-hit planes: the host takes the lean form only while option "aov" is off).
+// One block per 256 slots: ceil(n0 / 256) blocks, no grid stride.
+template <bool kCount, bool kSort>
+__global__ void __launch_bounds__(256) shade_camera_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
+                                                           uint4 *rng_out, Counters *counters)
+{
+    shade_body<kCount, kSort, false, true>(sc, P, im, wb, 0u, rng_out, counters, AovView{});
 }
 
 // ---- ray binning: bin counts -> first slots (two launches), then the move staging queue -> next queue.

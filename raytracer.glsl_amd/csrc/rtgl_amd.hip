@@ -28,6 +28,7 @@
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
 #include "rt_scan_launch.hpp"
+#include "rt_camera_keep.hpp"
 
 #pragma clang fp contract(off)
 
@@ -239,7 +240,9 @@ struct rtgl_context {
     // the camera-ray bounce's keep bits, kept across frames while camera, image and scene stand still (a progressive render's normal state):
     // the camera rays of two frames differ by the depth-of-field jitter only, so bits certified for one frame's rays with the packet bounds
     // widened by that jitter hold for all of them and packet_cull_kernel is skipped on bounce 0 (a third of its work)
-    uint32_t *d_keep0 = nullptr; size_t keep0_capacity = 0; bool keep0_valid = false; FrameParams keep0_params{}; uint32_t keep0_n0 = 0, keep0_words = 0; uint64_t keep0_scene = 0;
+    uint32_t *d_keep0 = nullptr; size_t keep0_capacity = 0; bool keep0_valid = false; rt_camera_keep::Camera keep0_camera{}; uint32_t keep0_n0 = 0, keep0_words = 0; uint64_t keep0_scene = 0;
+    int opt_camera_lean = 1;                                // the lean camera bounce on frames that reuse those bits (option "camera_lean", RTGL_AMD_CAMERA_LEAN; rt_wavefront.hpp, generate_rays_kernel)
+    uint32_t camera_lean_frames = 0;                        // frames of this context that took the lean camera bounce
     uint64_t scene_version = 0;
     void *d_plan = nullptr; size_t plan_capacity = 0;             // planned work distribution of culled scan launches: cost prefix sums per chunk
     void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
@@ -453,6 +456,7 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     if (const char *k = getenv("RTGL_AMD_SCAN_DYNAMIC")) { const int v = atoi(k); if (v >= 0 && v <= 4) ctx->opt_scan_dynamic = v; }   // ... and of its work distribution
     if (const char *k = getenv("RTGL_AMD_NARROW_FUSED")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_narrow_fused = v; }   // A/B of the scan's tail drain
     if (const char *k = getenv("RTGL_AMD_SORT_MOVE")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_sort_move = v; }   // A/B of ray binning's move
+    if (const char *k = getenv("RTGL_AMD_CAMERA_LEAN")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_camera_lean = v; }   // A/B of the lean camera bounce
     *out = ctx;
     return RTGL_OK;
 }
@@ -1052,6 +1056,15 @@ static void launch_shade(rtgl_context *ctx, dim3 grid, const SceneView &sc, cons
         hipLaunchKernelGGL((shade_kernel<false, kSort, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
 }
 
+// shade_camera_kernel: bounce 0 of a lean frame, a block per 256 slots of queue 0 (the kernel makes one pass)
+template <bool kSort>
+static void launch_shade_camera(rtgl_context *ctx, uint32_t n0, const SceneView &sc, const FrameParams &P, const ImageView &im, uint4 *rng_out)
+{
+    const dim3 grid((n0 + 255u) / 256u);
+    if (ctx->opt_counters) hipLaunchKernelGGL((shade_camera_kernel<true, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
+    else hipLaunchKernelGGL((shade_camera_kernel<false, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
+}
+
 // Upper estimate of the rays entering `bounce`, for grid sizing only (kernels grid-stride, so a low
 // estimate costs time, never correctness): last finished frame's count + 10 % + 2048, capped by n0.
 static uint32_t estimate_rays(const rtgl_context *ctx, uint32_t n0, uint32_t bounce)
@@ -1075,24 +1088,31 @@ static void launch_intersect(rtgl_context *ctx, const SceneView &sc, uint32_t n0
 #undef RTGL_LAUNCH_ISECT
 }
 
-// may the camera-ray keep bits computed for frame `a` serve frame `b`?  Same camera; then the rays differ by the jitter of camera_ray (:187-195)
-// only: origins by at most 2 |aperture|, unit directions by at most 2 |aperture| / (|focal| - |aperture|)
-static bool same_camera(const FrameParams &a, const FrameParams &b)
+// The camera-ray bounce of one frame and the kept bits (rt_camera_keep.hpp: the rule; here: its inputs, and the buffer).  Decided once
+// per frame, before ray generation is enqueued (launch_wavefront): the scan's launch of bounce 0 and the lean camera bounce both go by
+// it.  cam = NULL: not a single frame of one sample.  A frame that is `cached` without `have_bits` rebuilds the bits (launch_intersect_solo).
+using CameraKeep = rt_camera_keep::Decision;
+static rt_camera_keep::Camera keep_camera(const FrameParams &P)
 {
-    return a.use_dof == b.use_dof && a.cam_fov == b.cam_fov && a.cam_aperture == b.cam_aperture && a.cam_focal == b.cam_focal
-           && memcmp(a.cam_pos, b.cam_pos, sizeof a.cam_pos) == 0 && memcmp(a.cam_forward, b.cam_forward, sizeof a.cam_forward) == 0
-           && memcmp(a.cam_up, b.cam_up, sizeof a.cam_up) == 0 && memcmp(a.cam_right, b.cam_right, sizeof a.cam_right) == 0;
+    rt_camera_keep::Camera c{};
+    c.use_dof = P.use_dof; c.fov = P.cam_fov; c.aperture = P.cam_aperture; c.focal = P.cam_focal;
+    memcpy(c.pos, P.cam_pos, sizeof c.pos); memcpy(c.forward, P.cam_forward, sizeof c.forward); memcpy(c.up, P.cam_up, sizeof c.up); memcpy(c.right, P.cam_right, sizeof c.right);
+    return c;
 }
-static bool camera_keep_widening(const FrameParams &P, float *ro_add, float *sigma_add)
+static int camera_keep_decide(rtgl_context *ctx, uint32_t n0, const FrameParams *cam, CameraKeep *ck)
 {
-    *ro_add = *sigma_add = 0.0f;
-    if (!P.use_dof) return true;                         // the same ray every frame, bit for bit
-    const float a = fabsf(P.cam_aperture), f = fabsf(P.cam_focal);
-    const float pn = sqrtf(P.cam_pos[0] * P.cam_pos[0] + P.cam_pos[1] * P.cam_pos[1] + P.cam_pos[2] * P.cam_pos[2]);
-    if (!(a < 0.25f * f) || !(f < 1.0e18f) || !(pn < 1.0e18f)) return false;     // (NaN included) no bound worth having: certify every frame's rays
-    *ro_add = 2.0f * a * 1.001f + 1.0e-5f * (1.0f + pn);
-    *sigma_add = 2.0f * a / (f - a) * 1.001f + 4.0e-6f;
-    return true;
+    const rt_scan_launch::Setup setup = scan_setup(ctx);
+    rt_camera_keep::Frame f{};
+    f.culled = rt_scan_launch::culls(setup, 0u, false); f.single = cam != nullptr; f.enabled = !getenv("RTGL_AMD_NO_CAMERA_KEEP");
+    f.n0 = n0; f.words = ctx->wb.keep_words; f.scene = ctx->scene_version;
+    if (cam) f.camera = keep_camera(*cam);
+    const size_t need = rt_scan_launch::capacity(setup).keep_count(n0);
+    f.room = ctx->keep0_capacity >= need;
+    const rt_camera_keep::Key key{ctx->keep0_valid, ctx->keep0_n0, ctx->keep0_words, ctx->keep0_scene, ctx->keep0_camera};
+    *ck = rt_camera_keep::decide(key, f);
+    if (!ck->cached) return RTGL_OK;
+    if (!ck->have_bits) ctx->keep0_valid = false;      // (valid again once packet_cull_kernel is in the stream)
+    return buf_grow(ctx, ctx->d_keep0, ctx->keep0_capacity, need, need * sizeof(uint32_t));
 }
 
 // the sixteen instances of the scan, [counters][W - 1][dist]: one table for the attribute loop and for the launch
@@ -1102,7 +1122,8 @@ static const ScanKernel kScanKernels[2][2][4] = {{RTGL_SCAN_DISTS(false, 1), RTG
 #undef RTGL_SCAN_DISTS
 
 // kernel 4: one block per CU (forced by the LDS request), persistent over the ray blocks of its triangle chunk
-static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_t n0, uint32_t bounce, bool binned, const FrameParams *cam)
+// ck, cam: bounce 0 only -- what camera_keep_decide said of this frame, and the frame's uniforms
+static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_t n0, uint32_t bounce, bool binned, const CameraKeep *ck, const FrameParams *cam)
 {
     // 1. how this launch is cut (rt_scan_launch.hpp)
     const rt_scan_launch::Setup setup = scan_setup(ctx);
@@ -1126,16 +1147,11 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
         ctx->solo_attr_set = true;
     }
     float ro_add = 0.0f, sigma_add = 0.0f; bool have_bits = false;
+    const bool cached = L.cull && bounce == 0 && ck && cam && ck->cached;
     if (L.cull) {
         // camera-ray bounce of a single frame: the bits of an earlier frame of the same camera, image and scene, if there are any
-        if (bounce == 0 && cam && camera_keep_widening(*cam, &ro_add, &sigma_add) && !getenv("RTGL_AMD_NO_CAMERA_KEEP")) {
-            const size_t need = rt_scan_launch::capacity(setup).keep_count(n0);
-            if (ctx->keep0_capacity < need) ctx->keep0_valid = false;
-            RCCHK(buf_grow(ctx, ctx->d_keep0, ctx->keep0_capacity, need, need * sizeof(uint32_t)));
-            have_bits = ctx->keep0_valid && ctx->keep0_n0 == n0 && ctx->keep0_words == ctx->wb.keep_words && ctx->keep0_scene == ctx->scene_version && same_camera(ctx->keep0_params, *cam);
-            ctx->wb.keep = ctx->d_keep0;
-            if (!have_bits) { ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_params = *cam; }
-        } else { ctx->wb.keep = ctx->d_keep; ro_add = sigma_add = 0.0f; }
+        if (cached) { ctx->wb.keep = ctx->d_keep0; have_bits = ck->have_bits; ro_add = ck->ro_add; sigma_add = ck->sigma_add; }
+        else ctx->wb.keep = ctx->d_keep;
         if (L.dist == 2) {
             RCCHK(buf_grow(ctx, ctx->d_plan, ctx->plan_capacity, L.plan_need, L.plan_need));
             ctx->wb.plan_prefix = reinterpret_cast<uint32_t *>(ctx->d_plan); ctx->wb.plan_stride = L.stride;
@@ -1154,9 +1170,16 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
     if (L.cull) {
         // (a binned queue is always culled here, and never from kept bits: bounce >= 1.  Under RTGL_AMD_SORT_MOVE = 1 this launch is what
         // moves its rays out of the staging queue)
-        if (!have_bits)
-        hipLaunchKernelGGL(packet_cull_kernel, dim3(L.cull_blocks), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, setup.real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
-                           ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt_sort_move == 1));
+        if (!have_bits) {
+            hipLaunchKernelGGL(packet_cull_kernel, dim3(L.cull_blocks), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, setup.real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
+                               ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt_sort_move == 1));
+            if (cached) {
+                // the camera's bits are in the stream: from here on they serve the frames of this camera, image and scene (a frame that
+                // fails drops them again: render_batch)
+                HIPCHK(ctx, hipGetLastError());
+                ctx->keep0_valid = true; ctx->keep0_n0 = n0; ctx->keep0_words = ctx->wb.keep_words; ctx->keep0_scene = ctx->scene_version; ctx->keep0_camera = keep_camera(*cam);
+            }
+        }
         if (L.dist == 2) {
             hipLaunchKernelGGL(ctx->opt_counters ? scan_plan_kernel<true> : scan_plan_kernel<false>, dim3(L.chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
             hipLaunchKernelGGL(scan_plan_base_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->wb, L.chunks);
@@ -1200,6 +1223,12 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
         const uint32_t peak = ctx->h_counts[ctx->counts_capacity];
         if (!ctx->cand_fixed && peak > ctx->cand_region_pairs) ctx->cand_region_target = (uint32_t)std::min<uint64_t>((uint64_t)peak + peak / 4, 0xFFFFFFF0u);
     }
+    // the camera-ray bounce: from kept bits?  And then in its lean form (option "camera_lean"): a single frame of one sample, no first-hit planes
+    CameraKeep ck{};
+    const FrameParams *const cam = (B == 1 && P.samples == 1u) ? &P : nullptr;
+    if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && sc.n_tri_visits > 0 && P.max_bounce > 0) RCCHK(camera_keep_decide(ctx, n0, cam, &ck));
+    const bool lean = rt_camera_keep::lean(ck, ctx->opt_camera_lean, aov != nullptr);
+    if (lean) ctx->camera_lean_frames++;
     for (uint32_t s = 0; s < P.samples; ++s) {
         const uint32_t n_counts = ctx->counts_capacity + 1u <= 256u ? ctx->counts_capacity + 1u : 0u;      // cleared by generate_rays_kernel's first block
         if (!n_counts) HIPCHK(ctx, hipMemsetAsync(ctx->d_counts, 0, counts_bytes(ctx->counts_capacity), ctx->stream));
@@ -1212,7 +1241,8 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
         }
         for (uint32_t f = 0; f < B; ++f)
             hipLaunchKernelGGL(generate_rays_kernel, gen_grid, dim3(256), 0, ctx->stream, frames[f], im, ctx->wb, s, n0_frame,
-                               ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, f == 0 ? n_counts : 0u, f * n0_frame, B > 1 ? f << 28 : 0u, f == 0 ? n0 : 0u, f == 0 ? n_sched : 0u);
+                               ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, f == 0 ? n_counts : 0u, f * n0_frame, B > 1 ? f << 28 : 0u, f == 0 ? n0 : 0u, f == 0 ? n_sched : 0u,
+                               lean ? 1u : 0u);
         bool binned = false;                                 // the queue of the bounce about to be launched was binned
         for (uint32_t b = 0; b < P.max_bounce; ++b) {
             const int key = ctx->opt_wf_mode * 10 + ctx->opt_wf_rays;
@@ -1220,7 +1250,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
             if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_SPLIT || ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
                 if (sc.n_tri_visits > 0 && ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
                     kev_mark(ctx);
-                    { const int rc = launch_intersect_solo(ctx, sc, n0, b, binned, (B == 1 && P.samples == 1u) ? &P : nullptr); if (rc) return rc; }
+                    { const int rc = launch_intersect_solo(ctx, sc, n0, b, binned, b == 0u ? &ck : nullptr, cam); if (rc) return rc; }
                     kev_mark(ctx);
                 } else if (sc.n_tri_visits > 0) {
                     kev_mark(ctx);
@@ -1254,7 +1284,8 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     if (getenv("RTGL_AMD_HIST_FILL")) HIPCHK(ctx, hipMemsetAsync(ctx->d_sort_hist + (size_t)ctx->sort_set * set_words, 0, bins * sizeof(uint32_t), ctx->stream));      // (measurement: the fill launch per bounce that the turns replace)
                     ctx->wb.sort_hist = ctx->d_sort_hist + (size_t)ctx->sort_set * set_words;
                     ctx->wb.sort_hist_other = ctx->d_sort_hist + (size_t)(ctx->sort_set ^ 1) * set_words;
-                    launch_shade<true>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
+                    if (lean && b == 0u) launch_shade_camera<true>(ctx, n0, sc, P, im, rng_out);
+                    else launch_shade<true>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
                     hipLaunchKernelGGL(sort_sums_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     hipLaunchKernelGGL(sort_prefix_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
@@ -1262,7 +1293,8 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     else hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     HIPCHK(ctx, hipGetLastError());
                     ctx->sort_set ^= 1; ctx->sort_sets_clean = true;
-                } else launch_shade<false>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
+                } else if (lean && b == 0u) launch_shade_camera<false>(ctx, n0, sc, P, im, rng_out);
+                else launch_shade<false>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
                 binned = bin_next;
                 continue;
             }
@@ -1445,7 +1477,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
         HIPCHK(ctx, hipGetLastError());
     } else if (n0 > 0) {
         int rc = launch_wavefront(ctx, sc, frames, im, n0_frame, rng_out, ctx->opt_aov ? &aov : nullptr);
-        if (rc) return rc;
+        if (rc) { ctx->keep0_valid = false; return rc; }      // (a frame that failed half way vouches for nothing it left behind)
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     kev_mark(ctx);                                       // frame end
@@ -2383,6 +2415,9 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
     } else if (!strcmp(key, "narrow_fused")) {
         if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "narrow_fused must be 0 (narrow_phase_kernel tests the scan's survivors) or 1 (every scan wave tests its own at its end)");
         ctx->opt_narrow_fused = value;
+    } else if (!strcmp(key, "camera_lean")) {
+        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "camera_lean must be 0 (camera rays travel through queue 0 in full) or 1 (shade rebuilds them while the camera's keep bits are reused)");
+        ctx->opt_camera_lean = value;
     } else if (!strcmp(key, "frame_batch")) {
         if (value < 1 || value > (int)kBatchMax) return fail(ctx, RTGL_ERR_INVALID, "frame_batch (consecutive frames traced in one set of launches) must be 1..16");
         ctx->opt_frame_batch = value;
@@ -2449,6 +2484,8 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "scan_dynamic")) *value = ctx->opt_scan_dynamic;
     else if (!strcmp(key, "narrow_fused")) *value = ctx->opt_narrow_fused;
     else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
+    else if (!strcmp(key, "camera_lean")) *value = ctx->opt_camera_lean;
+    else if (!strcmp(key, "camera_lean_frames")) *value = (int)ctx->camera_lean_frames;      // read-only: frames of this context that took the lean camera bounce
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
     else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
     else if (!strcmp(key, "denoise_source")) *value = ctx->opt_denoise_source;
