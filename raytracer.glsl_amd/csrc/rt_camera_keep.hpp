@@ -19,9 +19,17 @@ inline bool same_camera(const Camera &a, const Camera &b)
            && std::memcmp(a.up, b.up, sizeof a.up) == 0 && std::memcmp(a.right, b.right, sizeof a.right) == 0;
 }
 
-// The rays of two frames of one camera differ by the depth-of-field jitter only: origins by at most 2 |aperture|, unit directions by at
-// most 2 |aperture| / (|focal| - |aperture|).  What packet culling adds to a granule's origin radius and direction spread so that its
-// certificates hold for every frame; false: no bound worth having (certify every frame's rays).
+// The rays of two frames of one camera differ by the depth-of-field jitter only.  Frame k has o_k = fl(pos + j_k), |j_k| <= 1.0001 |a|,
+// and d_k = normalize(fl(F - o_k)) with the focal point F = fl(pos + fl(dir f)), the same floats in every frame.  With u = 2^-24 (half an
+// ulp of 1), p = |pos| and every sum rounded per component:
+//   |o_j - o_k| <= 2.0002 |a| + 2 u (p + |a|)                                          <= ro_add
+//   |v_j - v_k| <= |o_j - o_k| + 2 u max|v|  <= 2.0002 |a| + 4 u (p + |f|)             (v = fl(F - o), |v| <= 1.26 |f|)
+//   |v_k|       >= |F - pos| - |o_k - pos| - u |v| >= |f| - 1.0001 |a| - 4 u (p + |f|)  (|dir| >= 1 - 3 u)
+//   |d_j - d_k| <= |v_j - v_k| / min |v| + the rounding of two normalisations (< 1e-6)
+// r = 8 u (p + |f|) takes the place of each 4 u (p + |f|): twice what the argument needs.  Where |f| - |a| < 4 r the quotient bounds
+// nothing worth having (a camera whose jitter is a few ulps of its position): refused like an aperture from |f| / 4 on.
+// What packet culling adds to a granule's origin radius and direction spread so that its certificates hold for every frame; false: no
+// bound worth having (certify every frame's rays).
 inline bool widening(const Camera &c, float *ro_add, float *sigma_add)
 {
     *ro_add = *sigma_add = 0.0f;
@@ -29,8 +37,10 @@ inline bool widening(const Camera &c, float *ro_add, float *sigma_add)
     const float a = std::fabs(c.aperture), f = std::fabs(c.focal);
     const float pn = std::sqrt(c.pos[0] * c.pos[0] + c.pos[1] * c.pos[1] + c.pos[2] * c.pos[2]);
     if (!(a < 0.25f * f) || !(f < 1.0e18f) || !(pn < 1.0e18f)) return false;     // (NaN included)
+    const float r = 4.76837158203125e-7f * (pn + f);     // 8 u (p + |f|)
+    if (!(f - a >= 4.0f * r)) return false;
     *ro_add = 2.0f * a * 1.001f + 1.0e-5f * (1.0f + pn);
-    *sigma_add = 2.0f * a / (f - a) * 1.001f + 4.0e-6f;
+    *sigma_add = (2.0f * a * 1.001f + r) / (f - a - r) + 4.0e-6f;
     return true;
 }
 

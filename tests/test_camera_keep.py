@@ -1,6 +1,7 @@
 """When the kept bits of the camera-ray bounce serve a frame (raytracer.glsl_amd/csrc/rt_camera_keep.hpp), without a GPU.
   * tests/cpp/camera_keep_check.cpp, built by the host compiler with the address and undefined-behaviour sanitizers and run as a child
-    process: the standing camera, every field of the key and of the camera, the frames the cache does not cover, the jitter bound.
+    process: the standing camera, every field of the key and of the camera, the frames the cache does not cover, the jitter bound
+    (its limits, the five far cameras at which its first version was too small, monotonicity in |pos|, the benchmark camera's growth).
   * rtgl_amd.hip keeps no second definition: the scan's launch and the lean camera bounce take one decision per frame."""
 import os
 import re
