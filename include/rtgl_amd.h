@@ -594,7 +594,10 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
  * strips of a rank), "camera_lean" (kernel 4, also RTGL_AMD_CAMERA_LEAN, read when a context is created: the camera-ray bounce of a frame that is culled from the keep
  * bits an earlier frame left -- same camera, image and scene, a single frame of one sample, "aov" off.  1 (default): ray generation stores only what the scan reads (origin,
  * direction, hit key) and the shade launch of that bounce rebuilds each camera ray from its queue slot instead of loading it; 0: every
- * camera ray travels through the queue in full.  Every other frame runs as with 0.  The image is the same bit for bit), "cull" (packet culling: a granule of 128 rays skips the tiles
+ * camera ray travels through the queue in full.  Every other frame runs as with 0.  The image is the same bit for bit), "shade_pass" (the wavefront kernels, also
+ * RTGL_AMD_SHADE_PASS, read when a context is created: the form of a bounce's shade launch.  1 (default): one pass, a block per 256 slots of the camera queue -- the
+ * one bound on a queue's length that the host knows exactly -- unless fewer than one block in 64 is expected to find rays; 0: every launch in grid-stride passes with a
+ * grid from the previous frames' ray counts, as before.  The image is the same bit for bit), "cull" (packet culling: a granule of 128 rays skips the tiles
  * of 10 triangles for which every one of its rays is certified to be rejected by the reference's own test: 0 off, 1 on the camera-ray
  * bounce, 2 on every bounce with the queues as they come, 3 (default) on the camera-ray bounce and on every bounce whose queue was BINNED
  * -- moved into (direction cell, origin cell) order between the bounces, which is what makes its granules coherent), "sort_min_rays"
@@ -610,7 +613,8 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
  * rtgl_device_image returns NULL when that submission fails) */
 int rtgl_set_option(rtgl_context *ctx, const char *key, int value);
 /* rtgl_get_option also answers read-only keys: "kernel_in_use" (the variant the last frame ran); "camera_lean_frames" (the frames of this
- * context that took the lean camera bounce, option "camera_lean": tells a taken path from a fallback) */
+ * context that took the lean camera bounce, option "camera_lean": tells a taken path from a fallback); "shade_pass_launches" (the shade
+ * launches of this context that made one pass, option "shade_pass") */
 int rtgl_get_option(rtgl_context *ctx, const char *key, int *value);
 /* elapsed GPU milliseconds of the last rtgl_render_frame (HIP events on the context's stream) */
 int rtgl_last_frame_ms(rtgl_context *ctx, float *ms);

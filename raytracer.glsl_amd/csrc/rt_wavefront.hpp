@@ -782,7 +782,11 @@ __device__ __forceinline__ uint32_t ray_bin_key(const WaveBuffers &wb, f3 o, f3 
 // kAov: the launch of bounce 0 of sample 0 while option "aov" is on; it also writes the first-hit planes
 // kCamera: the lean camera bounce (generate_rays_kernel) -- bounce 0 of a single frame of one sample.  The ray is rebuilt from its slot
 // with ray generation's own instructions instead of loaded; the hit key is all it reads of the queue.
-template <bool kCount, bool kSort, bool kAov, bool kCamera>
+// kStride: false -- ONE pass: block b takes slots 256 b .. 256 b + 255 and a block whose first slot lies behind the queue's end leaves at
+// once (no barrier, no atomic, no LDS), so the grid must cover every slot that can hold a ray: ceil(n0 / 256) blocks, n0 the slots of
+// queue 0, the one bound the host knows exactly (rt_shade_launch.hpp).  true -- grid-stride passes, any grid: what the loop keeps live
+// from pass to pass costs 99 VGPRs and 32 spilled scalar registers at 4 waves per SIMD, against 66-68 VGPRs, no spill and 7 waves.
+template <bool kCount, bool kSort, bool kAov, bool kCamera, bool kStride>
 __device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
                                            uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
 {
@@ -797,7 +801,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageVie
     // kSort: the 64-byte staging records of a wave's survivors (WaveBuffers::stage), assembled here and written out as whole lines.  Each
     // lane storing its own record took four store instructions that each wrote 16 bytes of every 64: shade 320 -> 380 us per C2 frame.
     __shared__ float4 s_rec[kSort ? 4 * 64 * 4 : 1];
-    for (uint32_t blk = blockIdx.x; blk * 256u < n_rays; blk += gridDim.x) {      // grid-stride, see intersect_kernel
+    for (uint32_t blk = blockIdx.x; blk * 256u < n_rays; blk += gridDim.x) {      // kStride: grid-stride, see intersect_kernel; otherwise left after one pass
     const uint32_t slot = blk * 256u + threadIdx.x;
     int cam_px = 0, cam_py = 0, cam_lrow = 0;
     const bool valid = slot < n_rays && (!kCamera || camera_slot_pixel(im, slot, cam_px, cam_py, cam_lrow));
@@ -883,9 +887,9 @@ __device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageVie
             if (i < parts) { const float4 v = s_rec[wave * 256u + i]; store_through(wb.stage + 4u * wave_base + i, v.x, v.y, v.z, v.w); }
         }
     }
-    // (the camera form is launched with a block per 256 slots of queue 0 -- its length is known on the host -- and makes one pass: what
-    // the loop keeps live from pass to pass cost it 38 to 62 spilled scalar registers and half its waves per SIMD)
-    if (kCamera) break;
+    // (one pass: the launch has a block per 256 slots of queue 0 -- its length is known on the host.  What the loop keeps live from pass
+    // to pass cost the camera form 38 to 62 spilled scalar registers and half its waves per SIMD)
+    if (!kStride) break;
     __syncthreads();                                                              // s_cnt is rewritten by the next batch
     }
     if (kCount) {
@@ -894,11 +898,20 @@ __device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageVie
     }
 }
 
+// One pass: launched with ceil(n0 / 256) blocks, never with a grid from an estimate (rt_shade_launch.hpp).
 template <bool kCount, bool kSort, bool kAov>
 __global__ void __launch_bounds__(256) shade_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
                                                     uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
 {
-    shade_body<kCount, kSort, kAov, false>(sc, P, im, wb, bounce, rng_out, counters, aov);
+    shade_body<kCount, kSort, kAov, false, false>(sc, P, im, wb, bounce, rng_out, counters, aov);
+}
+// The same body in grid-stride passes, correct with any grid: the short queues of the late bounces, where a block per 256 slots of
+// queue 0 would be a launch of empty blocks, and option "shade_pass" = 0.
+template <bool kCount, bool kSort, bool kAov>
+__global__ void __launch_bounds__(256) shade_stride_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
+                                                           uint32_t bounce, uint4 *rng_out, Counters *counters, AovView aov)
+{
+    shade_body<kCount, kSort, kAov, false, true>(sc, P, im, wb, bounce, rng_out, counters, aov);
 }
 // the shade launch of a lean camera bounce (bounce 0; no first-hit planes: the host takes the lean form only while option "aov" is off).
 // One block per 256 slots: ceil(n0 / 256) blocks, no grid stride.
@@ -906,7 +919,7 @@ template <bool kCount, bool kSort>
 __global__ void __launch_bounds__(256) shade_camera_kernel(SceneView sc, FrameParams P, ImageView im, WaveBuffers wb,
                                                            uint4 *rng_out, Counters *counters)
 {
-    shade_body<kCount, kSort, false, true>(sc, P, im, wb, 0u, rng_out, counters, AovView{});
+    shade_body<kCount, kSort, false, true, false>(sc, P, im, wb, 0u, rng_out, counters, AovView{});
 }
 
 // ---- ray binning: bin counts -> first slots (two launches), then the move staging queue -> next queue.

@@ -28,6 +28,7 @@
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
 #include "rt_scan_launch.hpp"
+#include "rt_shade_launch.hpp"
 #include "rt_camera_keep.hpp"
 
 #pragma clang fp contract(off)
@@ -243,6 +244,8 @@ struct rtgl_context {
     uint32_t *d_keep0 = nullptr; size_t keep0_capacity = 0; bool keep0_valid = false; rt_camera_keep::Camera keep0_camera{}; uint32_t keep0_n0 = 0, keep0_words = 0; uint64_t keep0_scene = 0;
     int opt_camera_lean = 1;                                // the lean camera bounce on frames that reuse those bits (option "camera_lean", RTGL_AMD_CAMERA_LEAN; rt_wavefront.hpp, generate_rays_kernel)
     uint32_t camera_lean_frames = 0;                        // frames of this context that took the lean camera bounce
+    int opt_shade_pass = 1;                                 // shade launches: 1 one pass where rt_shade_launch.hpp says so, 0 grid-stride passes everywhere (option "shade_pass", RTGL_AMD_SHADE_PASS)
+    uint32_t shade_pass_launches = 0;                       // launches of this context that took the one-pass shade_kernel
     uint64_t scene_version = 0;
     void *d_plan = nullptr; size_t plan_capacity = 0;             // planned work distribution of culled scan launches: cost prefix sums per chunk
     void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
@@ -457,6 +460,7 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     if (const char *k = getenv("RTGL_AMD_NARROW_FUSED")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_narrow_fused = v; }   // A/B of the scan's tail drain
     if (const char *k = getenv("RTGL_AMD_SORT_MOVE")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_sort_move = v; }   // A/B of ray binning's move
     if (const char *k = getenv("RTGL_AMD_CAMERA_LEAN")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_camera_lean = v; }   // A/B of the lean camera bounce
+    if (const char *k = getenv("RTGL_AMD_SHADE_PASS")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_shade_pass = v; }   // A/B of the one-pass shade launches
     *out = ctx;
     return RTGL_OK;
 }
@@ -1043,17 +1047,17 @@ static void launch_bounce(rtgl_context *ctx, const SceneView &sc, const FramePar
         hipLaunchKernelGGL((bounce_kernel<R, MODE, false, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
 }
 
-// shade_kernel of one bounce; aov as for launch_bounce
+// the shade launch of one bounce, in the form and with the grid that rt_shade_launch.hpp gives it (shade_kernel: one pass, its grid from
+// n0; shade_stride_kernel: any grid); aov as for launch_bounce
 template <bool kSort>
-static void launch_shade(rtgl_context *ctx, dim3 grid, const SceneView &sc, const FrameParams &P, const ImageView &im, uint32_t bounce, uint4 *rng_out, const AovView *aov)
+static void launch_shade(rtgl_context *ctx, const rt_shade_launch::Launch &L, const SceneView &sc, const FrameParams &P, const ImageView &im, uint32_t bounce, uint4 *rng_out, const AovView *aov)
 {
-    if (aov) {
-        if (ctx->opt_counters) hipLaunchKernelGGL((shade_kernel<true, kSort, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
-        else hipLaunchKernelGGL((shade_kernel<false, kSort, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
-    } else if (ctx->opt_counters)
-        hipLaunchKernelGGL((shade_kernel<true, kSort, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
-    else
-        hipLaunchKernelGGL((shade_kernel<false, kSort, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
+    using ShadeKernel = decltype(&shade_kernel<false, kSort, false>);
+    static const ShadeKernel kKernels[2][2][2] = {      // [one pass][counters][first-hit planes]
+        {{shade_stride_kernel<false, kSort, false>, shade_stride_kernel<false, kSort, true>}, {shade_stride_kernel<true, kSort, false>, shade_stride_kernel<true, kSort, true>}},
+        {{shade_kernel<false, kSort, false>, shade_kernel<false, kSort, true>}, {shade_kernel<true, kSort, false>, shade_kernel<true, kSort, true>}}};
+    if (L.one_pass) ctx->shade_pass_launches++;
+    hipLaunchKernelGGL(kKernels[L.one_pass][ctx->opt_counters != 0][aov != nullptr], dim3(L.blocks), dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, aov ? *aov : AovView{});
 }
 
 // shade_camera_kernel: bounce 0 of a lean frame, a block per 256 slots of queue 0 (the kernel makes one pass)
@@ -1065,8 +1069,10 @@ static void launch_shade_camera(rtgl_context *ctx, uint32_t n0, const SceneView 
     else hipLaunchKernelGGL((shade_camera_kernel<false, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
 }
 
-// Upper estimate of the rays entering `bounce`, for grid sizing only (kernels grid-stride, so a low
-// estimate costs time, never correctness): last finished frame's count + 10 % + 2048, capped by n0.
+// Estimate of the rays entering `bounce`: last finished frame's count + 10 % + 2048, capped by n0.  Usually above the count, but NOT a
+// bound: it survives upload_scene, and after a scene change the queue can be longer than an earlier scene's count + 10 % + 2048.  So it
+// sizes the grids of kernels that grid-stride only (a low estimate costs them time, never correctness) and decides what is worth doing
+// (binning); a kernel that makes one pass over its queue takes its grid from n0 (rt_shade_launch.hpp).
 static uint32_t estimate_rays(const rtgl_context *ctx, uint32_t n0, uint32_t bounce)
 {
     if (bounce == 0 || bounce >= ctx->est_counts.size()) return n0;
@@ -1267,12 +1273,12 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     }
                     kev_mark(ctx);
                 }
-                const dim3 shade_grid((estimate_rays(ctx, n0, b) + 255) / 256);
                 // ray binning: the queue of the next bounce in (direction bin, origin cell) order, where it is long enough to pay for
                 // the three small launches and the extra pass over its rays
                 const uint32_t est_next = estimate_rays(ctx, n0, b + 1u);
                 const bool bin_next = ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->opt_cull == 3 && sc.n_tri_visits > 0 && b + 1u < P.max_bounce
                                       && est_next >= (uint32_t)ctx->opt_sort_min_rays;
+                const rt_shade_launch::Launch shade = rt_shade_launch::launch(ctx->opt_shade_pass, n0, estimate_rays(ctx, n0, b), bin_next);
                 if (bin_next) {
                     // two sets of bin counters take turns: the move (sort_place_kernel or sort_scatter_kernel) zeroes the one the next binned bounce will count in
                     const size_t bins = (size_t)1 << ctx->wb.sort_bits, set_words = bins + bins / kSortSeg;
@@ -1285,7 +1291,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     ctx->wb.sort_hist = ctx->d_sort_hist + (size_t)ctx->sort_set * set_words;
                     ctx->wb.sort_hist_other = ctx->d_sort_hist + (size_t)(ctx->sort_set ^ 1) * set_words;
                     if (lean && b == 0u) launch_shade_camera<true>(ctx, n0, sc, P, im, rng_out);
-                    else launch_shade<true>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
+                    else launch_shade<true>(ctx, shade, sc, P, im, b, rng_out, aov_b);
                     hipLaunchKernelGGL(sort_sums_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     hipLaunchKernelGGL(sort_prefix_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
                     // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
@@ -1294,7 +1300,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     HIPCHK(ctx, hipGetLastError());
                     ctx->sort_set ^= 1; ctx->sort_sets_clean = true;
                 } else if (lean && b == 0u) launch_shade_camera<false>(ctx, n0, sc, P, im, rng_out);
-                else launch_shade<false>(ctx, shade_grid, sc, P, im, b, rng_out, aov_b);
+                else launch_shade<false>(ctx, shade, sc, P, im, b, rng_out, aov_b);
                 binned = bin_next;
                 continue;
             }
@@ -2418,6 +2424,9 @@ extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
     } else if (!strcmp(key, "camera_lean")) {
         if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "camera_lean must be 0 (camera rays travel through queue 0 in full) or 1 (shade rebuilds them while the camera's keep bits are reused)");
         ctx->opt_camera_lean = value;
+    } else if (!strcmp(key, "shade_pass")) {
+        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "shade_pass must be 0 (every shade launch in grid-stride passes) or 1 (one pass, a block per 256 slots of queue 0, unless the queue is expected to be all but empty)");
+        ctx->opt_shade_pass = value;
     } else if (!strcmp(key, "frame_batch")) {
         if (value < 1 || value > (int)kBatchMax) return fail(ctx, RTGL_ERR_INVALID, "frame_batch (consecutive frames traced in one set of launches) must be 1..16");
         ctx->opt_frame_batch = value;
@@ -2486,6 +2495,8 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
     else if (!strcmp(key, "camera_lean")) *value = ctx->opt_camera_lean;
     else if (!strcmp(key, "camera_lean_frames")) *value = (int)ctx->camera_lean_frames;      // read-only: frames of this context that took the lean camera bounce
+    else if (!strcmp(key, "shade_pass")) *value = ctx->opt_shade_pass;
+    else if (!strcmp(key, "shade_pass_launches")) *value = (int)ctx->shade_pass_launches;      // read-only: launches of this context that took the one-pass shade_kernel
     else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
     else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
     else if (!strcmp(key, "denoise_source")) *value = ctx->opt_denoise_source;
