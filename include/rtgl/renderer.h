@@ -510,6 +510,95 @@ public:
         if (summary) *summary = s;
         return done;
     }
+    // ---- adaptive sampling (rtgl_adaptive_*, include/rtgl_amd.h; extension): frames that trace only the 16 x 16 tiles that are still noisy.
+    // adaptive_begin() clears the image and opens a session (nullptr: the defaults, threshold 0.05, floor 0.01, min_samples 16, max_samples
+    // 1024, flags 0); adaptive_frame() renders one sample over the active tiles with the uniforms render() would send (one rand() per frame;
+    // the frame count is not advanced: a tile's own count is what the accumulation divides by); adaptive_update() estimates the tiles, sets
+    // the mask and returns the summary.  render(), reset of the image and load_state() end the session.  Each prints and returns false on failure.
+    bool adaptive_begin(const rtgl_adaptive_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        rtgl_adaptive_params p;
+        rtgl_adaptive_defaults(&p);
+        if (params) p = *params;
+        const int rc = rtgl_adaptive_begin(m_ctx, &p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool adaptive_frame()
+    {
+        if (!m_ctx) return false;
+        rtgl_frame_params p{};
+        p.time = m_time;
+        p.samples = m_samples;
+        p.max_bounce = static_cast<unsigned int>(m_bounces);
+        std::memcpy(p.background, &m_background.x, sizeof p.background);
+        p.random = rand();
+        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
+        p.use_dof = m_use_dof ? 1 : 0;
+        std::memcpy(p.camera_position, &m_camera.position.x, 12);
+        p.camera_fov = glm::radians(m_camera.fov);
+        p.camera_aperture = m_camera.aperture;
+        p.camera_focal_length = m_camera.focal_length;
+        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
+        std::memcpy(p.camera_right, &m_camera.right.x, 12);
+        std::memcpy(p.camera_up, &m_camera.up.x, 12);
+        m_last_params = p;
+        int rc = rtgl_set_frame_params(m_ctx, &p);
+        if (rc == RTGL_OK) rc = rtgl_adaptive_frame(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool adaptive_update(rtgl_adaptive_summary *summary = nullptr)
+    {
+        rtgl_adaptive_summary s{};
+        if (!m_ctx) return false;
+        const int rc = rtgl_adaptive_update(m_ctx, &s);
+        check(rc);
+        if (summary) *summary = s;
+        return rc == RTGL_OK;
+    }
+    // the mask, ceil(width / 16) x ceil(height / 16) bytes, row by row, non-zero = active; set: until the next adaptive_update()
+    bool adaptive_set_mask(const std::vector<uint8_t> &tiles)
+    {
+        if (!m_ctx || tiles.size() != (size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16)) return false;
+        const int rc = rtgl_adaptive_set_mask(m_ctx, tiles.data());
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    std::vector<uint8_t> adaptive_get_mask() const
+    {
+        if (!m_ctx) return {};
+        std::vector<uint8_t> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
+        if (rtgl_adaptive_get_mask(m_ctx, tiles.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
+    // the tile records, row by row; empty (and a message) before the first adaptive_begin()
+    std::vector<rtgl_adaptive_tile> read_adaptive_tiles() const
+    {
+        if (!m_ctx) return {};
+        std::vector<rtgl_adaptive_tile> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
+        if (rtgl_read_adaptive_tiles(m_ctx, tiles.data(), nullptr, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
+    // "render until every tile is this clean": a session of masked frames with an adaptive_update() after every check_every of them, until
+    // no tile is active (each is at or below `threshold`, a relative RMSE, or holds max_samples samples) or m_quit is set.  Returns the
+    // frames rendered; `summary` (if not null) receives the latest summary.
+    long render_adaptive(float threshold, uint32_t max_samples, uint32_t min_samples = 16, long check_every = 16, rtgl_adaptive_summary *summary = nullptr)
+    {
+        rtgl_adaptive_params p;
+        rtgl_adaptive_defaults(&p);
+        p.threshold = threshold; p.max_samples = max_samples; p.min_samples = min_samples;
+        rtgl_adaptive_summary s{};
+        long done = 0;
+        bool ok = check_every > 0 && adaptive_begin(&p) && adaptive_update(&s);
+        while (ok && !m_quit && !s.converged) {
+            for (long i = 0; ok && i < check_every; ++i, ++done) ok = adaptive_frame();
+            ok = ok && adaptive_update(&s);
+        }
+        if (summary) *summary = s;
+        return done;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

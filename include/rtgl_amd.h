@@ -584,6 +584,101 @@ int rtgl_error_reset(rtgl_context *ctx);                    /* drops the snapsho
 int rtgl_read_error_summary(rtgl_context *ctx, rtgl_error_summary *out);
 int rtgl_read_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty);
 void *rtgl_device_error_tiles(rtgl_context *ctx);
+
+/* -- adaptive sampling: frames that trace only the 16 x 16 tiles that are still noisy, with a sample count per tile.  The error estimate
+ * above tells a caller how noisy each tile is; this acts on it.  No reference counterpart.  No existing kernel changes: a masked frame is
+ * the ordinary per-bounce pipeline behind a ray generator that reads a list of 8 x 8 pixel blocks, traced as a one-frame image into a
+ * sample buffer, and a merge kernel folds that buffer into the image with the tile's own count.  DEFINED bit for bit under the rules of
+ * rtgl_error_estimate (tests/adaptive_mirror.py restates it): binary32, one rounding per operation in the order written, no contraction,
+ * correctly rounded divide, integers exact; lum and the balanced 256-leaf pairwise tree are the ones of rtgl_error_estimate.
+ *   Shapes: tiles are 16 x 16, tx = ceil(W / 16), ty = ceil(H / 16), tile index t = tx row + column.  Footprint: the pixels with
+ *   x < W/8*8 and y < H/8*8.  Blocks: the 8 x 8 pixel blocks of queue 0, row-major, blocks_x = (W/8*8) / 8; block b lies in the tile
+ *   (b / blocks_x / 2, b % blocks_x / 2).
+ *   State of a session: a count n[t] per tile, a snapshot plane S (one float per pixel) with its count m[t] per tile, a sample buffer the
+ *   size of the image, the tile records; on the host the mask active[t] and the block list: the indices of the footprint blocks that lie
+ *   in active tiles, ascending.
+ *   rtgl_adaptive_begin validates and stores the parameters, allocates what is missing, zeroes the image exactly as rtgl_clear_image does
+ *   (the error snapshot is dropped, the planes' count restarts), zeroes n, m and the records and sets every tile that holds a footprint
+ *   pixel active.
+ *   rtgl_adaptive_frame renders one frame of one sample over the active tiles.  Camera, random, max_bounce, background, environment and
+ *   DOF come from the current rtgl_frame_params; `frames` and `reset_flag` are ignored.  Slot idx of queue 0 is pixel (in & 7, in >> 3) of
+ *   block list[idx >> 6], in = idx & 63; n0 = 64 len(list).  Seeds and camera rays use absolute pixel coordinates as always: the sample of
+ *   an active pixel is bit for bit the sample the ordinary frame with the same uniforms gives that pixel, whatever the mask.  The frame is
+ *   traced as a frame with reset_flag = 1, frames = 0 into the sample buffer, which then holds x = (radiance + 0 0) / 1.  Then per
+ *   active tile t and per footprint pixel of it, with k = n[t] and prev the image:
+ *     v = (x + prev (float)k) / (float)(k + 1) per channel, alpha 1        (the accumulation's operations with frames = k)
+ *   and n[t] = k + 1.  Pixels of inactive tiles and pixels outside the footprint are not written.  With an empty list the call enqueues
+ *   nothing and returns RTGL_OK.  Frames a batching context holds are submitted first.  Where the effective kernel would be
+ *   RTGL_KERNEL_MEGA (explicit, or a scene without triangles) the frame runs RTGL_KERNEL_WAVEFRONT, and "kernel_in_use" says so.  The frame
+ *   neither uses nor leaves kept camera bits and never takes the lean camera bounce.  rtgl_last_frame_ms covers generation through merge.
+ *   rtgl_adaptive_update first runs, per tile with n > m:
+ *     m == 0: the snapshot is taken (S = lum(I) over the tile's footprint pixels, m = n); the record is {0, 0, 0, 0, n, m}: not valid.
+ *     m >= 1: c = (float)m / (float)(n - m);  per footprint pixel  Ln = lum(I);  Lm = S;  d = Ln - Lm;  den = ((Ln > 0) ? Ln : 0) + floor;
+ *       q = d / den;  e = q q  (no g factors: both means are unbiased).  The pixel COUNTS iff e - e == 0.  sum = the tree over the tile's 256
+ *       row-major indices, pixels that do not count and positions outside the footprint contributing +0;  count = the counting pixels;
+ *       mse = (sum / (float)count) c;  converged = count > 0 and mse <= threshold threshold;  count == 0: sum = mse = 0.  Then S = lum(I),
+ *       m = n.  The record is {sum, mse, count, converged, n, m}; it is VALID iff count > 0.
+ *   A tile with n == m keeps its record and its snapshot.
+ *   It then synchronises, reads the records and sets the mask:
+ *     active[t] = n < min_samples or (n < max_samples and not (valid and converged));   a tile without footprint pixels is never active.
+ *   It rebuilds and uploads the block list and fills the summary (over the tiles that hold a footprint pixel): tiles_total; tiles_active;
+ *   tiles_converged = valid and converged records; tiles_capped = n >= max_samples and not (valid and converged); blocks_active = the
+ *   list's length; samples_min, samples_max = the smallest and largest n; converged = no tile is active; samples_total = the sum of n over
+ *   the footprint's pixels; max_tile_mse = the largest mse of a valid record, 0 without one.
+ *   rtgl_adaptive_set_mask replaces the mask by an explicit one, tx x ty bytes, row by row, non-zero = active (a tile without footprint
+ *   pixels stays inactive), until the next rtgl_adaptive_update replaces it: this is also region-of-interest rendering.
+ *   rtgl_adaptive_get_mask copies the mask as it stands.  rtgl_read_adaptive_tiles (synchronises) copies the tx x ty records and stores tx
+ *   and ty where the pointers are not NULL; between updates the records are those of the latest update.  rtgl_device_adaptive_tiles: the
+ *   records on the device (valid until the context is destroyed; NULL before the first rtgl_adaptive_begin).
+ * Defaults (rtgl_adaptive_defaults): threshold 0.05, floor 0.01, min_samples 16, max_samples 1024, flags 0.
+ * RTGL_ERR_INVALID: NULL context, params or output pointer; threshold or floor not finite or not > 0; min_samples < 1; max_samples <
+ * min_samples; non-zero flags or reserved words; at rtgl_adaptive_frame: samples != 1 or max_bounce == 0 in the frame parameters.
+ * RTGL_ERR_STATE: no session (every call but begin and defaults); rtgl_adaptive_frame without frame parameters or with option "aov" or
+ * "rng_state" non-zero; a tiled or multi-device context.
+ * rtgl_render_frame, rtgl_clear_image, rtgl_write_image_f32 and rtgl_bind_device_image END the session (their own behaviour is unchanged):
+ * the image is no longer the session's.  The next rtgl_adaptive_frame is RTGL_ERR_STATE until a new rtgl_adaptive_begin.
+ * A masked frame drops the snapshot of rtgl_error_estimate, like every other writer of the image that is not a counted frame.
+ * Limits: the classic bias of stopping on an estimate (a tile stops when its noise happens to read low); a stopped tile is never
+ * re-examined; seams between tiles of different counts; the first-hit planes, RNG states, denoised, temporal and display buffers are not
+ * written by masked frames; single-device, untiled contexts only. */
+typedef struct rtgl_adaptive_params {
+    float    threshold;          /* > 0: the relative RMSE at or below which a tile stops */
+    float    floor;              /* > 0: added to the luminance a difference is taken relative to */
+    uint32_t min_samples;        /* >= 1: no tile stops below this count */
+    uint32_t max_samples;        /* >= min_samples: every tile stops at this count */
+    uint32_t flags;              /* none defined: must be 0 */
+    uint32_t reserved[3];        /* must be 0 */
+} rtgl_adaptive_params;          /* 32 bytes */
+typedef struct rtgl_adaptive_tile {
+    float    sum;
+    float    mse;
+    uint32_t count;
+    uint32_t converged;
+    uint32_t samples;            /* n */
+    uint32_t samples_snapshot;   /* m */
+    uint32_t reserved[2];
+} rtgl_adaptive_tile;            /* 32 bytes */
+typedef struct rtgl_adaptive_summary {
+    uint32_t tiles_total;        /* tiles that hold a footprint pixel */
+    uint32_t tiles_active;
+    uint32_t tiles_converged;
+    uint32_t tiles_capped;
+    uint32_t blocks_active;
+    uint32_t samples_min;
+    uint32_t samples_max;
+    uint32_t converged;          /* 1: no tile is active */
+    uint64_t samples_total;
+    float    max_tile_mse;
+    uint32_t reserved[5];
+} rtgl_adaptive_summary;         /* 64 bytes */
+int rtgl_adaptive_defaults(rtgl_adaptive_params *out);
+int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params *params);
+int rtgl_adaptive_frame(rtgl_context *ctx);
+int rtgl_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summary *summary_out);
+int rtgl_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles);
+int rtgl_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles);
+int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty);
+void *rtgl_device_adaptive_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -24,6 +24,8 @@
 #include "rt_temporal_clip.hpp"
 #include "rt_tonemap.hpp"
 #include "rt_error.hpp"
+#include "rt_adaptive.hpp"
+#include "rt_adaptive_plan.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
@@ -309,6 +311,12 @@ struct rtgl_context {
     // err_fm, err_first: the snapshot's `frames` and first_frames; err_rendered, err_fn: a frame has been rendered, and its `frames`
     float *d_err_snapshot = nullptr; uint4 *d_err_tiles = nullptr; uint32_t *d_err_summary = nullptr;
     uint64_t err_epoch = 1, err_snap_epoch = 0; int32_t err_fm = 0, err_first = 0, err_fn = 0; bool err_rendered = false, has_error = false;
+    // adaptive sampling (rt_adaptive.hpp, rt_adaptive_plan.hpp), all allocated by the first rtgl_adaptive_begin: the sample buffer a masked
+    // frame traces into, the snapshot plane, the tile records, the counts (n per tile, then m per tile) and the two lists a frame reads (the
+    // active blocks, then the active tiles).  ad_active: a session is open; the mask and the lists as they are on the device
+    float4 *d_ad_samples = nullptr; float *d_ad_snapshot = nullptr; uint4 *d_ad_records = nullptr; uint32_t *d_ad_counts = nullptr, *d_ad_lists = nullptr;
+    bool ad_active = false, has_adaptive = false; rtgl_adaptive_params ad_params{};
+    std::vector<uint8_t> ad_mask; std::vector<uint32_t> ad_blocks, ad_tiles;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -1214,8 +1222,10 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
 
 // frames.size() > 1: a batch -- every frame's camera rays are generated into its own stretch of queue 0 (n0_frame slots), everything
 // behind that sees ONE frame of n0 = B x n0_frame rays, and resolve_batch_kernel applies the frames' results to the image in order
+// masked != NULL: a masked frame of adaptive sampling (rt_adaptive.hpp) -- one frame whose queue 0 holds the n0_frame / 64 blocks of that
+// list.  The keep cache's key knows n0 and the camera but not the mask, so such a frame stays out of it: it runs as `cam == NULL` does.
 static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::vector<FrameParams> &frames, const ImageView &im, uint32_t n0_frame, uint4 *rng_out,
-                            const AovView *aov)
+                            const AovView *aov, const uint32_t *masked = nullptr)
 {
     const FrameParams &P = frames[0];
     const uint32_t B = (uint32_t)frames.size(), n0 = n0_frame * B;
@@ -1231,7 +1241,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
     }
     // the camera-ray bounce: from kept bits?  And then in its lean form (option "camera_lean"): a single frame of one sample, no first-hit planes
     CameraKeep ck{};
-    const FrameParams *const cam = (B == 1 && P.samples == 1u) ? &P : nullptr;
+    const FrameParams *const cam = (B == 1 && P.samples == 1u && !masked) ? &P : nullptr;
     if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && sc.n_tri_visits > 0 && P.max_bounce > 0) RCCHK(camera_keep_decide(ctx, n0, cam, &ck));
     const bool lean = rt_camera_keep::lean(ck, ctx->opt_camera_lean, aov != nullptr);
     if (lean) ctx->camera_lean_frames++;
@@ -1245,7 +1255,9 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
             if (words <= (size_t)gen_grid.x * 256u && !getenv("RTGL_AMD_SCHED_FILL")) n_sched = (uint32_t)words;      // (the variable: measurement of the fill launch this replaces)
             else HIPCHK(ctx, hipMemsetAsync(ctx->d_sched, 0, words * sizeof(uint32_t), ctx->stream));
         }
-        for (uint32_t f = 0; f < B; ++f)
+        if (masked)
+            hipLaunchKernelGGL(generate_rays_masked_kernel, gen_grid, dim3(256), 0, ctx->stream, P, im, ctx->wb, masked, n0_frame, ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, n_counts, n_sched);
+        else for (uint32_t f = 0; f < B; ++f)
             hipLaunchKernelGGL(generate_rays_kernel, gen_grid, dim3(256), 0, ctx->stream, frames[f], im, ctx->wb, s, n0_frame,
                                ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, f == 0 ? n_counts : 0u, f * n0_frame, B > 1 ? f << 28 : 0u, f == 0 ? n0 : 0u, f == 0 ? n_sched : 0u,
                                lean ? 1u : 0u);
@@ -1368,6 +1380,7 @@ static int flush_pending(rtgl_context *ctx)
 extern "C" int rtgl_render_frame(rtgl_context *ctx)
 {
     ENTER_NOFLUSH(ctx);
+    ctx->ad_active = false;                              // (adaptive sampling: an ordinary frame ends the session)
     if (!ctx->workers.empty()) {                         // every part's frame is submitted by its own thread; this one waits for all of them
         ctx->gathered = false;
         for (auto &w : ctx->workers) { { std::lock_guard<std::mutex> lk(w->m); w->state = PartWorker::kJob; } w->cv.notify_all(); }
@@ -1395,6 +1408,18 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
     return render_batch(ctx, std::vector<FrameParams>(1, ctx->params));
 }
 
+// the scene as the kernels see it
+static SceneView scene_view(const rtgl_context *ctx)
+{
+    SceneView sc{};
+    sc.spheres = ctx->d_spheres; sc.n_spheres = ctx->n_spheres;
+    sc.sphere_visits = ctx->d_sphere_visits; sc.n_sphere_visits = ctx->n_sphere_visits;
+    sc.materials = ctx->d_materials; sc.n_materials = ctx->n_materials;
+    sc.tri_edges = ctx->d_edges; sc.tri_planes = ctx->d_planes; sc.n_tri_visits = ctx->n_tri_visits;
+    sc.env = ctx->d_env; sc.env_w = ctx->env_w; sc.env_h = ctx->env_h; sc.env_c = ctx->env_c; sc.env_faces = ctx->env_faces;
+    return sc;
+}
+
 // one frame, or the frames of a batch in one set of launches
 static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch)
 {
@@ -1414,12 +1439,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
         ctx->visit_ids_dirty = false;
     }
 
-    SceneView sc{};
-    sc.spheres = ctx->d_spheres; sc.n_spheres = ctx->n_spheres;
-    sc.sphere_visits = ctx->d_sphere_visits; sc.n_sphere_visits = ctx->n_sphere_visits;
-    sc.materials = ctx->d_materials; sc.n_materials = ctx->n_materials;
-    sc.tri_edges = ctx->d_edges; sc.tri_planes = ctx->d_planes; sc.n_tri_visits = ctx->n_tri_visits;
-    sc.env = ctx->d_env; sc.env_w = ctx->env_w; sc.env_h = ctx->env_h; sc.env_c = ctx->env_c; sc.env_faces = ctx->env_faces;
+    const SceneView sc = scene_view(ctx);
     std::vector<FrameParams> frames(batch);
     for (FrameParams &f : frames) if (!ctx->d_env) f.use_envmap = 0;   // src/renderer.cpp:104-110: no cube map => u_use_envmap = false
     const FrameParams &P = frames[0];
@@ -1577,6 +1597,7 @@ extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     ++ctx->err_epoch;                                   // (rtgl_error_estimate: another image, the snapshot is dropped)
+    ctx->ad_active = false;                             // (adaptive sampling: ... and the session ends)
     if (!ctx->parts.empty()) {                          // scatter the rows to their owners
         ctx->gathered = false;
         std::vector<float> local;
@@ -1601,6 +1622,7 @@ extern "C" int rtgl_clear_image(rtgl_context *ctx)
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;                              // the first-hit planes' mean restarts with the next frame (their contents stay)
     ++ctx->err_epoch;                                     // (rtgl_error_estimate: the snapshot is dropped)
+    ctx->ad_active = false;                               // (adaptive sampling: the session ends)
     return RTGL_OK;
 }
 
@@ -1644,6 +1666,7 @@ extern "C" int rtgl_bind_device_image(rtgl_context *ctx, void *dptr)
     if (!ctx->parts.empty()) return fail(ctx, RTGL_ERR_STATE, "a multi-device context renders into its own per-device tile buffers");
     ctx->d_image = dptr ? (float4 *)dptr : ctx->d_image_own;
     ++ctx->err_epoch;                                     // (rtgl_error_estimate: another image, the snapshot is dropped)
+    ctx->ad_active = false;                               // (adaptive sampling: ... and the session ends)
     return RTGL_OK;
 }
 
@@ -2387,6 +2410,181 @@ extern "C" void *rtgl_device_error_tiles(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->has_error) { ctx->error = "rtgl_device_error_tiles: no rtgl_error_estimate call has succeeded on this context"; return nullptr; }
     return (void *)ctx->d_err_tiles;
+}
+
+// ---- adaptive sampling: masked frames over the tiles that are still noisy (rt_adaptive.hpp, rt_adaptive_plan.hpp) -------------------------
+extern "C" int rtgl_adaptive_defaults(rtgl_adaptive_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->threshold = 0.05f; out->floor = 0.01f; out->min_samples = 16u; out->max_samples = 1024u;
+    return RTGL_OK;
+}
+
+static_assert(sizeof(rtgl_adaptive_params) == 32 && sizeof(rtgl_adaptive_tile) == sizeof(rt_adaptive_plan::Tile) && sizeof(rtgl_adaptive_summary) == sizeof(rt_adaptive_plan::Summary)
+              && offsetof(rtgl_adaptive_summary, samples_total) == offsetof(rt_adaptive_plan::Summary, samples_total) && rt_adaptive_plan::kTile == kErrTile, "the layouts of the header");
+
+// the mask as it stands -> the two lists on the device (the active blocks, then the active tiles); synchronises: the host vectors are free again
+static int adaptive_upload_lists(rtgl_context *ctx)
+{
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    rt_adaptive_plan::build_lists(sh, ctx->ad_mask, ctx->ad_blocks, ctx->ad_tiles);
+    const size_t n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
+    if (!ctx->ad_blocks.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ad_lists, ctx->ad_blocks.data(), ctx->ad_blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->ad_tiles.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ad_lists + n_blocks, ctx->ad_tiles.data(), ctx->ad_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params *params)
+{
+    ENTER(ctx);
+    if (!params) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: params is NULL");
+    const rtgl_adaptive_params P = *params;
+    for (float v : { P.threshold, P.floor })
+        if (!std::isfinite(v) || !(v > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: threshold and floor must be finite and > 0");
+    if (P.min_samples < 1u || P.max_samples < P.min_samples) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: 1 <= min_samples <= max_samples is required");
+    if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: no flag is defined");
+    for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: reserved fields must be 0");
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_begin: a tiled or multi-device context holds strips, and the tiles are the whole picture's (out of scope): render on a single-device context");
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t px = (size_t)ctx->height * ctx->width, n_tiles = (size_t)sh.tx * sh.ty, n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
+    if ((uint64_t)n_blocks * 64ull > 0xFFFFFFF0ull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: the footprint does not fit 32-bit ray slots");
+    ctx->ad_active = false;
+    RCCHK(buf_ensure(ctx, ctx->d_ad_samples, px * sizeof(float4)));
+    RCCHK(buf_ensure(ctx, ctx->d_ad_snapshot, px * sizeof(float)));
+    RCCHK(buf_ensure(ctx, ctx->d_ad_records, n_tiles * sizeof(rtgl_adaptive_tile)));
+    RCCHK(buf_ensure(ctx, ctx->d_ad_counts, 2 * n_tiles * sizeof(uint32_t)));
+    RCCHK(buf_ensure(ctx, ctx->d_ad_lists, (n_blocks + n_tiles) * sizeof(uint32_t)));
+    // the image as rtgl_clear_image leaves it
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
+    ctx->aov_restart = true;
+    ++ctx->err_epoch;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ad_records, 0, n_tiles * sizeof(rtgl_adaptive_tile), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ad_counts, 0, 2 * n_tiles * sizeof(uint32_t), ctx->stream));
+    ctx->ad_params = P; ctx->has_adaptive = true;
+    rt_adaptive_plan::explicit_mask(sh, std::vector<uint8_t>(n_tiles, 1).data(), ctx->ad_mask);
+    RCCHK(adaptive_upload_lists(ctx));
+    ctx->ad_active = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
+    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
+    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
+    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: max_bounce must be > 0");
+    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
+    if (ctx->ad_blocks.empty()) return RTGL_OK;
+    if (ctx->visits_dirty) RCCHK(rebuild_sphere_visits(ctx));
+    if (ctx->tris_dirty) RCCHK(rebuild_triangles(ctx));
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const SceneView sc = scene_view(ctx);
+    // a one-frame image in the sample buffer: accumulate_pixel stores (radiance + 0 x 0) / 1
+    std::vector<FrameParams> frames(1, ctx->params);
+    FrameParams &P = frames[0];
+    if (!ctx->d_env) P.use_envmap = 0;
+    P.frames = 0; P.reset_flag = 1;
+    ImageView im{};
+    im.pixels = ctx->d_ad_samples; im.width = ctx->width; im.height = ctx->height;
+    im.disp_w = sh.fw; im.disp_h = sh.fh;
+    im.local_rows = ctx->local_rows; im.rank = ctx->rank; im.world = ctx->world; im.strip_rows = ctx->strip_rows;
+    if (ctx->opt_counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
+    const uint32_t n0 = (uint32_t)ctx->ad_blocks.size() * 64u;
+    // the per-bounce pipeline whatever the scene: where an ordinary frame would take the megakernel, RTGL_KERNEL_WAVEFRONT
+    const int effective = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt_kernel;
+    const int saved_kernel = ctx->opt_kernel;
+    ctx->opt_kernel = effective == RTGL_KERNEL_MEGA ? (int)RTGL_KERNEL_WAVEFRONT : effective;
+    ctx->kernel_in_use = ctx->opt_kernel;
+    int rc = ensure_wave_buffers(ctx, n0, P.max_bounce, false);
+    if (!rc) {
+        ctx->wb.batch_rad = nullptr; ctx->wb.batch_px = 0;
+        ctx->last_batch_frames = 1;
+        ctx->timing_this_frame = false;                   // (option "kernel_timing" covers ordinary frames)
+        rc = (int)hipEventRecord(ctx->ev0, ctx->stream) ? fail(ctx, RTGL_ERR_DEVICE, "hipEventRecord failed") : RTGL_OK;
+    }
+    if (!rc) {
+        rc = launch_wavefront(ctx, sc, frames, im, n0, nullptr, nullptr, ctx->d_ad_lists);
+        if (rc) ctx->keep0_valid = false;                 // (as in render_batch: a frame that failed half way vouches for nothing it left behind)
+    }
+    ctx->opt_kernel = saved_kernel;
+    if (rc) return rc;
+    AdaptiveMergeArgs a{};
+    a.image = ctx->d_image; a.samples = ctx->d_ad_samples; a.n = ctx->d_ad_counts;
+    a.tiles = ctx->d_ad_lists + (size_t)sh.blocks_x * sh.blocks_y;
+    a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh; a.tx = sh.tx;
+    hipLaunchKernelGGL(adaptive_merge_kernel, dim3((unsigned)ctx->ad_tiles.size()), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->timed = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summary *summary_out)
+{
+    ENTER(ctx);
+    if (!summary_out) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_update: summary_out is NULL");
+    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_update: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t n_tiles = (size_t)sh.tx * sh.ty;
+    AdaptiveTilesArgs a{};
+    a.image = ctx->d_image; a.snapshot = ctx->d_ad_snapshot; a.records = ctx->d_ad_records;
+    a.n = ctx->d_ad_counts; a.m = ctx->d_ad_counts + n_tiles;
+    a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh;
+    a.floor_ = ctx->ad_params.floor; a.threshold = ctx->ad_params.threshold;
+    hipLaunchKernelGGL(adaptive_tiles_kernel, dim3((unsigned)sh.tx, (unsigned)sh.ty), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<rt_adaptive_plan::Tile> records(n_tiles);
+    HIPCHK(ctx, hipMemcpyAsync(records.data(), ctx->d_ad_records, n_tiles * sizeof(rt_adaptive_plan::Tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t t = 0; t < (uint32_t)n_tiles; ++t) ctx->ad_mask[t] = rt_adaptive_plan::active(sh, t, records[t], ctx->ad_params.min_samples, ctx->ad_params.max_samples) ? 1 : 0;
+    RCCHK(adaptive_upload_lists(ctx));
+    const rt_adaptive_plan::Summary s = rt_adaptive_plan::summary(sh, records.data(), ctx->ad_mask, (uint32_t)ctx->ad_blocks.size(), ctx->ad_params.max_samples);
+    memcpy(summary_out, &s, sizeof s);
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_set_mask: tiles is NULL");
+    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_set_mask: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (frames in flight read the lists about to be replaced)
+    rt_adaptive_plan::explicit_mask(rt_adaptive_plan::shape(ctx->width, ctx->height), tiles, ctx->ad_mask);
+    return adaptive_upload_lists(ctx);
+}
+
+extern "C" int rtgl_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_get_mask: tiles is NULL");
+    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_get_mask: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    memcpy(tiles, ctx->ad_mask.data(), ctx->ad_mask.size());
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "tiles is NULL");
+    if (!ctx->has_adaptive) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context");
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_ad_records, (size_t)sh.tx * sh.ty * sizeof(rtgl_adaptive_tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tx) *tx = (uint32_t)sh.tx;
+    if (ty) *ty = (uint32_t)sh.ty;
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_adaptive_tiles(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->has_adaptive) { ctx->error = "rtgl_device_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context"; return nullptr; }
+    return (void *)ctx->d_ad_records;
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

@@ -38,6 +38,10 @@ TONEMAP_AUTO_EXPOSURE = 1
 ERROR_DEFAULTS = dict(threshold=0.05, floor=0.01, quantile_permille=950, first_frames=1, keep_snapshot=False)
 ERROR_KEEP_SNAPSHOT = 1
 ERROR_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("count", np.uint32), ("converged", np.uint32)])
+# adaptive sampling (rtgl_adaptive_*)
+ADAPTIVE_DEFAULTS = dict(threshold=0.05, floor=0.01, min_samples=16, max_samples=1024)
+ADAPTIVE_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("count", np.uint32), ("converged", np.uint32), ("samples", np.uint32),
+                                ("samples_snapshot", np.uint32), ("reserved", np.uint32, (2,))])
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -59,6 +63,8 @@ ABI_SYMBOLS = [
     "rtgl_read_tonemap_exposure", "rtgl_read_tonemap_histogram",
     "rtgl_error_defaults", "rtgl_error_estimate", "rtgl_error_reset", "rtgl_read_error_summary", "rtgl_read_error_tiles",
     "rtgl_device_error_tiles",
+    "rtgl_adaptive_defaults", "rtgl_adaptive_begin", "rtgl_adaptive_frame", "rtgl_adaptive_update", "rtgl_adaptive_set_mask",
+    "rtgl_adaptive_get_mask", "rtgl_read_adaptive_tiles", "rtgl_device_adaptive_tiles",
 ]
 
 
@@ -128,6 +134,19 @@ class CErrorSummary(C.Structure):
     _fields_ = [("valid", C.c_uint32), ("converged", C.c_uint32), ("frames_now", C.c_int32), ("frames_snapshot", C.c_int32),
                 ("tiles_valid", C.c_uint32), ("tiles_converged", C.c_uint32), ("pixels_ignored", C.c_uint32), ("scale", C.c_float),
                 ("mse", C.c_float), ("max_tile_mse", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class CAdaptiveParams(C.Structure):
+    """rtgl_adaptive_params"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class CAdaptiveSummary(C.Structure):
+    """rtgl_adaptive_summary"""
+    _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("tiles_converged", C.c_uint32), ("tiles_capped", C.c_uint32),
+                ("blocks_active", C.c_uint32), ("samples_min", C.c_uint32), ("samples_max", C.c_uint32), ("converged", C.c_uint32),
+                ("samples_total", C.c_uint64), ("max_tile_mse", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
 def build_library(force: bool = False) -> str:
@@ -208,6 +227,14 @@ def load_library() -> C.CDLL:
     L.rtgl_read_error_summary.argtypes = [vp, C.POINTER(CErrorSummary)]
     L.rtgl_read_error_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     L.rtgl_device_error_tiles.argtypes = [vp]; L.rtgl_device_error_tiles.restype = vp
+    L.rtgl_adaptive_defaults.argtypes = [C.POINTER(CAdaptiveParams)]
+    L.rtgl_adaptive_begin.argtypes = [vp, C.POINTER(CAdaptiveParams)]
+    L.rtgl_adaptive_frame.argtypes = [vp]
+    L.rtgl_adaptive_update.argtypes = [vp, C.POINTER(CAdaptiveSummary)]
+    L.rtgl_adaptive_set_mask.argtypes = [vp, vp]
+    L.rtgl_adaptive_get_mask.argtypes = [vp, vp]
+    L.rtgl_read_adaptive_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.rtgl_device_adaptive_tiles.argtypes = [vp]; L.rtgl_device_adaptive_tiles.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -589,6 +616,64 @@ class Context:
         """Device pointer of the tile records (0 before the first successful error_estimate(): see the context's last error)."""
         return int(self.lib.rtgl_device_error_tiles(self.h) or 0)
 
+    # --- adaptive sampling
+    def adaptive_begin(self, threshold=None, floor=None, min_samples=None, max_samples=None):
+        """Open a session of masked frames (rtgl_adaptive_begin): the image is cleared, every tile is active and has no sample.  None keeps
+        the library's default (ADAPTIVE_DEFAULTS)."""
+        p = CAdaptiveParams()
+        self._chk(self.lib.rtgl_adaptive_defaults(C.byref(p)))
+        for name, value in (("threshold", threshold), ("floor", floor)):
+            if value is not None:
+                setattr(p, name, float(value))
+        for name, value in (("min_samples", min_samples), ("max_samples", max_samples)):
+            if value is not None:
+                setattr(p, name, int(value))
+        self._chk(self.lib.rtgl_adaptive_begin(self.h, C.byref(p)))
+
+    def adaptive_frame(self, p: FrameParams | None = None, sync: bool = True):
+        """One frame of one sample over the active tiles (rtgl_adaptive_frame), with the parameters `p` if given."""
+        if p is not None:
+            self.set_params(p)
+        self._chk(self.lib.rtgl_adaptive_frame(self.h))
+        if sync:
+            self._chk(self.lib.rtgl_synchronize(self.h))
+
+    def adaptive_update(self) -> dict:
+        """Estimate the tiles that were sampled since their snapshot, set the mask from the records (rtgl_adaptive_update; synchronises)
+        and return the summary: ints, and max_tile_mse as np.float32."""
+        s = CAdaptiveSummary()
+        self._chk(self.lib.rtgl_adaptive_update(self.h, C.byref(s)))
+        out = {k: int(getattr(s, k)) for k in ("tiles_total", "tiles_active", "tiles_converged", "tiles_capped", "blocks_active", "samples_min",
+                                               "samples_max", "converged", "samples_total")}
+        out["max_tile_mse"] = np.frombuffer(bytes(s), np.float32)[10]      # (the bits, not a round trip through a Python float)
+        return out
+
+    def _tiles_shape(self):
+        return (self.height + 15) // 16, (self.width + 15) // 16
+
+    def adaptive_set_mask(self, tiles):
+        """An explicit mask (ty, tx), non-zero = active, until the next adaptive_update()."""
+        t = np.ascontiguousarray(np.asarray(tiles) != 0, np.uint8)
+        assert t.shape == self._tiles_shape()
+        self._chk(self.lib.rtgl_adaptive_set_mask(self.h, _ptr(t)))
+
+    def adaptive_get_mask(self) -> np.ndarray:
+        out = np.zeros(self._tiles_shape(), np.uint8)
+        self._chk(self.lib.rtgl_adaptive_get_mask(self.h, _ptr(out)))
+        return out
+
+    def read_adaptive_tiles(self) -> np.ndarray:
+        """The tile records as a structured array (ty, tx) of ADAPTIVE_TILE_DTYPE; tile row 0 = image row 0."""
+        out = np.zeros(self._tiles_shape(), ADAPTIVE_TILE_DTYPE)
+        nx, ny = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.rtgl_read_adaptive_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
+        assert (int(ny.value), int(nx.value)) == out.shape
+        return out
+
+    def device_adaptive_tiles_ptr(self) -> int:
+        """Device pointer of the tile records (0 before the first adaptive_begin(): see the context's last error)."""
+        return int(self.lib.rtgl_device_adaptive_tiles(self.h) or 0)
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -681,6 +766,21 @@ class HeadlessRenderer(FrameLoop):
             summary = self.ctx.read_error_summary()
             if summary["valid"] and summary["converged"]:
                 break
+        return done, summary
+
+    def render_adaptive(self, threshold: float, max_samples: int, min_samples: int = 16, check_every: int = 16, floor=None):
+        """Render until every tile is at or below `threshold` (a relative RMSE) or holds `max_samples` samples: a session of masked
+        frames (adaptive_begin), with the uniforms render_frame() would use (frames and reset_flag are ignored), an adaptive_update()
+        after every `check_every` of them, until no tile is active.  Returns (frames rendered, the latest summary)."""
+        if check_every < 1:
+            raise ValueError("render_adaptive: check_every must be >= 1")
+        self.ctx.adaptive_begin(threshold=threshold, floor=floor, min_samples=min_samples, max_samples=max_samples)
+        done, summary = 0, self.ctx.adaptive_update()
+        while not summary["converged"]:
+            for _ in range(check_every):
+                self.ctx.adaptive_frame(self.next_frame(), sync=False)
+                done += 1
+            summary = self.ctx.adaptive_update()
         return done, summary
 
     def read_temporal(self) -> np.ndarray:
