@@ -599,6 +599,113 @@ public:
         if (summary) *summary = s;
         return done;
     }
+    // ---- robust accumulation (rtgl_robust_*, include/rtgl_amd.h; extension): the frames dealt round-robin into bucket means, and a resolve
+    // that drops the buckets whose luminance disagrees with the others, so that a firefly does not stay in the picture with weight 1/N.
+    // robust_begin() opens a session (nullptr: the defaults, buckets 8, flags 0); robust_frame() renders one frame of one sample with the
+    // uniforms render() would send, but with frames = 0 and reset_flag = 1 (one rand() per frame; the frame count is not advanced), and
+    // folds it into the next bucket; robust_accumulate() folds the image as it stands; robust_resolve() writes the trimmed mean (nullptr:
+    // the defaults, gain 1, dest 0, flags 0) to the output plane (read_robust()) or, with dest RTGL_ROBUST_DEST_IMAGE, to the accumulation
+    // image, which denoise(), tonemap() and save_to_file() then take; robust_end() frees the planes.  Each prints and returns false on failure.
+    bool robust_begin(const rtgl_robust_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        rtgl_robust_params p;
+        rtgl_robust_defaults(&p, nullptr);
+        if (params) p = *params;
+        const int rc = rtgl_robust_begin(m_ctx, &p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_accumulate()
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_accumulate(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_frame()
+    {
+        if (!m_ctx) return false;
+        rtgl_frame_params p{};
+        p.time = m_time;
+        p.frames = 0;
+        p.samples = m_samples;
+        p.max_bounce = static_cast<unsigned int>(m_bounces);
+        std::memcpy(p.background, &m_background.x, sizeof p.background);
+        p.random = rand();
+        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
+        p.use_dof = m_use_dof ? 1 : 0;
+        std::memcpy(p.camera_position, &m_camera.position.x, 12);
+        p.camera_fov = glm::radians(m_camera.fov);
+        p.camera_aperture = m_camera.aperture;
+        p.camera_focal_length = m_camera.focal_length;
+        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
+        std::memcpy(p.camera_right, &m_camera.right.x, 12);
+        std::memcpy(p.camera_up, &m_camera.up.x, 12);
+        p.reset_flag = 1;
+        m_last_params = p;
+        int rc = rtgl_set_frame_params(m_ctx, &p);
+        if (rc == RTGL_OK) rc = rtgl_render_frame(m_ctx);
+        if (rc == RTGL_OK) rc = rtgl_robust_accumulate(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_resolve(const rtgl_robust_resolve_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        rtgl_robust_resolve_params p;
+        rtgl_robust_defaults(nullptr, &p);
+        if (params) p = *params;
+        const int rc = rtgl_robust_resolve(m_ctx, &p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_end()
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_end(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the frames folded since robust_begin(); -1 (and a message) without a session
+    long robust_frames() const
+    {
+        uint32_t n = 0;
+        if (!m_ctx) return -1;
+        if (rtgl_robust_frames(m_ctx, &n, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return -1; }
+        return (long)n;
+    }
+    // the output plane of the latest robust_resolve() with dest RTGL_ROBUST_DEST_BUFFER, RGBA32F, row 0 = bottom, a = the Gini coefficient
+    // of the pixel's bucket luminances; empty (and a message) before one
+    std::vector<float> read_robust() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_robust_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // the mean of the frames bucket j holds, RGBA32F
+    std::vector<float> read_robust_bucket(uint32_t j) const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_robust_bucket_f32(m_ctx, j, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // "a picture of `frames` samples without its fireflies": robust_begin(), `frames` times robust_frame() (or until m_quit is set), then
+    // robust_resolve().  Returns the frames rendered; with to_image the accumulation image holds the picture, otherwise read_robust() gives it.
+    long render_robust(long frames, uint32_t buckets = 8, float gain = 1.0f, bool to_image = false)
+    {
+        rtgl_robust_params p;
+        rtgl_robust_resolve_params rp;
+        rtgl_robust_defaults(&p, &rp);
+        p.buckets = buckets; rp.gain = gain; rp.dest = to_image ? RTGL_ROBUST_DEST_IMAGE : RTGL_ROBUST_DEST_BUFFER;
+        long done = 0;
+        bool ok = frames > 0 && robust_begin(&p);
+        while (ok && !m_quit && done < frames) { ok = robust_frame(); if (ok) ++done; }
+        if (ok && done > 0) robust_resolve(&rp);
+        return done;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

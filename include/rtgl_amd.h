@@ -679,6 +679,75 @@ int rtgl_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles);
 int rtgl_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles);
 int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty);
 void *rtgl_device_adaptive_tiles(rtgl_context *ctx);
+
+/* -- robust accumulation: the frames dealt round-robin into K bucket means, and a resolve that drops the buckets that disagree with the
+ * others (median of means with a Gini-adaptive trim; Buisine et al., EGSR 2021; Jung et al. 2015).  A firefly stays in a running mean with
+ * weight 1/N for the rest of the accumulation; here it stays in one bucket, and the resolve leaves that bucket out where the buckets'
+ * luminances are unequal enough.  Where they agree nothing is dropped and the result is the mean.  No reference counterpart.  The frame
+ * path, every existing kernel and every existing entry point are untouched: one streaming fold per frame, one resolve when the picture
+ * is wanted.  DEFINED bit for bit under the rules of rtgl_error_estimate (tests/robust_mirror.py restates it): binary32, one rounding per
+ * operation in the order written, no contraction, correctly rounded divide, subnormals kept, integers exact; (float) of an integer is
+ * exact here.  Where a result is a NaN is defined; the NaN's sign and payload are not.
+ *   State of a session: K planes of the context's rows (local_rows x width float4, bucket-major), one output plane of that size, the
+ *   frame count N.  All of it is allocated by rtgl_robust_begin and freed by rtgl_robust_end: a context that never begins holds none.
+ *   rtgl_robust_begin validates the parameters, allocates (a second begin restarts the session and reallocates only if K changed),
+ *   zeroes the planes and sets N = 0.
+ *   rtgl_robust_accumulate folds the accumulation image AS IT STANDS, taken as one sample x, into bucket j = N mod K, which holds
+ *   k = N div K samples, per component, x, y, z and w alike:
+ *     b' = (x + b (float)k) / (float)(k + 1)                             (the accumulation's operations with frames = k)
+ *   then N = N + 1.  The caller renders each frame with reset_flag = 1, frames = 0, so that the image holds one frame's radiance; the call
+ *   cannot check that, and folds whatever the image holds.  Frames a batching context holds are submitted first.  The image, the counters
+ *   of rtgl_error_estimate and an adaptive session are not touched.
+ *   rtgl_robust_resolve needs N >= 1.  With n_j = N div K + (j < N mod K ? 1 : 0), per pixel:
+ *     1. l_j = (0.25 r + 0.5 g) + 0.25 b of bucket j                     (lum of rtgl_error_estimate)
+ *     2. key_j = l_j if l_j is finite, else +inf
+ *     3. rank_j = the number of i != j with key_i < key_j or (key_i == key_j and i < j)
+ *     4. S = the keys added to +0 one by one in bucket order
+ *     5. A = the products (float)(2 rank_j - (K - 1)) key_j added to +0 one by one in bucket order
+ *     6. G = 1 if S is not finite; else G = 0 if not S > 0; else G = A / ((float)K S).  Then G = 1 if not G <= 1; then G = 0 if not G >= 0.
+ *     7. u = (G gain) (float)(K / 2);  t = (K - 1) / 2 if u >= (float)((K - 1) / 2), else (int)u (truncated);  t = 0 while N < K.
+ *     8. bucket j is KEPT iff n_j > 0 and t <= rank_j <= K - 1 - t.
+ *     9. W = the (float)n_j of the kept buckets added to +0 one by one in BUCKET order; C = the products (float)n_j b_j likewise, per
+ *        component, w included;  out = C / W.
+ *   G is the Gini coefficient of the bucket luminances; K / 2 G buckets go at either end, at least one (K even: two) stays.
+ *   dest = RTGL_ROBUST_DEST_BUFFER stores {out.x, out.y, out.z, G} in the output plane, which rtgl_read_robust_f32 reads; nothing else
+ *   changes.  dest = RTGL_ROBUST_DEST_IMAGE stores out, all four components, in the accumulation image and does on the host what
+ *   rtgl_write_image_f32 does: an adaptive session ends, the snapshot of rtgl_error_estimate is dropped, the first-hit planes and their
+ *   count stay as they are.  rtgl_denoise*, rtgl_tonemap and save_to_file then take the picture like any image.  The session goes on
+ *   after either.  gain = 0 is the plain weighted mean of the buckets.
+ *   rtgl_robust_end frees the planes.  rtgl_robust_frames stores N and K where the pointers are not NULL.  rtgl_read_robust_f32 copies
+ *   the output plane of the latest resolve with dest BUFFER, rtgl_read_robust_bucket_f32 the plane of one bucket (both synchronise; the
+ *   context's rows, as rtgl_read_image_f32 of a single-device context gives them).
+ * A tiled context (rtgl_create_tiled) works on its own strips: there is no neighbourhood.
+ * Defaults (rtgl_robust_defaults; either pointer may be NULL, not both): buckets 8, flags 0; gain 1, dest 0, flags 0.
+ * RTGL_ERR_INVALID: NULL context, params or output pointer (rtgl_robust_frames: both NULL); buckets not 4, 8 or 16; gain NaN, negative or
+ * infinite; dest > 1; non-zero flags or reserved words; bucket >= K.
+ * RTGL_ERR_STATE: no session (every call but begin and defaults: before the first begin and after rtgl_robust_end); rtgl_robust_resolve
+ * with N = 0; rtgl_read_robust_f32 before a resolve with dest BUFFER; rtgl_robust_accumulate after 2^32 - 1 frames; a multi-device context
+ * (rtgl_create_multi).
+ * Limits: a trimmed estimator loses energy where it trims (3-5 % on the measured firefly scenes); it is biased for N finite and
+ * consistent as N grows; the ranks are of luminance, so an outlier in hue at equal luminance passes; K = 16 with under about 4 samples
+ * per bucket trims smooth pixels too; memory is 16 (K + 1) bytes per pixel. */
+typedef struct rtgl_robust_params {
+    uint32_t buckets;            /* K: 4, 8 or 16 */
+    uint32_t flags;              /* none defined: must be 0 */
+    uint32_t reserved[6];        /* must be 0 */
+} rtgl_robust_params;            /* 32 bytes */
+typedef struct rtgl_robust_resolve_params {
+    float    gain;               /* finite, >= 0: scales the trim; 0: the weighted mean */
+    uint32_t dest;               /* RTGL_ROBUST_DEST_* */
+    uint32_t flags;              /* none defined: must be 0 */
+    uint32_t reserved[5];        /* must be 0 */
+} rtgl_robust_resolve_params;    /* 32 bytes */
+enum { RTGL_ROBUST_DEST_BUFFER = 0, RTGL_ROBUST_DEST_IMAGE = 1 };
+int rtgl_robust_defaults(rtgl_robust_params *params, rtgl_robust_resolve_params *resolve_params);
+int rtgl_robust_begin(rtgl_context *ctx, const rtgl_robust_params *params);
+int rtgl_robust_accumulate(rtgl_context *ctx);
+int rtgl_robust_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params);
+int rtgl_robust_end(rtgl_context *ctx);
+int rtgl_robust_frames(rtgl_context *ctx, uint32_t *frames, uint32_t *buckets);
+int rtgl_read_robust_f32(rtgl_context *ctx, float *rgba);
+int rtgl_read_robust_bucket_f32(rtgl_context *ctx, uint32_t bucket, float *rgba);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -26,6 +26,8 @@
 #include "rt_error.hpp"
 #include "rt_adaptive.hpp"
 #include "rt_adaptive_plan.hpp"
+#include "rt_robust.hpp"
+#include "rt_robust_plan.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
@@ -317,6 +319,10 @@ struct rtgl_context {
     float4 *d_ad_samples = nullptr; float *d_ad_snapshot = nullptr; uint4 *d_ad_records = nullptr; uint32_t *d_ad_counts = nullptr, *d_ad_lists = nullptr;
     bool ad_active = false, has_adaptive = false; rtgl_adaptive_params ad_params{};
     std::vector<uint8_t> ad_mask; std::vector<uint32_t> ad_blocks, ad_tiles;
+    // robust accumulation (rt_robust.hpp, rt_robust_plan.hpp), allocated by rtgl_robust_begin and freed by rtgl_robust_end: the rb_K bucket
+    // planes (bucket-major) and the output plane.  rb_active: a session is open; rb_N: the frames folded; rb_resolved: the output plane holds a resolve
+    float4 *d_rb_buckets = nullptr, *d_rb_out = nullptr;
+    uint32_t rb_K = 0, rb_N = 0; bool rb_active = false, rb_resolved = false;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -2585,6 +2591,130 @@ extern "C" void *rtgl_device_adaptive_tiles(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->has_adaptive) { ctx->error = "rtgl_device_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context"; return nullptr; }
     return (void *)ctx->d_ad_records;
+}
+
+// ---- robust accumulation: K bucket means and a Gini-trimmed resolve (rt_robust.hpp, rt_robust_plan.hpp) -----------------------------------
+static_assert(sizeof(rtgl_robust_params) == sizeof(rt_robust_plan::Params) && sizeof(rtgl_robust_resolve_params) == sizeof(rt_robust_plan::ResolveParams)
+              && offsetof(rtgl_robust_resolve_params, dest) == offsetof(rt_robust_plan::ResolveParams, dest) && (uint32_t)RTGL_ROBUST_DEST_BUFFER == rt_robust_plan::kDestBuffer
+              && (uint32_t)RTGL_ROBUST_DEST_IMAGE == rt_robust_plan::kDestImage, "the layouts of the header");
+
+extern "C" int rtgl_robust_defaults(rtgl_robust_params *params, rtgl_robust_resolve_params *resolve_params)
+{
+    if (!params && !resolve_params) return RTGL_ERR_INVALID;
+    if (params) { const rt_robust_plan::Params p = rt_robust_plan::default_params(); memcpy(params, &p, sizeof p); }
+    if (resolve_params) { const rt_robust_plan::ResolveParams p = rt_robust_plan::default_resolve_params(); memcpy(resolve_params, &p, sizeof p); }
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_begin(rtgl_context *ctx, const rtgl_robust_params *params)
+{
+    ENTER(ctx);
+    if (!params) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_begin: params is NULL");
+    rt_robust_plan::Params P;
+    memcpy(&P, params, sizeof P);
+    if (const char *why = rt_robust_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_begin: ") + why);
+    if (!ctx->parts.empty())
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_begin: a multi-device context holds its rows on several devices (out of scope): accumulate on a single-device or a tiled context");
+    const size_t px = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width);
+    ctx->rb_active = false;
+    if (ctx->rb_K != P.buckets) { RCCHK(buf_release(ctx, ctx->d_rb_buckets)); ctx->rb_K = 0; }
+    RCCHK(buf_ensure(ctx, ctx->d_rb_buckets, rt_robust_plan::bucket_bytes(px, P.buckets)));
+    ctx->rb_K = P.buckets;
+    RCCHK(buf_ensure(ctx, ctx->d_rb_out, rt_robust_plan::output_bytes(px)));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_buckets, 0, rt_robust_plan::bucket_bytes(px, P.buckets), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_out, 0, rt_robust_plan::output_bytes(px), ctx->stream));
+    ctx->rb_N = 0; ctx->rb_resolved = false; ctx->rb_active = true;
+    return RTGL_OK;
+}
+
+static const char *const kNoRobustSession = ": no session (rtgl_robust_begin has not been called, or rtgl_robust_end has)";
+
+extern "C" int rtgl_robust_accumulate(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_accumulate") + kNoRobustSession);
+    if (ctx->rb_N == rt_robust_plan::kMaxFrames) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_accumulate: the frame count is 32 bits wide");
+    const size_t px = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width), n = (size_t)ctx->local_rows * ctx->width;
+    if (n) {
+        hipLaunchKernelGGL(robust_accumulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4 *)ctx->d_image,
+                           ctx->d_rb_buckets + (size_t)rt_robust_plan::next_bucket(ctx->rb_N, ctx->rb_K) * px, rt_robust_plan::next_count(ctx->rb_N, ctx->rb_K), (uint32_t)n);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    ctx->rb_N++;
+    return RTGL_OK;
+}
+
+template <int K>
+static void launch_robust_resolve(rtgl_context *ctx, const RobustResolveArgs &a, bool to_image)
+{
+    const dim3 grid((unsigned)((a.n + 255u) / 256u));
+    if (to_image) hipLaunchKernelGGL((robust_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((robust_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+extern "C" int rtgl_robust_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params)
+{
+    ENTER(ctx);
+    if (!params) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_resolve: params is NULL");
+    rt_robust_plan::ResolveParams P;
+    memcpy(&P, params, sizeof P);
+    if (const char *why = rt_robust_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_resolve: ") + why);
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_resolve") + kNoRobustSession);
+    if (ctx->rb_N == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_resolve: no frame has been accumulated since rtgl_robust_begin");
+    const bool to_image = P.dest == rt_robust_plan::kDestImage;
+    if (to_image) {                                       // on the host, what rtgl_write_image_f32 does
+        ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
+        ctx->ad_active = false;                           // (adaptive sampling: ... and the session ends)
+    }
+    RobustResolveArgs a{};
+    a.buckets = ctx->d_rb_buckets; a.out = to_image ? ctx->d_image : ctx->d_rb_out;
+    a.plane = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width); a.n = (uint32_t)((size_t)ctx->local_rows * ctx->width);
+    a.frames = ctx->rb_N; a.gain = P.gain;
+    if (a.n) {
+        if (ctx->rb_K == 4u) launch_robust_resolve<4>(ctx, a, to_image);
+        else if (ctx->rb_K == 8u) launch_robust_resolve<8>(ctx, a, to_image);
+        else launch_robust_resolve<16>(ctx, a, to_image);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (!to_image) ctx->rb_resolved = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_end(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_end") + kNoRobustSession);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (folds and resolves in flight use the planes)
+    ctx->rb_active = false; ctx->rb_resolved = false; ctx->rb_K = 0; ctx->rb_N = 0;
+    return buf_release(ctx, ctx->d_rb_buckets, ctx->d_rb_out);
+}
+
+extern "C" int rtgl_robust_frames(rtgl_context *ctx, uint32_t *frames, uint32_t *buckets)
+{
+    ENTER_NOFLUSH(ctx);
+    if (!frames && !buckets) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_frames: both pointers are NULL");
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_frames") + kNoRobustSession);
+    if (frames) *frames = ctx->rb_N;
+    if (buckets) *buckets = ctx->rb_K;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_robust_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_f32") + kNoRobustSession);
+    if (!ctx->rb_resolved) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_robust_f32: no rtgl_robust_resolve with dest RTGL_ROBUST_DEST_BUFFER since rtgl_robust_begin");
+    return read_rows(ctx, rgba, ctx->d_rb_out, 16);
+}
+
+extern "C" int rtgl_read_robust_bucket_f32(rtgl_context *ctx, uint32_t bucket, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
+    if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_bucket_f32") + kNoRobustSession);
+    if (bucket >= ctx->rb_K) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_bucket_f32: bucket >= buckets");
+    return read_rows(ctx, rgba, ctx->d_rb_buckets + (size_t)bucket * rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width), 16);
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

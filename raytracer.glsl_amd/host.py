@@ -42,6 +42,9 @@ ERROR_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("count",
 ADAPTIVE_DEFAULTS = dict(threshold=0.05, floor=0.01, min_samples=16, max_samples=1024)
 ADAPTIVE_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("count", np.uint32), ("converged", np.uint32), ("samples", np.uint32),
                                 ("samples_snapshot", np.uint32), ("reserved", np.uint32, (2,))])
+# robust accumulation (rtgl_robust_*)
+ROBUST_DEFAULTS = dict(buckets=8, gain=1.0, dest=0)
+ROBUST_DEST_BUFFER, ROBUST_DEST_IMAGE = 0, 1
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -65,6 +68,8 @@ ABI_SYMBOLS = [
     "rtgl_device_error_tiles",
     "rtgl_adaptive_defaults", "rtgl_adaptive_begin", "rtgl_adaptive_frame", "rtgl_adaptive_update", "rtgl_adaptive_set_mask",
     "rtgl_adaptive_get_mask", "rtgl_read_adaptive_tiles", "rtgl_device_adaptive_tiles",
+    "rtgl_robust_defaults", "rtgl_robust_begin", "rtgl_robust_accumulate", "rtgl_robust_resolve", "rtgl_robust_end", "rtgl_robust_frames",
+    "rtgl_read_robust_f32", "rtgl_read_robust_bucket_f32",
 ]
 
 
@@ -147,6 +152,16 @@ class CAdaptiveSummary(C.Structure):
     _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("tiles_converged", C.c_uint32), ("tiles_capped", C.c_uint32),
                 ("blocks_active", C.c_uint32), ("samples_min", C.c_uint32), ("samples_max", C.c_uint32), ("converged", C.c_uint32),
                 ("samples_total", C.c_uint64), ("max_tile_mse", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class CRobustParams(C.Structure):
+    """rtgl_robust_params"""
+    _fields_ = [("buckets", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class CRobustResolveParams(C.Structure):
+    """rtgl_robust_resolve_params"""
+    _fields_ = [("gain", C.c_float), ("dest", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
 def build_library(force: bool = False) -> str:
@@ -235,6 +250,14 @@ def load_library() -> C.CDLL:
     L.rtgl_adaptive_get_mask.argtypes = [vp, vp]
     L.rtgl_read_adaptive_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     L.rtgl_device_adaptive_tiles.argtypes = [vp]; L.rtgl_device_adaptive_tiles.restype = vp
+    L.rtgl_robust_defaults.argtypes = [C.POINTER(CRobustParams), C.POINTER(CRobustResolveParams)]
+    L.rtgl_robust_begin.argtypes = [vp, C.POINTER(CRobustParams)]
+    L.rtgl_robust_accumulate.argtypes = [vp]
+    L.rtgl_robust_resolve.argtypes = [vp, C.POINTER(CRobustResolveParams)]
+    L.rtgl_robust_end.argtypes = [vp]
+    L.rtgl_robust_frames.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.rtgl_read_robust_f32.argtypes = [vp, vp]
+    L.rtgl_read_robust_bucket_f32.argtypes = [vp, u32, vp]
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -674,6 +697,51 @@ class Context:
         """Device pointer of the tile records (0 before the first adaptive_begin(): see the context's last error)."""
         return int(self.lib.rtgl_device_adaptive_tiles(self.h) or 0)
 
+    # --- robust accumulation
+    def robust_begin(self, buckets=None):
+        """Open a session of robust accumulation (rtgl_robust_begin): `buckets` zeroed bucket planes of this context's rows and no frame
+        yet.  None keeps the library's default (ROBUST_DEFAULTS)."""
+        p = CRobustParams()
+        self._chk(self.lib.rtgl_robust_defaults(C.byref(p), None))
+        if buckets is not None:
+            p.buckets = int(buckets)
+        self._chk(self.lib.rtgl_robust_begin(self.h, C.byref(p)))
+
+    def robust_accumulate(self):
+        """Fold the image as it stands, taken as one sample, into the next bucket (rtgl_robust_accumulate)."""
+        self._chk(self.lib.rtgl_robust_accumulate(self.h))
+
+    def robust_resolve(self, gain=None, dest=None):
+        """The trimmed mean of the buckets (rtgl_robust_resolve) into the output plane (dest ROBUST_DEST_BUFFER: read_robust()) or into
+        the accumulation image (ROBUST_DEST_IMAGE).  None keeps the library's default."""
+        p = CRobustResolveParams()
+        self._chk(self.lib.rtgl_robust_defaults(None, C.byref(p)))
+        if gain is not None:
+            p.gain = float(gain)
+        if dest is not None:
+            p.dest = int(dest)
+        self._chk(self.lib.rtgl_robust_resolve(self.h, C.byref(p)))
+
+    def robust_end(self):
+        self._chk(self.lib.rtgl_robust_end(self.h))
+
+    def robust_frames(self):
+        """(frames folded since robust_begin(), buckets)"""
+        n, k = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.rtgl_robust_frames(self.h, C.byref(n), C.byref(k)))
+        return int(n.value), int(k.value)
+
+    def read_robust(self) -> np.ndarray:
+        """The output plane of the latest robust_resolve() with dest ROBUST_DEST_BUFFER: this context's rows, RGB and the Gini coefficient."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_robust_f32(self.h, _ptr(out)))
+        return out
+
+    def read_robust_bucket(self, j: int) -> np.ndarray:
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_robust_bucket_f32(self.h, int(j), _ptr(out)))
+        return out
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -782,6 +850,19 @@ class HeadlessRenderer(FrameLoop):
                 done += 1
             summary = self.ctx.adaptive_update()
         return done, summary
+
+    def render_robust(self, frames: int, buckets: int = 8, gain: float = 1.0, to_image: bool = False) -> np.ndarray:
+        """`frames` one-sample frames (the uniforms render_frame() would use, with frames = 0 and reset_flag = 1) folded into `buckets`
+        bucket means (robust_begin, robust_accumulate), then the trimmed mean of the buckets (robust_resolve).  Returns the resolved
+        picture: RGB and the Gini coefficient, or with to_image the accumulation image, which then holds it.  The session stays open."""
+        if frames < 1:
+            raise ValueError("render_robust: frames must be >= 1")
+        self.ctx.robust_begin(buckets=buckets)
+        for _ in range(frames):
+            self.ctx.render(self.next_frame().replace(frames=0, reset_flag=1), sync=False)
+            self.ctx.robust_accumulate()
+        self.ctx.robust_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
+        return self.ctx.read_image() if to_image else self.ctx.read_robust()
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
