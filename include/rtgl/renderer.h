@@ -170,28 +170,12 @@ public:
     {
         (void)dt;
         if (!m_ctx) return;
-        rtgl_frame_params p{};
-        p.time = m_time;
-        p.frames = m_frames;
-        p.samples = m_samples;
-        p.max_bounce = static_cast<unsigned int>(m_bounces);
-        std::memcpy(p.background, &m_background.x, sizeof p.background);
-        p.random = rand();
-        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
-        p.use_dof = m_use_dof ? 1 : 0;
-        std::memcpy(p.camera_position, &m_camera.position.x, 12);
-        p.camera_fov = glm::radians(m_camera.fov);
-        p.camera_aperture = m_camera.aperture;
-        p.camera_focal_length = m_camera.focal_length;
-        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
-        std::memcpy(p.camera_right, &m_camera.right.x, 12);
-        std::memcpy(p.camera_up, &m_camera.up.x, 12);
-        p.reset_flag = m_reset ? 1 : 0;
+        const rtgl_frame_params p = frame_params(m_frames, m_reset ? 1 : 0);
+        record(p);
         if (m_reset) {                       // the stale frame count was already captured above
             m_reset = false;
             m_time = 0; m_frames = 0;
         }
-        m_last_params = p;
         check(rtgl_set_frame_params(m_ctx, &p));
         check(rtgl_render_frame(m_ctx));
     }
@@ -313,7 +297,11 @@ public:
     void set_background(const glm::vec3 &c) { m_background = c; }
     Camera &camera() { return m_camera; }
     rtgl_context *context() { return m_ctx; }
-    const rtgl_frame_params &last_frame_params() const { return m_last_params; }   // what the last render() uploaded
+    const rtgl_frame_params &last_frame_params() const { return m_last_params; }   // what the last frame of any kind uploaded
+    // every frame of any kind (render(), adaptive_frame(), robust_frame(), also inside run() and the render_*() loops) appends what it
+    // uploaded to `log` (extension; nullptr: stop).  The vector is the caller's and must outlive the logging.  A session frame that the
+    // library refused (no session, say) has drawn its rand() but is neither logged nor shown by last_frame_params().
+    void set_frame_params_log(std::vector<rtgl_frame_params> *log) { m_params_log = log; }
 
     // 8-bit, clamped, vertically flipped PNG named render_<W>x<H>_<unixtime>_<frames>.png (src/renderer.cpp:218-245)
     void save_to_file() const
@@ -500,9 +488,10 @@ public:
         long done = 0;
         while (m_ctx && !m_quit && done < max_frames && check_every > 0) {
             const long round = std::min(check_every, max_frames - done);
+            const long before = m_recorded;
             set_frame_budget(round);
             run();
-            done += round;
+            done += m_recorded - before;                         // (what run() rendered: SDL_QUIT cuts a round short)
             if (!error_estimate(&p)) break;
             s = read_error_summary();
             if (s.valid && s.converged) break;
@@ -513,7 +502,8 @@ public:
     // ---- adaptive sampling (rtgl_adaptive_*, include/rtgl_amd.h; extension): frames that trace only the 16 x 16 tiles that are still noisy.
     // adaptive_begin() clears the image and opens a session (nullptr: the defaults, threshold 0.05, floor 0.01, min_samples 16, max_samples
     // 1024, flags 0); adaptive_frame() renders one sample over the active tiles with the uniforms render() would send (one rand() per frame;
-    // the frame count is not advanced: a tile's own count is what the accumulation divides by); adaptive_update() estimates the tiles, sets
+    // the frame count is not advanced and a pending reset_buffer() stays pending for the next render(): a tile's own count is what the
+    // accumulation divides by); adaptive_update() estimates the tiles, sets
     // the mask and returns the summary.  render(), reset of the image and load_state() end the session.  Each prints and returns false on failure.
     bool adaptive_begin(const rtgl_adaptive_params *params = nullptr)
     {
@@ -528,24 +518,10 @@ public:
     bool adaptive_frame()
     {
         if (!m_ctx) return false;
-        rtgl_frame_params p{};
-        p.time = m_time;
-        p.samples = m_samples;
-        p.max_bounce = static_cast<unsigned int>(m_bounces);
-        std::memcpy(p.background, &m_background.x, sizeof p.background);
-        p.random = rand();
-        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
-        p.use_dof = m_use_dof ? 1 : 0;
-        std::memcpy(p.camera_position, &m_camera.position.x, 12);
-        p.camera_fov = glm::radians(m_camera.fov);
-        p.camera_aperture = m_camera.aperture;
-        p.camera_focal_length = m_camera.focal_length;
-        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
-        std::memcpy(p.camera_right, &m_camera.right.x, 12);
-        std::memcpy(p.camera_up, &m_camera.up.x, 12);
-        m_last_params = p;
+        const rtgl_frame_params p = frame_params(0, 0);        // (rtgl_adaptive_frame ignores frames and reset_flag)
         int rc = rtgl_set_frame_params(m_ctx, &p);
         if (rc == RTGL_OK) rc = rtgl_adaptive_frame(m_ctx);
+        if (rc == RTGL_OK) record(p);
         check(rc);
         return rc == RTGL_OK;
     }
@@ -593,7 +569,7 @@ public:
         long done = 0;
         bool ok = check_every > 0 && adaptive_begin(&p) && adaptive_update(&s);
         while (ok && !m_quit && !s.converged) {
-            for (long i = 0; ok && i < check_every; ++i, ++done) ok = adaptive_frame();
+            for (long i = 0; ok && i < check_every; ++i) { ok = adaptive_frame(); if (ok) ++done; }
             ok = ok && adaptive_update(&s);
         }
         if (summary) *summary = s;
@@ -602,7 +578,8 @@ public:
     // ---- robust accumulation (rtgl_robust_*, include/rtgl_amd.h; extension): the frames dealt round-robin into bucket means, and a resolve
     // that drops the buckets whose luminance disagrees with the others, so that a firefly does not stay in the picture with weight 1/N.
     // robust_begin() opens a session (nullptr: the defaults, buckets 8, flags 0); robust_frame() renders one frame of one sample with the
-    // uniforms render() would send, but with frames = 0 and reset_flag = 1 (one rand() per frame; the frame count is not advanced), and
+    // uniforms render() would send, but with frames = 0 and reset_flag = 1 (one rand() per frame; the frame count is not advanced and a
+    // pending reset_buffer() stays pending for the next render()), and
     // folds it into the next bucket; robust_accumulate() folds the image as it stands; robust_resolve() writes the trimmed mean (nullptr:
     // the defaults, gain 1, dest 0, flags 0) to the output plane (read_robust()) or, with dest RTGL_ROBUST_DEST_IMAGE, to the accumulation
     // image, which denoise(), tonemap() and save_to_file() then take; robust_end() frees the planes.  Each prints and returns false on failure.
@@ -626,26 +603,10 @@ public:
     bool robust_frame()
     {
         if (!m_ctx) return false;
-        rtgl_frame_params p{};
-        p.time = m_time;
-        p.frames = 0;
-        p.samples = m_samples;
-        p.max_bounce = static_cast<unsigned int>(m_bounces);
-        std::memcpy(p.background, &m_background.x, sizeof p.background);
-        p.random = rand();
-        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
-        p.use_dof = m_use_dof ? 1 : 0;
-        std::memcpy(p.camera_position, &m_camera.position.x, 12);
-        p.camera_fov = glm::radians(m_camera.fov);
-        p.camera_aperture = m_camera.aperture;
-        p.camera_focal_length = m_camera.focal_length;
-        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
-        std::memcpy(p.camera_right, &m_camera.right.x, 12);
-        std::memcpy(p.camera_up, &m_camera.up.x, 12);
-        p.reset_flag = 1;
-        m_last_params = p;
+        const rtgl_frame_params p = frame_params(0, 1);
         int rc = rtgl_set_frame_params(m_ctx, &p);
         if (rc == RTGL_OK) rc = rtgl_render_frame(m_ctx);
+        if (rc == RTGL_OK) record(p);                          // (the frame was rendered, whatever the fold says)
         if (rc == RTGL_OK) rc = rtgl_robust_accumulate(m_ctx);
         check(rc);
         return rc == RTGL_OK;
@@ -765,10 +726,42 @@ private:
         if (!f) { std::cerr << "Could not write " << path << std::endl; return false; }
         return true;
     }
+    // The uniforms of one frame of any kind, marshalled in one place (src/renderer.cpp:96-122): one rand() per call; the caller says what
+    // `frames` and `reset_flag` carry.
+    rtgl_frame_params frame_params(int frames, int reset_flag)
+    {
+        rtgl_frame_params p{};
+        p.time = m_time;
+        p.frames = frames;
+        p.samples = m_samples;
+        p.max_bounce = static_cast<unsigned int>(m_bounces);
+        std::memcpy(p.background, &m_background.x, sizeof p.background);
+        p.random = rand();
+        p.use_envmap = m_envmap ? (m_use_envmap ? 1 : 0) : 0;
+        p.use_dof = m_use_dof ? 1 : 0;
+        std::memcpy(p.camera_position, &m_camera.position.x, 12);
+        p.camera_fov = glm::radians(m_camera.fov);
+        p.camera_aperture = m_camera.aperture;
+        p.camera_focal_length = m_camera.focal_length;
+        std::memcpy(p.camera_forward, &m_camera.forward.x, 12);
+        std::memcpy(p.camera_right, &m_camera.right.x, 12);
+        std::memcpy(p.camera_up, &m_camera.up.x, 12);
+        p.reset_flag = reset_flag;
+        return p;
+    }
+    // a frame the library took: last_frame_params(), the log if one is set, the count render_until() goes by
+    void record(const rtgl_frame_params &p)
+    {
+        m_last_params = p;
+        if (m_params_log) m_params_log->push_back(p);
+        ++m_recorded;
+    }
     void check(int rc) const { if (rc != RTGL_OK) std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; }
 
     rtgl_context *m_ctx = nullptr;
     rtgl_frame_params m_last_params{};
+    std::vector<rtgl_frame_params> *m_params_log = nullptr;
+    long m_recorded = 0;
     std::unique_ptr<CubemapTexture> m_envmap = nullptr;
     int m_bounces = 5;
     unsigned int m_samples = 1;

@@ -766,6 +766,11 @@ class FrameLoop:
             self.m_frames = 0
         return p
 
+    def session_frame(self, reset_flag: int = 0) -> FrameParams:
+        """The uniforms of one frame of an adaptive or robust session (renderer.h's adaptive_frame() / robust_frame()): one rand(), like
+        every frame, but frames = 0, the frame count is not advanced and a pending reset stays pending for the next next_frame()."""
+        return self.params.replace(frames=0, reset_flag=reset_flag, random=self._rand.rand())
+
 
 class HeadlessRenderer(FrameLoop):
     """FrameLoop driving a Context: the Python twin of include/rtgl/renderer.h's Renderer."""
@@ -838,28 +843,30 @@ class HeadlessRenderer(FrameLoop):
 
     def render_adaptive(self, threshold: float, max_samples: int, min_samples: int = 16, check_every: int = 16, floor=None):
         """Render until every tile is at or below `threshold` (a relative RMSE) or holds `max_samples` samples: a session of masked
-        frames (adaptive_begin), with the uniforms render_frame() would use (frames and reset_flag are ignored), an adaptive_update()
-        after every `check_every` of them, until no tile is active.  Returns (frames rendered, the latest summary)."""
+        frames (adaptive_begin), with the uniforms render_frame() would use (frames and reset_flag are ignored; one rand() per frame, the
+        frame count is not advanced and a pending reset_buffer() stays pending, as in renderer.h), an adaptive_update() after every
+        `check_every` of them, until no tile is active.  Returns (frames rendered, the latest summary)."""
         if check_every < 1:
             raise ValueError("render_adaptive: check_every must be >= 1")
         self.ctx.adaptive_begin(threshold=threshold, floor=floor, min_samples=min_samples, max_samples=max_samples)
         done, summary = 0, self.ctx.adaptive_update()
         while not summary["converged"]:
             for _ in range(check_every):
-                self.ctx.adaptive_frame(self.next_frame(), sync=False)
+                self.ctx.adaptive_frame(self.session_frame(), sync=False)
                 done += 1
             summary = self.ctx.adaptive_update()
         return done, summary
 
     def render_robust(self, frames: int, buckets: int = 8, gain: float = 1.0, to_image: bool = False) -> np.ndarray:
-        """`frames` one-sample frames (the uniforms render_frame() would use, with frames = 0 and reset_flag = 1) folded into `buckets`
-        bucket means (robust_begin, robust_accumulate), then the trimmed mean of the buckets (robust_resolve).  Returns the resolved
-        picture: RGB and the Gini coefficient, or with to_image the accumulation image, which then holds it.  The session stays open."""
+        """`frames` one-sample frames (the uniforms render_frame() would use, with frames = 0 and reset_flag = 1; one rand() per frame, the
+        frame count is not advanced and a pending reset_buffer() stays pending, as in renderer.h) folded into `buckets` bucket means
+        (robust_begin, robust_accumulate), then the trimmed mean of the buckets (robust_resolve).  Returns the resolved picture: RGB and
+        the Gini coefficient, or with to_image the accumulation image, which then holds it.  The session stays open."""
         if frames < 1:
             raise ValueError("render_robust: frames must be >= 1")
         self.ctx.robust_begin(buckets=buckets)
         for _ in range(frames):
-            self.ctx.render(self.next_frame().replace(frames=0, reset_flag=1), sync=False)
+            self.ctx.render(self.session_frame(reset_flag=1), sync=False)
             self.ctx.robust_accumulate()
         self.ctx.robust_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
         return self.ctx.read_image() if to_image else self.ctx.read_robust()

@@ -149,16 +149,29 @@ def test_render_robust_of_the_headless_renderer(rt):
     for r in (a, b):
         r.set_scene(sc.scene_c1(True))
         r.params = sc.params_c1()
-    for _ in range(9):
-        b.ctx.render(b.next_frame().replace(frames=0, reset_flag=1))
+    g = sc.GlibcRand(0)
+    stream = [g.rand() for _ in range(20)]
+    for k in range(9):
+        b.ctx.render(b.params.replace(frames=0, reset_flag=1, random=stream[k]))
         sess.accumulate(b.ctx.read_image())
     got = a.render_robust(9, buckets=4, gain=2.0)
     assert same(got, sess.resolve(2.0)) and a.ctx.robust_frames() == (9, 4)
     assert same(a.ctx.read_image(), b.ctx.read_image())            # the image still holds the last frame
-    b.m_frames, b._rand = 0, sc.GlibcRand(0)
-    a.m_frames, a._rand = 0, sc.GlibcRand(0)
+    # the session drew nine words and left the loop's counters alone, as renderer.h's robust_frame() does
+    assert (a.m_frames, a.m_reset) == (0, False) and a._rand.rand() == stream[9]
+    a.reset_buffer()
+    sess2 = rm.Session(64, 64, 4)
+    for k in range(10, 19):
+        b.ctx.render(b.params.replace(frames=0, reset_flag=1, random=stream[k]))
+        sess2.accumulate(b.ctx.read_image())
     got = a.render_robust(9, buckets=4, gain=2.0, to_image=True)
-    assert same(got, sess.resolve(2.0, rm.DEST_IMAGE)) and same(a.ctx.read_image(), got)
+    assert same(got, sess2.resolve(2.0, rm.DEST_IMAGE)) and same(a.ctx.read_image(), got)
+    assert not same(sess2.resolve(2.0), sess.resolve(2.0))         # (other words, another picture)
+    assert (a.m_frames, a.m_reset) == (0, True)                     # the pending reset is still pending ...
+    p = a.render_frame()
+    assert (p.frames, p.reset_flag, p.random) == (1, 1, stream[19]) and (a.m_frames, a.m_reset) == (0, False)      # ... for the next ordinary frame
+    b.ctx.render(b.params.replace(frames=1, reset_flag=1, random=stream[19]))
+    assert same(a.ctx.read_image(), b.ctx.read_image())
     with pytest.raises(ValueError):
         a.render_robust(0)
     a.ctx.close()

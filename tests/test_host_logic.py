@@ -34,6 +34,31 @@ def test_frame_loop_follows_reference_bookkeeping(rt):
     assert [(p.frames, p.random, p.reset_flag) for p in got] == [(p.frames, p.random, p.reset_flag) for p in want]
 
 
+def test_session_frames_leave_the_frame_count_and_a_pending_reset_alone(rt):
+    """renderer.h's adaptive_frame() / robust_frame(): one rand() per session frame, the frame count not advanced, a pending reset left
+    for the next ordinary frame -- what FrameLoop uploads during and after a session, with and without a pending reset"""
+    g = rt.scenes.GlibcRand(0)
+    stream = [g.rand() for _ in range(12)]
+    for pending in (False, True):
+        loop = rt.host.FrameLoop()
+        got = [loop.next_frame() for _ in range(2)]
+        if pending:
+            loop.reset_buffer()
+        got += [loop.session_frame() for _ in range(3)]                  # an adaptive session: frames and reset_flag are not used
+        assert (loop.m_frames, loop.m_reset) == (2, pending)
+        got += [loop.session_frame(reset_flag=1) for _ in range(2)]     # a robust session
+        assert (loop.m_frames, loop.m_reset) == (2, pending)
+        got += [loop.next_frame() for _ in range(3)]
+        assert [p.random for p in got] == stream[:10]                    # one draw per frame of any kind, in order
+        after = [(3, 1), (1, 0), (2, 0)] if pending else [(3, 0), (4, 0), (5, 0)]
+        assert [(p.frames, p.reset_flag) for p in got] == [(1, 0), (2, 0)] + [(0, 0)] * 3 + [(0, 1)] * 2 + after
+        assert (loop.m_frames, loop.m_reset) == (after[-1][0], False)
+    # everything but frames, reset_flag and random is the loop's own parameters
+    loop = rt.host.FrameLoop(rt.scenes.FrameParams().replace(max_bounce=3, use_dof=0, camera_position=(1.0, 2.0, 3.0)))
+    a, b = loop.next_frame(), loop.session_frame(reset_flag=1)
+    assert a.replace(frames=0, reset_flag=1, random=b.random) == b and b.random == stream[1]
+
+
 def test_default_params_are_the_reference_defaults(rt):
     p = rt.scenes.FrameParams()
     assert (p.max_bounce, p.samples, p.use_dof, p.use_envmap) == (5, 1, 1, 1)          # renderer.h:167-175
