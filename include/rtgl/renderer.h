@@ -667,6 +667,54 @@ public:
         if (ok && done > 0) robust_resolve(&rp);
         return done;
     }
+    // ---- robust error estimate (rtgl_robust_error_estimate, include/rtgl_amd.h; extension): how noisy the picture robust_resolve() makes
+    // still is, per 16 x 16 tile and for the picture, from the spread of the open session's buckets.  nullptr: its defaults (threshold 0.05,
+    // floor 0.01, the resolve's gain 1, quantile_permille 950, flags 0).  Needs as many frames as buckets.  Prints and returns false on failure.
+    bool robust_error_estimate(const rtgl_robust_error_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_error_estimate(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the summary of the session's last robust_error_estimate() (synchronises); all zero (and a message) before the first successful one
+    rtgl_error_summary read_robust_error_summary() const
+    {
+        rtgl_error_summary s{};
+        if (m_ctx && rtgl_read_robust_error_summary(m_ctx, &s) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; s = rtgl_error_summary{}; }
+        return s;
+    }
+    // "a picture without its fireflies, this clean": robust_begin(), robust_frame() in rounds of check_every frames with a
+    // robust_error_estimate() after each round once the session holds `buckets` frames, until a summary is converged at `threshold` (a
+    // relative RMSE per tile, of the picture resolved with `gain`; floor and quantile from `params`, nullptr: the defaults), m_quit is set, a
+    // frame is refused or max_frames frames have been rendered; then robust_resolve() with the same gain.  Returns the frames rendered (a
+    // refused frame is not counted); `summary` (if not null) receives the latest summary, all zero if no estimate was made.
+    long render_robust_until(float threshold, long max_frames, long check_every = 16, uint32_t buckets = 8, float gain = 1.0f, bool to_image = false,
+                             const rtgl_robust_error_params *params = nullptr, rtgl_error_summary *summary = nullptr)
+    {
+        rtgl_robust_params p;
+        rtgl_robust_resolve_params rp;
+        rtgl_robust_error_params ep;
+        rtgl_robust_defaults(&p, &rp);
+        rtgl_robust_error_defaults(&ep);
+        if (params) ep = *params;
+        p.buckets = buckets; rp.gain = gain; rp.dest = to_image ? RTGL_ROBUST_DEST_IMAGE : RTGL_ROBUST_DEST_BUFFER;
+        ep.threshold = threshold; ep.gain = gain;
+        rtgl_error_summary s{};
+        long done = 0;
+        bool ok = max_frames > 0 && check_every > 0 && robust_begin(&p);
+        while (ok && !m_quit && done < max_frames) {
+            const long round = std::min(check_every, max_frames - done);
+            for (long k = 0; ok && !m_quit && k < round; ++k) { ok = robust_frame(); if (ok) ++done; }
+            if (!ok || done < (long)buckets) continue;
+            if (!robust_error_estimate(&ep)) break;
+            s = read_robust_error_summary();
+            if (s.valid && s.converged) break;
+        }
+        if (done > 0 && m_ctx) robust_resolve(&rp);
+        if (summary) *summary = s;
+        return done;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

@@ -748,6 +748,58 @@ int rtgl_robust_end(rtgl_context *ctx);
 int rtgl_robust_frames(rtgl_context *ctx, uint32_t *frames, uint32_t *buckets);
 int rtgl_read_robust_f32(rtgl_context *ctx, float *rgba);
 int rtgl_read_robust_bucket_f32(rtgl_context *ctx, uint32_t bucket, float *rgba);
+
+/* -- robust error estimate: the noise level of the picture rtgl_robust_resolve makes, and the stop rule of a robust session.  The K
+ * buckets of an open session are K independent estimates of every pixel; their spread, taken over the buckets the resolve keeps, is an
+ * estimate of the noise of the picture the resolve makes (Yuen's standard error of a trimmed mean: the variance of the WINSORIZED
+ * luminances over h (h - 1), h the buckets kept).  rtgl_error_estimate needs an accumulating image and cannot serve a session, whose
+ * image is reset every frame.  No reference counterpart.  Every existing kernel and entry point is untouched.  DEFINED bit for bit under
+ * the rules of rtgl_error_estimate (tests/robust_error_mirror.py restates it): binary32, one rounding per operation in the order written,
+ * no contraction, correctly rounded divide, subnormals kept, integers exact.  rtgl_error_summary and rtgl_error_tile are reused as they
+ * are; footprint, tiles, lum and the balanced 256-leaf pairwise tree are those of rtgl_error_estimate.
+ *   Per footprint pixel, with K, N and the bucket planes of the open session:
+ *     1. steps 1-7 of rtgl_robust_resolve with THIS call's gain: key_j, rank_j, S, A, G, t
+ *     2. lo = the key of the bucket with rank t;  hi = the key of the bucket with rank K - 1 - t
+ *     3. w_j = min(max(key_j, lo), hi)                                   (the winsorized keys)
+ *     4. M = the w_j added to +0 one by one in bucket order;  mw = M / (float)K
+ *     5. D = the squares (w_j - mw) (w_j - mw) added to +0 one by one in bucket order
+ *     6. T = the key_j of the kept buckets (t <= rank_j <= K - 1 - t) added to +0 one by one in bucket order
+ *     7. h = K - 2 t;  mu = T / (float)h;  v = D / (float)(h (h - 1))    (with t = 0 the textbook s^2 / K)
+ *     8. den = ((mu > 0) ? mu : 0) + floor;  e = v / (den den)
+ *     9. the pixel COUNTS iff e - e == 0
+ *   h >= 2 always: K is even and t is at most (K - 1) / 2.  The buckets are taken as EQUALLY weighted: their sample counts differ by at
+ *   most one (n_j of rtgl_robust_resolve), and mu is the plain mean of the kept keys, not the resolve's weighted one.
+ *   Per tile: sum = the e of the pixels that count by the tree (the others and positions outside the footprint: +0), count,
+ *   mse = sum / (float)count (there is no scale: c = 1), converged = count > 0 and mse <= threshold threshold; a tile with count == 0
+ *   has the record {0, 0, 0, 0}.
+ *   Whole picture: the solve of rtgl_error_estimate with c = 1 and valid = 1.  The summary carries frames_now = (int32_t)N,
+ *   frames_snapshot = 0 and scale = 1.
+ *   State: the tile records and the summary are buffers of the SESSION, allocated by its first estimate and freed by rtgl_robust_end; a
+ *   second rtgl_robust_begin keeps the memory, and the read-outs wait for the new session's first estimate.  The call writes nothing else:
+ *   the buckets, the output plane, the image, the first-hit planes, the snapshot and the records of rtgl_error_estimate and an adaptive
+ *   session are only read or not touched.  It submits held frames first, enqueues on the context's stream and returns without waiting;
+ *   rtgl_read_robust_error_summary and rtgl_read_robust_error_tiles synchronise (the latter copies tx x ty records and stores tx and ty
+ *   where the pointers are not NULL).  rtgl_device_robust_error_tiles: the records on the device, valid until rtgl_robust_end.
+ * Defaults (rtgl_robust_error_defaults; rtgl_robust_error_estimate with params NULL): threshold 0.05, floor 0.01, gain 1, quantile 950, flags 0.
+ * RTGL_ERR_INVALID: NULL context or output pointer; threshold or floor not finite or not > 0; gain NaN, negative or infinite;
+ * quantile_permille outside 1..1000; non-zero flags or reserved words.
+ * RTGL_ERR_STATE: no session; N < K (an empty bucket has no luminance); a tiled or multi-device context (a strip is not the picture); the
+ * read-outs before the first successful estimate of the session (rtgl_device_robust_error_tiles: NULL).
+ * Limits: luminance only; on firefly scenes the estimate reads LOW at small N (a firefly not yet drawn is in no bucket); K = 16 is
+ * unreliable below about 16 samples per bucket; the bias of the trim itself is not seen; equal bucket weights are assumed. */
+typedef struct rtgl_robust_error_params {
+    float    threshold;          /* > 0, finite: relative RMSE a tile must be at or below */
+    float    floor;              /* > 0, finite */
+    float    gain;               /* finite, >= 0: the resolve's gain; the estimate is of THAT picture */
+    uint32_t quantile_permille;  /* 1..1000 */
+    uint32_t flags;              /* none defined: must be 0 */
+    uint32_t reserved[3];        /* must be 0 */
+} rtgl_robust_error_params;      /* 32 bytes */
+int rtgl_robust_error_defaults(rtgl_robust_error_params *out);
+int rtgl_robust_error_estimate(rtgl_context *ctx, const rtgl_robust_error_params *params);
+int rtgl_read_robust_error_summary(rtgl_context *ctx, rtgl_error_summary *out);
+int rtgl_read_robust_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty);
+void *rtgl_device_robust_error_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

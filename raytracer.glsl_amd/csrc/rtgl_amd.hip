@@ -28,6 +28,8 @@
 #include "rt_adaptive_plan.hpp"
 #include "rt_robust.hpp"
 #include "rt_robust_plan.hpp"
+#include "rt_spread.hpp"
+#include "rt_spread_plan.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
@@ -323,6 +325,9 @@ struct rtgl_context {
     // planes (bucket-major) and the output plane.  rb_active: a session is open; rb_N: the frames folded; rb_resolved: the output plane holds a resolve
     float4 *d_rb_buckets = nullptr, *d_rb_out = nullptr;
     uint32_t rb_K = 0, rb_N = 0; bool rb_active = false, rb_resolved = false;
+    // rtgl_robust_error_estimate (rt_spread.hpp, rt_spread_plan.hpp): the tile records and the summary of the session, allocated by its
+    // first estimate and freed by rtgl_robust_end.  has_rb_error: an estimate of THIS session has succeeded
+    uint4 *d_rbe_tiles = nullptr; uint32_t *d_rbe_summary = nullptr; bool has_rb_error = false;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -2623,7 +2628,7 @@ extern "C" int rtgl_robust_begin(rtgl_context *ctx, const rtgl_robust_params *pa
     RCCHK(buf_ensure(ctx, ctx->d_rb_out, rt_robust_plan::output_bytes(px)));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_buckets, 0, rt_robust_plan::bucket_bytes(px, P.buckets), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_out, 0, rt_robust_plan::output_bytes(px), ctx->stream));
-    ctx->rb_N = 0; ctx->rb_resolved = false; ctx->rb_active = true;
+    ctx->rb_N = 0; ctx->rb_resolved = false; ctx->has_rb_error = false; ctx->rb_active = true;      // (the records of rtgl_robust_error_estimate stay allocated)
     return RTGL_OK;
 }
 
@@ -2685,8 +2690,8 @@ extern "C" int rtgl_robust_end(rtgl_context *ctx)
     ENTER(ctx);
     if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_end") + kNoRobustSession);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (folds and resolves in flight use the planes)
-    ctx->rb_active = false; ctx->rb_resolved = false; ctx->rb_K = 0; ctx->rb_N = 0;
-    return buf_release(ctx, ctx->d_rb_buckets, ctx->d_rb_out);
+    ctx->rb_active = false; ctx->rb_resolved = false; ctx->has_rb_error = false; ctx->rb_K = 0; ctx->rb_N = 0;
+    return buf_release(ctx, ctx->d_rb_buckets, ctx->d_rb_out, ctx->d_rbe_tiles, ctx->d_rbe_summary);
 }
 
 extern "C" int rtgl_robust_frames(rtgl_context *ctx, uint32_t *frames, uint32_t *buckets)
@@ -2715,6 +2720,82 @@ extern "C" int rtgl_read_robust_bucket_f32(rtgl_context *ctx, uint32_t bucket, f
     if (!ctx->rb_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_bucket_f32") + kNoRobustSession);
     if (bucket >= ctx->rb_K) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_bucket_f32: bucket >= buckets");
     return read_rows(ctx, rgba, ctx->d_rb_buckets + (size_t)bucket * rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width), 16);
+}
+
+// ---- rtgl_robust_error_estimate: the noise level of the picture a session's resolve makes (rt_spread.hpp, rt_spread_plan.hpp) -------------
+static_assert(sizeof(rtgl_robust_error_params) == sizeof(rt_spread_plan::Params) && offsetof(rtgl_robust_error_params, quantile_permille) == offsetof(rt_spread_plan::Params, quantile_permille)
+              && rt_spread_plan::kSummaryBytes == kErrSummaryWords * 4 && rt_spread_plan::kRecordBytes == sizeof(uint4) && rt_spread_plan::kTile == (uint32_t)kErrTile, "the layouts of the header");
+
+extern "C" int rtgl_robust_error_defaults(rtgl_robust_error_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    const rt_spread_plan::Params p = rt_spread_plan::default_params();
+    memcpy(out, &p, sizeof p);
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_error_estimate(rtgl_context *ctx, const rtgl_robust_error_params *params)
+{
+    ENTER(ctx);
+    rt_spread_plan::Params P = rt_spread_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_spread_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_error_estimate: ") + why);
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_error_estimate: a tiled or multi-device context holds strips, and the estimate is of the whole picture (out of scope): render on a single-device context");
+    if (const char *why = rt_spread_plan::refused(ctx->rb_active, ctx->rb_N, ctx->rb_K)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_error_estimate: ") + why);
+    if (!rt_spread_plan::footprint_fits(ctx->width, ctx->height)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_error_estimate: the footprint does not fit 32-bit counts");
+    const unsigned tx = rt_spread_plan::tiles_along(ctx->width), ty = rt_spread_plan::tiles_along(ctx->height);
+    RCCHK(buf_ensure(ctx, ctx->d_rbe_tiles, rt_spread_plan::record_bytes(ctx->width, ctx->height)));
+    RCCHK(buf_ensure(ctx, ctx->d_rbe_summary, rt_spread_plan::kSummaryBytes));
+    SpreadTilesArgs a{};
+    a.buckets = ctx->d_rb_buckets; a.tiles = ctx->d_rbe_tiles; a.plane = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width);
+    a.width = ctx->width; a.fw = (int32_t)rt_spread_plan::footprint_side(ctx->width); a.fh = (int32_t)rt_spread_plan::footprint_side(ctx->height);
+    a.gain = P.gain; a.floor_ = P.floor; a.threshold = P.threshold;
+    ErrorSolveArgs s{};
+    s.tiles = ctx->d_rbe_tiles; s.summary = ctx->d_rbe_summary; s.n_tiles = tx * ty; s.valid = 1u;
+    s.frames_now = (int32_t)ctx->rb_N; s.frames_snapshot = 0;
+    s.footprint = (uint32_t)rt_spread_plan::footprint(ctx->width, ctx->height); s.quantile_permille = P.quantile_permille; s.c = 1.0f;
+    const dim3 grid(tx, ty);
+    if (ctx->rb_K == 4u) hipLaunchKernelGGL(spread_tiles_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
+    else if (ctx->rb_K == 8u) hipLaunchKernelGGL(spread_tiles_kernel<8>, grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(spread_tiles_kernel<16>, grid, dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(error_solve_kernel, dim3(1), dim3(256), 0, ctx->stream, s);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_rb_error = true;
+    return RTGL_OK;
+}
+
+static const char *const kNoRobustError = ": no rtgl_robust_error_estimate call has succeeded in this session";
+
+extern "C" int rtgl_read_robust_error_summary(rtgl_context *ctx, rtgl_error_summary *out)
+{
+    ENTER(ctx);
+    if (!out) return fail(ctx, RTGL_ERR_INVALID, "out is NULL");
+    if (!ctx->rb_active || !ctx->has_rb_error) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_error_summary") + kNoRobustError);
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_rbe_summary, sizeof *out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_read_robust_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "tiles is NULL");
+    if (!ctx->rb_active || !ctx->has_rb_error) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_error_tiles") + kNoRobustError);
+    const uint32_t nx = rt_spread_plan::tiles_along(ctx->width), ny = rt_spread_plan::tiles_along(ctx->height);
+    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_rbe_tiles, (size_t)nx * ny * sizeof(rtgl_error_tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tx) *tx = nx;
+    if (ty) *ty = ny;
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_robust_error_tiles(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->rb_active || !ctx->has_rb_error) { ctx->error = std::string("rtgl_device_robust_error_tiles") + kNoRobustError; return nullptr; }
+    return (void *)ctx->d_rbe_tiles;
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

@@ -45,6 +45,8 @@ ADAPTIVE_TILE_DTYPE = np.dtype([("sum", np.float32), ("mse", np.float32), ("coun
 # robust accumulation (rtgl_robust_*)
 ROBUST_DEFAULTS = dict(buckets=8, gain=1.0, dest=0)
 ROBUST_DEST_BUFFER, ROBUST_DEST_IMAGE = 0, 1
+# rtgl_robust_error_estimate
+ROBUST_ERROR_DEFAULTS = dict(threshold=0.05, floor=0.01, gain=1.0, quantile_permille=950)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -70,6 +72,8 @@ ABI_SYMBOLS = [
     "rtgl_adaptive_get_mask", "rtgl_read_adaptive_tiles", "rtgl_device_adaptive_tiles",
     "rtgl_robust_defaults", "rtgl_robust_begin", "rtgl_robust_accumulate", "rtgl_robust_resolve", "rtgl_robust_end", "rtgl_robust_frames",
     "rtgl_read_robust_f32", "rtgl_read_robust_bucket_f32",
+    "rtgl_robust_error_defaults", "rtgl_robust_error_estimate", "rtgl_read_robust_error_summary", "rtgl_read_robust_error_tiles",
+    "rtgl_device_robust_error_tiles",
 ]
 
 
@@ -162,6 +166,12 @@ class CRobustParams(C.Structure):
 class CRobustResolveParams(C.Structure):
     """rtgl_robust_resolve_params"""
     _fields_ = [("gain", C.c_float), ("dest", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class CRobustErrorParams(C.Structure):
+    """rtgl_robust_error_params"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("gain", C.c_float), ("quantile_permille", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
 
 
 def build_library(force: bool = False) -> str:
@@ -258,6 +268,11 @@ def load_library() -> C.CDLL:
     L.rtgl_robust_frames.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.rtgl_read_robust_f32.argtypes = [vp, vp]
     L.rtgl_read_robust_bucket_f32.argtypes = [vp, u32, vp]
+    L.rtgl_robust_error_defaults.argtypes = [C.POINTER(CRobustErrorParams)]
+    L.rtgl_robust_error_estimate.argtypes = [vp, C.POINTER(CRobustErrorParams)]
+    L.rtgl_read_robust_error_summary.argtypes = [vp, C.POINTER(CErrorSummary)]
+    L.rtgl_read_robust_error_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.rtgl_device_robust_error_tiles.argtypes = [vp]; L.rtgl_device_robust_error_tiles.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -616,15 +631,19 @@ class Context:
         """Drop the snapshot: the next error_estimate() takes a new one."""
         self._chk(self.lib.rtgl_error_reset(self.h))
 
+    @staticmethod
+    def _summary_dict(s: CErrorSummary) -> dict:
+        out = {k: int(getattr(s, k)) for k in ("valid", "converged", "frames_now", "frames_snapshot", "tiles_valid", "tiles_converged", "pixels_ignored")}
+        raw = np.frombuffer(bytes(s), np.float32)                      # (the bits, not a round trip through a Python float)
+        out.update(scale=raw[7], mse=raw[8], max_tile_mse=raw[9])
+        return out
+
     def read_error_summary(self) -> dict:
         """The summary of the last error_estimate() (synchronises): valid, converged, frames_now, frames_snapshot, tiles_valid,
         tiles_converged, pixels_ignored as int, scale, mse, max_tile_mse as np.float32."""
         s = CErrorSummary()
         self._chk(self.lib.rtgl_read_error_summary(self.h, C.byref(s)))
-        out = {k: int(getattr(s, k)) for k in ("valid", "converged", "frames_now", "frames_snapshot", "tiles_valid", "tiles_converged", "pixels_ignored")}
-        raw = np.frombuffer(bytes(s), np.float32)                      # (the bits, not a round trip through a Python float)
-        out.update(scale=raw[7], mse=raw[8], max_tile_mse=raw[9])
-        return out
+        return self._summary_dict(s)
 
     def read_error_tiles(self) -> np.ndarray:
         """The tile records of the last error_estimate() as a structured array (ty, tx) of ERROR_TILE_DTYPE; tile row 0 = image row 0."""
@@ -741,6 +760,40 @@ class Context:
         out = np.zeros((self.local_rows, self.width, 4), np.float32)
         self._chk(self.lib.rtgl_read_robust_bucket_f32(self.h, int(j), _ptr(out)))
         return out
+
+    # --- robust error estimate
+    def robust_error_estimate(self, threshold=None, floor=None, gain=None, quantile_permille=None):
+        """Enqueue the error estimate of the open robust session (rtgl_robust_error_estimate; does not wait): the relative MSE of the
+        luminance of the picture robust_resolve(gain=gain) makes, per 16 x 16 tile and for the picture, from the spread of the buckets, and
+        whether `quantile_permille` of the tiles are at or below `threshold` (a relative RMSE).  Needs at least as many frames as buckets.
+        None keeps the library's default (ROBUST_ERROR_DEFAULTS)."""
+        p = CRobustErrorParams()
+        self._chk(self.lib.rtgl_robust_error_defaults(C.byref(p)))
+        for name, value in (("threshold", threshold), ("floor", floor), ("gain", gain)):
+            if value is not None:
+                setattr(p, name, float(value))
+        if quantile_permille is not None:
+            p.quantile_permille = int(quantile_permille)
+        self._chk(self.lib.rtgl_robust_error_estimate(self.h, C.byref(p)))
+
+    def read_robust_error_summary(self) -> dict:
+        """The summary of the session's last robust_error_estimate() (synchronises), with the fields of read_error_summary():
+        frames_now is the session's frame count, frames_snapshot 0 and scale 1."""
+        s = CErrorSummary()
+        self._chk(self.lib.rtgl_read_robust_error_summary(self.h, C.byref(s)))
+        return self._summary_dict(s)
+
+    def read_robust_error_tiles(self) -> np.ndarray:
+        """The tile records of the session's last robust_error_estimate() as a structured array (ty, tx) of ERROR_TILE_DTYPE."""
+        out = np.zeros(self._tiles_shape(), ERROR_TILE_DTYPE)
+        nx, ny = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.rtgl_read_robust_error_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
+        assert (int(ny.value), int(nx.value)) == out.shape
+        return out
+
+    def device_robust_error_tiles_ptr(self) -> int:
+        """Device pointer of those records (0 before the session's first successful robust_error_estimate(): see the context's last error)."""
+        return int(self.lib.rtgl_device_robust_error_tiles(self.h) or 0)
 
 
 class FrameLoop:
@@ -870,6 +923,35 @@ class HeadlessRenderer(FrameLoop):
             self.ctx.robust_accumulate()
         self.ctx.robust_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
         return self.ctx.read_image() if to_image else self.ctx.read_robust()
+
+    def robust_error_estimate(self, **params):
+        self.ctx.robust_error_estimate(**params)
+
+    def read_robust_error_summary(self) -> dict:
+        return self.ctx.read_robust_error_summary()
+
+    def render_robust_until(self, threshold: float, max_frames: int, check_every: int = 16, buckets: int = 8, gain: float = 1.0, to_image: bool = False, **params):
+        """Render a robust session until its resolved picture is this clean: session frames as render_robust() makes them, a
+        robust_error_estimate(threshold=threshold, gain=gain, **params) after every `check_every` of them once the session holds at
+        least `buckets` frames (and after the last one), stopping at the first converged summary or after `max_frames` frames; then the
+        resolve with the same gain.  Returns (frames rendered, the latest summary or None if no estimate was possible, the resolved
+        picture as render_robust() returns it).  The session stays open."""
+        if max_frames < 1 or check_every < 1:
+            raise ValueError("render_robust_until: max_frames and check_every must be >= 1")
+        self.ctx.robust_begin(buckets=buckets)
+        done, summary = 0, None
+        while done < max_frames:
+            for _ in range(min(check_every, max_frames - done)):
+                self.ctx.render(self.session_frame(reset_flag=1), sync=False)
+                self.ctx.robust_accumulate()
+                done += 1
+            if done >= buckets:
+                self.ctx.robust_error_estimate(threshold=threshold, gain=gain, **params)
+                summary = self.ctx.read_robust_error_summary()
+                if summary["valid"] and summary["converged"]:
+                    break
+        self.ctx.robust_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
+        return done, summary, (self.ctx.read_image() if to_image else self.ctx.read_robust())
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
