@@ -33,6 +33,10 @@ typedef enum rtgl_status {
     RTGL_ERR_NO_DEVICE = -3, /* no usable gfx950 device: the library has no CPU fallback */
     RTGL_ERR_STATE = -4      /* call not valid in the current state */
 } rtgl_status;
+/* Order of the checks: a call that is wrong in its arguments AND in the state of the context reports the arguments (RTGL_ERR_INVALID): every
+ * entry point checks its parameters before it looks at the context.  Two checks need the context and come after its state: n < 1 of
+ * rtgl_error_estimate (F_n is known only once a frame has been rendered) and samples / max_bounce of rtgl_adaptive_frame.  A post-process
+ * call (rtgl_denoise and everything below it in this header) that is refused changes nothing: no buffer, no option, no session, no snapshot. */
 
 /* The 17 uniforms of reference shaders/raytracer.glsl:62-81, set per frame by
  * src/renderer.cpp:96-123 (glUniform* by name).  camera_fov is in radians (renderer.cpp:116).
@@ -114,7 +118,9 @@ int rtgl_create(rtgl_context **out, int width, int height, int device);
 /* Same, but this context owns only the row strips s with (s % world) == rank, where strip s covers
  * image rows [s*strip_rows, (s+1)*strip_rows).  Pixel seeds and camera rays use absolute pixel
  * coordinates, so the union over ranks is bit-identical to a single-context render.  strip_rows
- * must be a multiple of 8.  (No reference counterpart: SURVEY.md 8(e).) */
+ * must be a multiple of 8.  (No reference counterpart: SURVEY.md 8(e).)  The calls that need the whole picture say below that they are RTGL_ERR_STATE
+ * on such a context; rtgl_temporal_reset, rtgl_tonemap_reset and rtgl_error_reset only drop state that such a context never has, and
+ * return RTGL_OK. */
 int rtgl_create_tiled(rtgl_context **out, int width, int height, int device, int rank, int world, int strip_rows);
 
 /* Single-process multi-device context: the image is cut into strips of strip_rows rows, strip s belongs to
@@ -315,6 +321,9 @@ void *rtgl_device_denoise_variance(rtgl_context *ctx);
  *   Stores: {out, n} to the other history buffer; P(p) and, when the normal plane is enabled (whatever sigma_normal), N(p), as read, to the
  *   other guide copies; the host keeps the camera record.  With sigma_normal <= 0 the normal plane need not be enabled and is then neither
  *   read nor copied.
+ *   rtgl_temporal_reset and a change of "temporal_moments" drop the history for the NEXT rtgl_temporal_accumulate only: the latest history
+ *   buffer (and its moments) stay what rtgl_read_temporal_f32, "denoise_source" = 1, rtgl_tonemap source 2 and rtgl_temporal_clip work on.
+ *   The CURRENT camera is that of the latest rtgl_set_frame_params, whether or not a frame was rendered with it.
  *   The first call and the first after rtgl_temporal_reset have no history (out = I.rgb, n = 1 everywhere).  The history is dropped in the
  *   same way when this call needs Np and the previous call stored none because the normal plane was off then.
  * Defaults (rtgl_temporal_defaults, and a NULL params): max_history 32, sigma_normal 0.3, sigma_position 0.05.
@@ -518,7 +527,8 @@ int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256], uint32_t 
  *   rtgl_bind_device_image, any rendered frame with reset_flag != 0, and by a call whose F_n <= F_m or whose first_frames differs from the
  *   snapshot's.  (That host-side bookkeeping is all this extension adds to those entry points.)
  *   Per call: F_n = the `frames` of the parameters the latest frame was rendered with (frames a batching context holds are submitted
- *   first).  The image after that frame carries the weight F_n + 1 (what the accumulation divides by); first_frames is the `frames` of the
+ *   first).  Only rtgl_render_frame counts here: a masked frame (rtgl_adaptive_frame) ignores `frames` and leaves F_n as it was, and a
+ *   context that has rendered nothing else has rendered no frame (RTGL_ERR_STATE).  The image after that frame carries the weight F_n + 1 (what the accumulation divides by); first_frames is the `frames` of the
  *   first frame after the image was last zero -- 1 in the reference's loop, 0 for a caller who counts from 0 --, so the image holds
  *   n = F_n + 1 - first_frames real frames and equals their mean times n / (F_n + 1).  n < 1 is RTGL_ERR_INVALID.
  *     g_n = (float)((double)(F_n + 1) / (double)n);   m and g_m likewise from the snapshot's F_m;   c = (float)((double)m / (double)(n - m)).
@@ -637,6 +647,8 @@ void *rtgl_device_error_tiles(rtgl_context *ctx);
  * "rng_state" non-zero; a tiled or multi-device context.
  * rtgl_render_frame, rtgl_clear_image, rtgl_write_image_f32 and rtgl_bind_device_image END the session (their own behaviour is unchanged):
  * the image is no longer the session's.  The next rtgl_adaptive_frame is RTGL_ERR_STATE until a new rtgl_adaptive_begin.
+ * rtgl_render_frame ends it when the frame is accepted: a call refused for its parameters (RTGL_ERR_STATE before rtgl_set_frame_params,
+ * RTGL_ERR_INVALID for samples == 0, which divides by zero in the reference) leaves the session open.
  * A masked frame drops the snapshot of rtgl_error_estimate, like every other writer of the image that is not a counted frame.
  * Limits: the classic bias of stopping on an estimate (a tile stops when its noise happens to read low); a stopped tile is never
  * re-examined; seams between tiles of different counts; the first-hit planes, RNG states, denoised, temporal and display buffers are not

@@ -1391,7 +1391,6 @@ static int flush_pending(rtgl_context *ctx)
 extern "C" int rtgl_render_frame(rtgl_context *ctx)
 {
     ENTER_NOFLUSH(ctx);
-    ctx->ad_active = false;                              // (adaptive sampling: an ordinary frame ends the session)
     if (!ctx->workers.empty()) {                         // every part's frame is submitted by its own thread; this one waits for all of them
         ctx->gathered = false;
         for (auto &w : ctx->workers) { { std::lock_guard<std::mutex> lk(w->m); w->state = PartWorker::kJob; } w->cv.notify_all(); }
@@ -1407,6 +1406,7 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
     FANOUT(ctx, rtgl_render_frame(part));
     if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
     if (ctx->params.samples == 0) return fail(ctx, RTGL_ERR_INVALID, "u_samples == 0 divides by zero in the reference; refused");
+    ctx->ad_active = false;                              // (adaptive sampling: an ordinary frame ends the session; one refused above does not)
     // frame batching: hold the frame back until the batch is full.  Only what the batched pipeline covers: one sample per frame, the
     // per-bounce pipeline (a scene with triangles), no per-frame read-outs (counters, RNG states)
     const bool batchable = ctx->opt_frame_batch > 1 && ctx->params.samples == 1 && ctx->params.max_bounce > 0 && !ctx->opt_counters && !ctx->opt_rng_state

@@ -1,0 +1,274 @@
+"""tests/post_sequence_inputs.py and tests/post_sequence_model.py on the CPU: the generator is deterministic and meets its alphabet and its
+hazards, the model predicts both refusal classes for every feature, and on synthetic traced inputs -- the families of the *_inputs.py
+modules, no device, no oracle -- the model driven through ONE feature gives, step for step, what that feature's own mirror or stateful
+class gives when driven alone: the composition adds nothing."""
+import numpy as np
+import pytest
+
+import adaptive_mirror as am
+import denoise_guided_mirror as dgm
+import denoise_inputs as di
+import denoise_mirror as dm
+import error_inputs as ei
+import error_mirror as em
+import post_sequence_inputs as ps
+import post_sequence_model as pm
+import robust_error_mirror as rem
+import robust_inputs as ri
+import robust_mirror as rm
+import temporal_clip_inputs as tci
+import temporal_clip_mirror as tcm
+import temporal_inputs as ti
+import temporal_moments_inputs as mi
+import tonemap_inputs as toi
+import tonemap_mirror as tmm
+
+f32 = np.float32
+S = ps.S
+NAN_CAP = ti.NAN_CAP                    # the share the value cases allow (tests/test_denoise_guided_mirror.py, tests/test_temporal_clip_mirror.py)
+assert NAN_CAP == tci.NAN_CAP == 0.02
+H, W = 53, 70
+
+
+def words(a):
+    a = np.ascontiguousarray(a, f32)
+    return np.where(np.isnan(a), np.uint32(0x7FC00000), a.view(np.uint32))
+
+
+def same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    return bool((words(a) == words(b)).all()) if a.dtype == f32 else a.tobytes() == b.tobytes()
+
+
+class Synthetic:
+    """a tracer without a device: every frame is a view of temporal_inputs' step scene through the frame's camera, with an albedo plane of
+    temporal_moments_inputs; no NaN anywhere"""
+
+    def __init__(self, seq):
+        self.seq, self.k = seq, 0
+
+    def __call__(self, step, params, model):
+        if step.kind not in ("render", "adaptive_frame"):
+            return None
+        self.k += 1
+        rng = np.random.default_rng([self.seq.seed, self.k])
+        image, normal, position = ti.view(ps.CAMERAS[step.args["camera"]], self.seq.W, self.seq.H, ti.STEP, rng)
+        if step.kind == "adaptive_frame":
+            return dict(sample=image)
+        planes = {pm.A: mi.albedo_plane(self.seq.H, self.seq.W, self.k), pm.N: normal, pm.P: position, pm.IDS: np.zeros(image.shape, np.int32)}
+        return dict(image=image, planes=planes)
+
+
+_walks = {}
+
+
+def synthetic_walk(seed):
+    if seed not in _walks:
+        seq = ps.sequence(seed)
+        steps = [ps.resolved(seq, s) for s in seq.steps]
+        _walks[seed] = (seq, pm.walk(pm.PostModel(seq.H, seq.W), steps, Synthetic(seq), lambda s: ps.frame_params(seq.base, s.args)))
+    return _walks[seed]
+
+
+# ------------------------------------------------------------------------------------------------ the generator
+
+def test_the_generator_is_deterministic():
+    for seed in (0, 5, 17):
+        a, b = ps.sequence(seed), ps.sequence(seed)
+        assert (a.W, a.H, a.units) == (b.W, b.H, b.units) and repr(a.steps) == repr(b.steps)
+        assert ps.MIN_STEPS <= len(a.steps) <= ps.MAX_STEPS
+    assert repr(ps.sequence(0).steps) != repr(ps.sequence(9).steps), "seeds that share a row differ in their parameters"
+
+
+@pytest.mark.parametrize("start", [0, 7])
+def test_every_alphabet_entry_and_every_hazard_twice(start):
+    seqs = [ps.sequence(s) for s in ps.default_seeds(start=start)]
+    missing = [name for name, pred in ps.ALPHABET if not any(pred(s) for q in seqs for s in q.steps)]
+    assert not missing, f"alphabet entries that never occur: {missing}"
+    rare = [(name, n) for name, n in ((name, sum(bool(pred(q.steps)) for q in seqs)) for name, pred in ps.HAZARDS) if n < 2]
+    assert not rare, f"hazards in fewer than two sequences: {rare}"
+    assert all(ps.MIN_STEPS <= len(q.steps) <= ps.MAX_STEPS for q in seqs)
+
+
+def test_three_default_sequences_per_size():
+    sizes = [(q.W, q.H) for q in (ps.sequence(s) for s in ps.default_seeds())]
+    assert sorted(set(sizes)) == sorted(ps.SIZES) and all(sizes.count(s) == 3 for s in ps.SIZES)
+
+
+def test_both_refusal_classes_are_predicted_for_every_feature():
+    seen = {f: set() for f in ps.FEATURES}
+    accepted = refused = 0
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        for s, (status, _, _) in zip(seq.steps, walk):
+            accepted += status == 0
+            refused += status != 0
+            for f, kinds in ps.FEATURES.items():
+                if s.kind in kinds:
+                    seen[f].add(status)
+    lacking = {f: sorted(v) for f, v in seen.items() if not {0, pm.INVALID, pm.STATE} <= v}
+    assert not lacking, f"features without an accepted step, a -1 and a -4: {lacking}"
+    assert refused * 10 >= accepted and accepted > 2 * refused, (accepted, refused)
+
+
+def test_a_refused_step_changes_no_read_out():
+    for seed in ps.default_seeds()[:3]:
+        seq, walk = synthetic_walk(seed)
+        for k in range(1, len(walk)):
+            if walk[k][0] != 0:
+                before, after = walk[k - 1][1], walk[k][1]
+                unchanged = lambda a, b: a is b or (isinstance(a, tuple) and a == b)
+                assert all(all(unchanged(after[name][b], before[name][b]) for b in pm.BITS) if name == "planes" else unchanged(after[name], before[name])
+                           for name in pm.READOUTS), (seed, k)
+
+
+def test_the_nan_share_of_the_expected_outputs_stays_under_the_cap():
+    total = nans = 0
+    for seed in ps.default_seeds():
+        for _, out, _ in synthetic_walk(seed)[1]:
+            for name in ("image", "denoised", "variance", "history", "moments", "robust_buckets", "robust_output"):
+                if not isinstance(out[name], str):
+                    total += out[name].size
+                    nans += int(np.isnan(out[name]).sum())
+    assert total > 0 and nans <= NAN_CAP * total, (nans, total)
+
+
+# ------------------------------------------------------------------------------------------------ one feature at a time
+
+def planes_of(albedo, normal, position):
+    return {pm.A: albedo, pm.N: normal, pm.P: position, pm.IDS: np.zeros(position.shape, np.int32)}
+
+
+def drive(model, steps, frames):
+    """frames: the traced inputs of the render steps, in order"""
+    it = iter(frames)
+    return pm.walk(model, steps, lambda s, p, m: next(it) if s.kind == "render" else None, lambda s: s.args.get("camera"))
+
+
+def render(camera=None, frames=0, reset_flag=1):
+    return S("render", frames=frames, reset_flag=reset_flag, camera=camera)
+
+
+def test_the_denoisers_alone():
+    image, albedo, normal, position = di.make("benign", H, W, {}, seed=3)
+    frame = dict(image=image, planes=planes_of(albedo, normal, position))
+    steps = [S("set_aov", mask=7), render()]
+    want = []
+    for passes in (0, 1, 5):
+        for demod in (True, False):
+            steps.append(S("denoise", passes=passes, demodulate=demod, sigma_color=16.0, sigma_normal=0.3, sigma_position=0.05))
+            want.append(("denoised", dm.denoise(image, albedo, normal, position, passes=passes, demodulate=demod)))
+            steps.append(S("denoise_guided", passes=passes, demodulate=demod, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, firefly_ratio=1.0))
+            want.append(("guided",) + dgm.denoise_guided(image, albedo, normal, position, passes=passes, demodulate=demod))
+    walk = drive(pm.PostModel(H, W), steps, [frame])
+    for (status, out, _), w in zip(walk[2:], want):
+        assert status == 0
+        assert same(out["denoised"], w[1]) and (w[0] == "denoised" or same(out["variance"], w[2]))
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("family", ["translate", "dolly"])
+def test_the_temporal_calls_alone(family, mode):
+    seq = mi.make(family, H, W, seed=1)
+    steps, frames = [S("set_aov", mask=7), S("set_option", key="temporal_moments", value=mode)], []
+    for image, normal, position, camera, albedo in seq:
+        steps += [render(camera), S("temporal_accumulate", **tcm.tm.DEFAULTS), S("temporal_clip", **tcm.DEFAULTS)]
+        frames.append(dict(image=image, planes=planes_of(albedo, normal, position)))
+    walk = drive(pm.PostModel(H, W), steps, frames)
+    for k, (H0, H1, M0, M1) in enumerate(tcm.run(seq, mode=mode, clip_params={})):
+        after_acc, after_clip = walk[2 + 3 * k + 1][1], walk[2 + 3 * k + 2][1]
+        assert same(after_acc["history"], H0) and same(after_clip["history"], H1), k
+        if mode:
+            assert same(after_acc["moments"], M0) and same(after_clip["moments"], M1), k
+        else:
+            assert after_acc["moments"] == pm.REFUSED
+
+
+def test_the_display_transform_alone():
+    images = [toi.family(name, H, W) for name in ("hdr", "bin_edges", "hdr", "black")]
+    calls = [dict(auto=True, adapt=0.5, op=1), dict(auto=False, exposure=0.5, op=2), dict(auto=True, adapt=0.25, op=0), dict(auto=True, adapt=0.5, op=1)]
+    steps, alone, want = [], tmm.Tonemapper(), []
+    for img, c in zip(images, calls):
+        c = dict(dict(source=0, exposure=1.0, adapt=1.0), **c)
+        steps += [render(), S("tonemap", **c)]
+        want.append(alone(img, **{k: v for k, v in c.items() if k != "source"}))
+    steps.insert(6, S("tonemap_reset"))
+    alone2, want = tmm.Tonemapper(), []
+    for k, (img, c) in enumerate(zip(images, calls)):
+        if k == 3:
+            alone2.reset()
+        want.append(alone2(img, **c))
+    walk = drive(pm.PostModel(H, W), steps, [dict(image=i, planes={}) for i in images])
+    got = [out for (status, out, _), s in zip(walk, steps) if s.kind == "tonemap"]
+    hist = None
+    for g, w in zip(got, want):
+        hist = (w["hist"], w["ignored"]) if w["hist"] is not None else hist
+        assert same(g["display"], w["display"]) and words(g["exposure"]) == words(w["exposure"])
+        assert (g["histogram"][0] == hist[0]).all() and g["histogram"][1] == hist[1]
+
+
+@pytest.mark.parametrize("family", ["gauss1", "gauss0", "one_noisy_tile"])
+def test_the_error_estimate_alone(family):
+    fam = ei.family(family, H, W)
+    steps = []
+    for s in fam:
+        steps += [render(frames=s["frames"], reset_flag=0), S("error_estimate", keep_snapshot=False, first_frames=s["params"].get("first_frames", 1))]
+    walk = drive(pm.PostModel(H, W), steps, [dict(image=s["image"], planes={}) for s in fam])
+    want = ei.run([dict(s, params=dict(first_frames=s["params"].get("first_frames", 1))) for s in fam])
+    for k, w in enumerate(want):
+        status, out, _ = walk[2 * k + 1]
+        assert status == 0 and em.same_result(out["error_summary"], w) == [], k
+    assert any(w["valid"] == 1 for w in want)
+
+
+def test_the_adaptive_session_alone():
+    samples = ri.noisy(np.random.default_rng(5), H, W, 6, firefly=0.0)
+    params = dict(threshold=0.5, min_samples=2, max_samples=4)
+    alone = am.Session(H, W, **params)
+    steps = [S("adaptive_begin", **params)]
+    results = []
+    for k, smp in enumerate(samples):
+        if k == 2:
+            tiles = ps.mask_tiles("checker", H, W)
+            steps.append(S("adaptive_set_mask", tiles=tiles))
+            alone.set_mask(tiles)
+            results.append(None)
+        steps.append(S("adaptive_frame", camera=None))
+        alone.frame(smp)
+        results.append((alone.image, None))
+        if k % 2:
+            steps.append(S("adaptive_update"))
+            results.append((alone.image, alone.update(), alone.records.copy(), alone.mask.copy()))
+    it = iter(samples)
+    walk = pm.walk(pm.PostModel(H, W), steps, lambda s, p, m: dict(sample=next(it)) if s.kind == "adaptive_frame" else None)
+    for (status, out, summary), w in zip(walk[1:], results):
+        assert status == 0
+        if w is None:
+            continue
+        assert same(out["image"], w[0])
+        if w[1] is not None:
+            assert am.same_summary(summary, w[1]) == [] and out["adaptive_tiles"].tobytes() == w[2].tobytes() and (out["adaptive_mask"] == w[3]).all()
+
+
+@pytest.mark.parametrize("K", rm.BUCKETS)
+def test_the_robust_session_alone(K):
+    case = ri.make("ragged", H, W, K)
+    alone = rm.Session(H, W, K)
+    steps, want = [S("robust_begin", buckets=K)], []
+    for smp in case["samples"]:
+        steps += [render(), S("robust_accumulate")]
+        alone.accumulate(smp)
+        want.append(alone.planes.copy())
+    for gain in case["gains"]:
+        steps += [S("robust_resolve", gain=gain, dest=0), S("robust_error_estimate", threshold=0.05, floor=0.01, gain=gain), S("robust_resolve", gain=gain, dest=1)]
+    walk = drive(pm.PostModel(H, W), steps, [dict(image=s, planes={}) for s in case["samples"]])
+    for k, w in enumerate(want):
+        assert same(walk[2 + 2 * k][1]["robust_buckets"], w), k
+    base = 1 + 2 * len(want)
+    for k, gain in enumerate(case["gains"]):
+        a, b, c = (walk[base + 3 * k + j][1] for j in range(3))
+        assert same(a["robust_output"], alone.resolve(gain)) and same(c["image"], alone.resolve(gain, rm.DEST_IMAGE))
+        assert em.same_result(b["robust_error_summary"], rem.estimate(alone.planes, alone.N, gain=gain)) == []
+        assert c["robust_frames"] == (alone.N, K)
