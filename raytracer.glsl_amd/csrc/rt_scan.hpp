@@ -24,6 +24,7 @@
 #pragma once
 #include <type_traits>
 #include "rt_mfma.hpp"
+#include "rt_scan_items.hpp"
 
 #pragma clang fp contract(off)
 
@@ -739,9 +740,8 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     // all blocks of a chunk would sit on one XCD and every XCD would pull every ray through its L2 (measured: 130 MB of HBM traffic per C2
     // launch against 58 MB).  So, when there are enough blocks, eight consecutive blocks share a chunk: the waves that take the same items
     // of different chunks then sit on the same XCD and share the rays in its L2.
-    constexpr uint32_t kXcds = 8;
-    const bool by_xcd = gridDim.x >= kXcds * n_chunks;
-    const uint32_t c_first = by_xcd ? (blockIdx.x / kXcds) % n_chunks : blockIdx.x % n_chunks;
+    // (rt_scan_items.hpp: first_chunk, blocks_on, rank_on)
+    const uint32_t c_first = rt_scan_items::first_chunk(gridDim.x, blockIdx.x, n_chunks);
     // ---- planned: the block's interval (p_lo, p_hi] of the cost line of all items (chunk-major; plan_base = where each chunk starts).  An
     // unculled launch needs no plan: every item costs the same, chunk c starts at c x granules.
     typedef const unsigned long long __attribute__((address_space(4))) *ConstU64;
@@ -815,25 +815,21 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         const uint32_t n_items = __builtin_amdgcn_readfirstlane((cull && dynamic) ? wb.item_counts[c] : n_gran);
         const ConstWords items_k = (ConstWords)(uintptr_t)(wb.items + (size_t)c * wb.items_stride);
         // blocks that start on this chunk, and this block's rank among them
-        uint32_t blocks_here, rank_here;
-        if (by_xcd) {
-            const uint32_t rest = gridDim.x % (kXcds * n_chunks);
-            blocks_here = (gridDim.x / (kXcds * n_chunks)) * kXcds + min(kXcds, rest > kXcds * c ? rest - kXcds * c : 0u);
-            rank_here = (blockIdx.x / (kXcds * n_chunks)) * kXcds + blockIdx.x % kXcds;
-        } else { blocks_here = (gridDim.x - c + n_chunks - 1u) / n_chunks; rank_here = blockIdx.x / n_chunks; }
-        constexpr uint32_t kNone = 0xFFFFFFFFu;
+        const uint32_t blocks_here = rt_scan_items::blocks_on(gridDim.x, c, n_chunks), rank_here = rt_scan_items::rank_on(gridDim.x, blockIdx.x, n_chunks);
+        constexpr uint32_t kNone = rt_scan_items::kNone;
         // (the address is made to look divergent: for a uniform one LLVM's atomic optimizer rewrites the operation into its wave-aggregated
         // form, which is no faster here and longer)
         // hybrid: two of three granules (hybrid_div - 1 of hybrid_div) in fixed turns (nothing to wait for, every wave knows its next item), every third -- spread evenly
         // over the queue, so that the tail looks like the rest -- claimed from the chunk's counter when the wave is through with its
         // turns: with culling an item costs anything between nothing and 128 tiles, and fixed turns alone left the launch waiting for
         // its unluckiest wave (1.5 x the mean wave on bounce 1 of C2, 2.4 x on bounce 4)
-        const uint32_t hdiv = max(wb.hybrid_div, 1u), hturn = max(hdiv - 1u, 1u);      // hybrid: every hdiv-th granule is claimed (1: all of them)
-        const uint32_t n_tail = hybrid ? n_gran / hdiv : 0u, n_turns = n_gran - n_tail;
+        // (rt_scan_items.hpp holds the two numberings; tests/cpp/scan_items_check.cpp: every granule exactly once)
+        const uint32_t hdiv = rt_scan_items::hdiv_of(wb.hybrid_div);                    // hybrid: every hdiv-th granule is claimed (1: all of them)
+        const uint32_t n_tail = hybrid ? rt_scan_items::n_tail(n_gran, hdiv) : 0u, n_turns = n_gran - n_tail;
         const uint32_t n_claimable = hybrid ? n_tail : n_items;
         auto claim = [&](uint32_t seen, uint32_t &lo, uint32_t &end) {
             const uint32_t rem = n_claimable > seen ? n_claimable - seen : 0u;
-            const uint32_t n = hybrid ? min(max(rem / (2u * max(blocks_here, 1u) * kWaves), 1u), 4u) : min(max(rem / (4u * max(blocks_here, 1u) * kWaves), 1u), 16u);
+            const uint32_t n = hybrid ? rt_scan_items::claim_batch_hybrid(rem, blocks_here, kWaves) : rt_scan_items::claim_batch_dynamic(rem, blocks_here, kWaves);
             uint32_t v = 0u;
             if (lane == 0) v = atomicAdd(counter + opaque_zero, n);
             const uint32_t at = __builtin_amdgcn_readfirstlane(v);
@@ -845,7 +841,7 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         // from the granule's row (chunk_keep_bits), through the scalar cache.
         const ConstWords keep_k = (ConstWords)(uintptr_t)wb.keep;
         auto item_of = [&](uint32_t k, uint32_t &g, Mask128 &bits) {
-            g = hybrid ? (tail ? hdiv * k + (hdiv - 1u) : (k / hturn) * hdiv + k % hturn) : k; bits = keep_all;
+            g = hybrid ? rt_scan_items::hybrid_granule(tail, k, hdiv) : k; bits = keep_all;
             if (cull) {
                 if (dynamic) g = items_k[k];
                 bits = chunk_keep_bits(keep_k + (size_t)g * wb.keep_words, tile_begin, n_tiles);
@@ -875,10 +871,13 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
         uint32_t rec_k = kNone, rec_g = 0u;                    // the record of an item read ahead
         Mask128 rec_keep = {0ull, 0ull};
         uint32_t ray_k = kNone;                                // W = 1: the item whose rays are in (or on their way to) nxt_a / nxt_b
+        // (hybrid, leaving the turns for the tail: k is renumbered, and a record or rays read ahead belong to the turn numbering -- the last
+        // turn has no successor, so the record still names that turn, and the first claimed index may equal it: forgotten here.  The wave
+        // that starts in the tail, above, has read nothing ahead yet.)
         auto advance = [&]() {
             k += step;
             if (dynamic && k >= hi) claim(hi, k, hi);          // (dynamic: the batch is used up)
-            if (hybrid && k >= hi) { if (tail) claim(hi, k, hi); else { tail = true; step = 1u; claim(0u, k, hi); } }
+            if (hybrid && k >= hi) { if (tail) claim(hi, k, hi); else { tail = true; step = 1u; rec_k = kNone; ray_k = kNone; claim(0u, k, hi); } }
         };
         // The wave's survivor queue lives across its items of this chunk: an entry names its item by the item's turn in a ring of 16
         // granules, and the queue is handed over when it is full, when the ring is about to wrap, and behind the chunk's last item --

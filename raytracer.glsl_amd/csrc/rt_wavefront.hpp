@@ -18,6 +18,7 @@
 // R = rays per lane: each fetched record is used for R rays, dividing the operand traffic per test.
 #pragma once
 #include "rt_device.hpp"
+#include "rt_bin_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -75,16 +76,11 @@ struct WaveBuffers {
     uint32_t *sort_hist_other;    // the counters of the NEXT binned bounce: the move leaves them zero (two sets take turns; no fill launch per bounce)
     uint32_t sort_bits;           // key = direction bin (8 bits: 16 x 16 octahedral cells in Morton order) << 3 sort_ob | origin word (3 sort_ob bits)
     uint32_t sort_ob;
-    uint32_t sort_db, sort_T;     // direction cells per axis = 2^sort_db (4); origin cell bits behind the flag
     // origin word = [outside flag][3 sort_ob - 1 cell bits].  Inside the mesh's box (+ one cell): cells of the box, the bits dealt to the
     // axes by extent (a flat mesh spends none on its thin axis) and interleaved longest-cell-first.  Outside (the ground, the spheres: at
     // C2 58 % of the rays entering bounce 2): 16 cells per axis whose size doubles with the distance from the box's centre -- clamped
     // into the box's border cells those rays used to blow up the bounds of every granule there.
-    float sort_lo[3], sort_inv_cell[3];        // inside: cell_a = (o_a - lo_a) * inv_cell_a, clamped
-    float sort_in_lo[3], sort_in_hi[3];        // the inside test
-    float sort_cen[3], sort_inv_unit;          // outside: j = floor(log2(1 + |o_a - cen_a| * inv_unit)), clamped to 7; cell = 8 + j or 7 - j
-    uint32_t sort_in_bits, sort_out_bits;      // bits per axis, 4 bits each (x | y << 4 | z << 8)
-    uint32_t sort_in_order, sort_out_order;    // the axis of every key bit from the top, 2 bits each
+    rt_bin_plan::Cells sort_cells;             // (rt_bin_plan.hpp: the widths, the cells and the key itself)
     float4 *batch_rad;            // frame batching (option "frame_batch"): the paths of B consecutive frames travel through ONE set of launches;
     uint32_t batch_px;            //   a finished path leaves its radiance in batch_rad[frame slot * batch_px + pixel] (the slot rides in the top
                                   //   four bits of the path's pixel word), resolve_batch_kernel folds the slots into the image in frame order
@@ -735,49 +731,7 @@ __global__ void __launch_bounds__(256) intersect_kernel(SceneView sc, WaveBuffer
 // compaction into the next queue (wave ballot + prefix popcount, one atomicAdd per wave).
 // kSort: the survivors go to the staging queue with their bin key and their rank inside the bin (one atomic per ray on the bin's
 // counter: the rays of a wave scatter over hundreds of bins); sort_prefix_kernel + sort_place_kernel (or sort_scatter_kernel) finish the job.
-__device__ __forceinline__ uint32_t spread2(uint32_t x)        // 8 bits -> every second bit
-{
-    x &= 0xffu; x = (x | (x << 4)) & 0x0f0fu; x = (x | (x << 2)) & 0x3333u; x = (x | (x << 1)) & 0x5555u;
-    return x;
-}
-__device__ __forceinline__ uint32_t ray_bin_key(const WaveBuffers &wb, f3 o, f3 d)
-{
-    // direction: octahedral map of d / (|dx| + |dy| + |dz|) to 16 x 16 cells (a zero or non-finite direction lands in some cell: any
-    // key is valid, only the tightness of the granules depends on it)
-    const float l1 = fabsf(d.x) + fabsf(d.y) + fabsf(d.z);
-    const float il = l1 > 0.0f ? 1.0f / l1 : 0.0f;
-    float u = d.x * il, v = d.y * il;
-    if (d.z < 0.0f) { const float uu = (1.0f - fabsf(v)) * (u < 0.0f ? -1.0f : 1.0f), vv = (1.0f - fabsf(u)) * (v < 0.0f ? -1.0f : 1.0f); u = uu; v = vv; }
-    const int nd = 1 << wb.sort_db;
-    const int iu = min(nd - 1, max(0, (int)((u * 0.5f + 0.5f) * (float)nd))), iv = min(nd - 1, max(0, (int)((v * 0.5f + 0.5f) * (float)nd)));
-    const uint32_t dir = spread2((uint32_t)iu) | (spread2((uint32_t)iv) << 1);
-    const uint32_t T = wb.sort_T;
-    const float oa[3] = {o.x, o.y, o.z};
-    const bool inside = o.x >= wb.sort_in_lo[0] && o.x <= wb.sort_in_hi[0] && o.y >= wb.sort_in_lo[1] && o.y <= wb.sort_in_hi[1] && o.z >= wb.sort_in_lo[2] && o.z <= wb.sort_in_hi[2];   // (NaN: outside)
-    const uint32_t bits3 = inside ? wb.sort_in_bits : wb.sort_out_bits, order = inside ? wb.sort_in_order : wb.sort_out_order;
-    uint32_t c[3], left[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t nb = (bits3 >> (4 * a)) & 15u;
-        left[a] = nb;
-        if (inside) c[a] = (uint32_t)fminf(fmaxf((oa[a] - wb.sort_lo[a]) * wb.sort_inv_cell[a], 0.0f), (float)((1u << nb) - 1u));
-        else {
-            const float u = fminf(fabsf(oa[a] - wb.sort_cen[a]) * wb.sort_inv_unit, 1.0e6f);                 // (NaN -> 1e6)
-            const uint32_t j = min(7u, (__float_as_uint(1.0f + u) >> 23) - 127u);
-            c[a] = (oa[a] >= wb.sort_cen[a] ? 8u + j : 7u - j) >> (4u - nb);
-        }
-    }
-    uint32_t cell = 0u;
-    const uint32_t n = left[0] + left[1] + left[2];             // <= T (the outside cells stop at four bits per axis)
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t a = (order >> (2u * i)) & 3u;
-        const uint32_t l = (a == 0u ? left[0] : a == 1u ? left[1] : left[2]) - 1u;
-        const uint32_t v = a == 0u ? c[0] : a == 1u ? c[1] : c[2];
-        cell = (cell << 1) | ((v >> l) & 1u);
-        left[0] = a == 0u ? l : left[0]; left[1] = a == 1u ? l : left[1]; left[2] = a == 2u ? l : left[2];
-    }
-    return (dir << (T + 1u)) | (inside ? 0u : 1u << T) | (cell << (T - n));
-}
+// (the bin key of a ray: rt_bin_plan::ray_bin_key)
 
 // kAov: the launch of bounce 0 of sample 0 while option "aov" is on; it also writes the first-hit planes
 // kCamera: the lean camera bounce (generate_rays_kernel) -- bounce 0 of a single frame of one sample.  The ray is rebuilt from its slot
@@ -857,7 +811,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, FrameParams P, ImageVie
             // (the bin's counter first: its round trip -- a device-scope atomic is performed at the memory side -- runs beside the ray's stores)
             // Lanes of the wave that share a bin (camera rays off a mirror, neighbours in a binned queue) take their ranks from ONE
             // atomic: the groups are found with a readlane + ballot per distinct key, the leaders' atomics go out together.
-            const uint32_t key = ray_bin_key(wb, s.o, s.d);
+            const uint32_t key = rt_bin_plan::ray_bin_key(wb.sort_cells, s.o.x, s.o.y, s.o.z, s.d.x, s.d.y, s.d.z);
             uint32_t grp_n = 1u, grp_rank = 0u; int grp_leader = lane;
             for (unsigned long long todo = __ballot(1); todo;) {
                 const int l = __builtin_ctzll(todo);
@@ -925,7 +879,7 @@ __global__ void __launch_bounds__(256) shade_camera_kernel(SceneView sc, FramePa
 // ---- ray binning: bin counts -> first slots (two launches), then the move staging queue -> next queue.
 // sort_sums_kernel: one block per 4096 bins, their sum.  sort_prefix_kernel: every block adds up the sums of the blocks before it and
 // turns its own 4096 counts into first slots, in place.
-constexpr uint32_t kSortSeg = 4096;
+constexpr uint32_t kSortSeg = rt_bin_plan::kSortSeg;
 __global__ void __launch_bounds__(256) sort_sums_kernel(WaveBuffers wb)
 {
     __shared__ uint32_t part[4];

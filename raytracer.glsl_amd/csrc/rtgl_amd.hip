@@ -256,6 +256,7 @@ struct rtgl_context {
     void *d_plan = nullptr; size_t plan_capacity = 0;             // planned work distribution of culled scan launches: cost prefix sums per chunk
     void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
     uint32_t *d_sort_hist = nullptr; uint32_t sort_bits_alloc = 0;      // two sets of bin counters, used in turns
+    bool bin_refusal_said = false;                                     // a refused RTGL_AMD_SORT_OB / _DB pair was reported on stderr
     int sort_set = 0; uint32_t sort_set_bits = 0; bool sort_sets_clean = false;      // the set the next binned bounce counts in; false: zero both first (fresh, or a frame was abandoned half way)
     int opt_narrow_fused = 1;                // kernel 4: 1 (default) the scan waves test their own survivors at their end (rt_scan.hpp, tail drain), 0 narrow_phase_kernel does (RTGL_AMD_NARROW_FUSED)
     int opt_sort_move = 1;                   // ray binning's move (rt_wavefront.hpp, WaveBuffers): 1 gathered by packet_cull_kernel, 0 scattered (RTGL_AMD_SORT_MOVE)
@@ -802,7 +803,10 @@ static std::vector<uint32_t> kd_order(const rtgl_context *ctx, const std::vector
     float ext = 0.0f;
     for (int a = 0; a < 3; ++a) if (blo[a] <= bhi[a]) ext = std::max(ext, bhi[a] - blo[a]);
     float lambda = 0.4f * ext;
-    if (const char *e = getenv("RTGL_AMD_KD_LAMBDA")) lambda = (float)atof(e) * ext;      // (tuning: fraction of the mesh's extent)
+    // (tuning: fraction of the mesh's extent.  The weight only orders the triangles into tiles -- every bound is taken over what a tile
+    // ends up holding, so any order is a correct one -- but the splits below compare the weighted normals, and a NaN or an
+    // infinite weight (0 x inf) would hand nth_element keys without a strict weak order: finite values of 0 .. 1e6 only, else the default)
+    if (const char *e = getenv("RTGL_AMD_KD_LAMBDA")) { const float v = (float)atof(e); if (std::isfinite(v) && v >= 0.0f && v <= 1.0e6f) lambda = v * ext; }
     for (size_t v = 0; v < n; ++v) for (int a = 3; a < 6; ++a) pts[6 * v + a] *= lambda;
     std::vector<uint32_t> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
@@ -892,7 +896,7 @@ static int rebuild_triangles(rtgl_context *ctx)
         RCCHK(buf_alloc(ctx, ctx->d_mf_A, a_bytes));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_mf_A, 0, a_bytes, ctx->stream));
         hipLaunchKernelGGL(prepare_mfma_kernel, dim3(ctx->n_mf_groups), dim3(64), 0, ctx->stream, ctx->d_vertices, d_visit,
-                           ctx->d_mf_order, ctx->n_tri_visits, ctx->n_mf_groups, ctx->mf_group_quads, ctx->d_mf_groups, ctx->d_mf_A, getenv("RTGL_AMD_ROW_GAMMA") ? (float)atof(getenv("RTGL_AMD_ROW_GAMMA")) : 1.220703125e-4f);
+                           ctx->d_mf_order, ctx->n_tri_visits, ctx->n_mf_groups, ctx->mf_group_quads, ctx->d_mf_groups, ctx->d_mf_A, getenv("RTGL_AMD_ROW_GAMMA") ? (float)atof(getenv("RTGL_AMD_ROW_GAMMA")) : 1.220703125e-4f);      // (tuning.  Any value is covered: it only picks the row's scale, which mf_build_rows_kernel takes as a power of two within 1e-12 .. 1e12 or as 1 -- exact either way, and the group's bounds are taken over the scaled rows: DESIGN.md 3.1)
         HIPCHK(ctx, hipGetLastError());
         // packet-culling records, one per tile of the storage order (all-zero records -- unusable -- behind the last one)
         const uint32_t n_tiles_all = ctx->n_mf_groups * ctx->mf_group_quads * (uint32_t)kMfQuadTiles, n_tiles_alloc = n_tiles_all + 128u;
@@ -932,43 +936,24 @@ static rt_scan_launch::Setup scan_setup(const rtgl_context *ctx) { return {(uint
 
 static size_t counts_bytes(uint32_t capacity) { return (size_t)(capacity + 1u) * sizeof(uint32_t); }      // ray counts per bounce + the fullest candidate region
 
-// The origin word of the bin key (rt_wavefront.hpp, ray_bin_key): 3 sort_ob - 1 cell bits behind the outside flag.  Inside: every bit goes to
-// the axis whose cells are still the longest (a degenerate axis gets the last ones, which then carry nothing); outside: one bit less for
-// the axis the mesh is thinnest on.
-static void set_bin_cells(rtgl_context *ctx)
+// The environment's tuning of ray binning.  A refused (RTGL_AMD_SORT_OB, RTGL_AMD_SORT_DB) pair falls back to the defaults with one line on
+// stderr (tuning variables have no status path); rt_bin_plan.hpp says which pairs are accepted and why.
+static rt_bin_plan::Plan bin_plan(rtgl_context *ctx, uint32_t n0)
 {
-    WaveBuffers &wb = ctx->wb;
-    const uint32_t T = wb.sort_T;
-    const float ext_max = ctx->mesh_ext > 0.0f ? ctx->mesh_ext * 1.02f : 1.0f;
-    float ext[3]; uint32_t bits[3] = {0, 0, 0}, order = 0;
-    for (int a = 0; a < 3; ++a) ext[a] = std::max((ctx->mesh_hi[a] - ctx->mesh_lo[a]) + 0.02f * ext_max, 1.0e-6f * ext_max);
-    for (uint32_t i = 0; i < T; ++i) {
-        int best = 0;
-        for (int a = 1; a < 3; ++a) if (ext[a] / (float)(1u << bits[a]) > ext[best] / (float)(1u << bits[best])) best = a;
-        if (bits[best] >= 10u) for (int a = 0; a < 3; ++a) if (bits[a] < bits[best]) best = a;
-        bits[best]++; order |= (uint32_t)best << (2u * i);
+    const char *eo = getenv("RTGL_AMD_SORT_OB"), *ed = getenv("RTGL_AMD_SORT_DB");
+    const rt_bin_plan::Plan p = rt_bin_plan::plan(n0, eo ? std::max(atoi(eo), 0) : -1, ed ? std::max(atoi(ed), 0) : -1);
+    if (p.refused && !ctx->bin_refusal_said) {                // (once per context)
+        fprintf(stderr, "rtgl_amd: RTGL_AMD_SORT_OB=%s RTGL_AMD_SORT_DB=%s refused (rt_bin_plan.hpp: accepted pairs), using %u and %u\n", eo ? eo : "(unset)", ed ? ed : "(unset)", p.ob, p.db);
+        ctx->bin_refusal_said = true;
     }
-    float cell_max = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        wb.sort_lo[a] = ctx->mesh_lo[a] - 0.01f * ext_max;
-        wb.sort_inv_cell[a] = (float)(1u << bits[a]) / ext[a];
-        if (bits[a]) cell_max = std::max(cell_max, ext[a] / (float)(1u << bits[a]));
-    }
-    for (int a = 0; a < 3; ++a) { wb.sort_in_lo[a] = wb.sort_lo[a] - cell_max; wb.sort_in_hi[a] = wb.sort_lo[a] + ext[a] + cell_max; wb.sort_cen[a] = wb.sort_lo[a] + 0.5f * ext[a]; }
-    if (const char *e = getenv("RTGL_AMD_BIN_SPLIT")) if (atoi(e) == 0) for (int a = 0; a < 3; ++a) { wb.sort_in_lo[a] = -INFINITY; wb.sort_in_hi[a] = INFINITY; }      // (tuning: every origin clamped into the box's cells)
-    wb.sort_in_bits = bits[0] | (bits[1] << 4) | (bits[2] << 8); wb.sort_in_order = order;
-    wb.sort_inv_unit = 8.0f / ext_max;                            // the first outside cell ends a quarter of the half extent from the centre
-    if (const char *e = getenv("RTGL_AMD_BIN_UNIT")) { const float v = (float)atof(e); if (v > 0.0f) wb.sort_inv_unit = v / ext_max; }      // (tuning)
-    int thin = 0;
-    for (int a = 1; a < 3; ++a) if (ext[a] < ext[thin]) thin = a;
-    uint32_t ob[3] = {0, 0, 0}, oorder = 0;
-    for (uint32_t i = 0; i < T; ++i) {                            // round robin, the thin axis last
-        int best = -1;
-        for (int k = 0; k < 3; ++k) { const int a = (thin + 1 + k) % 3; if (best < 0 || ob[a] < ob[best]) best = a; }
-        if (ob[best] >= 4u) break;                                // (16 cells per axis at most: T <= 12 here)
-        ob[best]++; oorder |= (uint32_t)best << (2u * i);
-    }
-    wb.sort_out_bits = ob[0] | (ob[1] << 4) | (ob[2] << 8); wb.sort_out_order = oorder;
+    return p;
+}
+
+// The cells of the bin key's origin word (rt_bin_plan::cells) for the mesh in place
+static void set_bin_cells(rtgl_context *ctx, const rt_bin_plan::Plan &plan)
+{
+    const char *es = getenv("RTGL_AMD_BIN_SPLIT"), *eu = getenv("RTGL_AMD_BIN_UNIT");      // (tuning: 0 = every origin clamped into the box's cells; the outside cells' unit)
+    ctx->wb.sort_cells = rt_bin_plan::cells(ctx->mesh_lo, ctx->mesh_hi, ctx->mesh_ext, plan.T, plan.db, !(es && atoi(es) == 0), eu ? (float)atof(eu) : 0.0f);
 }
 
 static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_bounce, bool multi_sample)
@@ -1001,21 +986,18 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
             const size_t cap = ctx->stage_capacity;
             ctx->wb.stage = (float4 *)p; p += cap * 64; ctx->wb.sort_kr = (uint2 *)p; p += cap * 8; ctx->wb.stage_pixel = (uint32_t *)p; p += cap * 4;
             ctx->wb.sort_src = (uint32_t *)p;
-            // origin cell bits behind the flag: 11, 14 for more than twelve million rays
-            ctx->wb.sort_ob = n0 > (12u << 20) ? 5u : 4u;            // (C5, 8.3 M rays: 917 Mpaths/s with 4, 909 with 5; C2 in batches of eight, 16.6 M: 2.12 against 2.10 ms per frame)
-            if (const char *e = getenv("RTGL_AMD_SORT_OB")) { const int v = atoi(e); if (v >= 1 && v <= 5) ctx->wb.sort_ob = (uint32_t)v; }      // (tuning)
-            ctx->wb.sort_db = 4u;
-            if (const char *e = getenv("RTGL_AMD_SORT_DB")) { const int v = atoi(e); if (v >= 2 && v <= 6) ctx->wb.sort_db = (uint32_t)v; }      // (tuning: the bins stay as many)
-            ctx->wb.sort_bits = 8u + 3u * ctx->wb.sort_ob;
-            ctx->wb.sort_T = ctx->wb.sort_bits - 1u - 2u * ctx->wb.sort_db;
+            // (C5, 8.3 M rays: 917 Mpaths/s with 4 origin bit triples, 909 with 5; C2 in batches of eight, 16.6 M: 2.12 against 2.10 ms per frame)
+            const rt_bin_plan::Plan plan = bin_plan(ctx, n0);
+            ctx->wb.sort_ob = plan.ob; ctx->wb.sort_bits = plan.bits;
             if (ctx->sort_bits_alloc < ctx->wb.sort_bits) ctx->sort_sets_clean = false;
-            const size_t bins = (size_t)1 << ctx->wb.sort_bits;
-            RCCHK(buf_grow(ctx, ctx->d_sort_hist, ctx->sort_bits_alloc, ctx->wb.sort_bits, 2 * (bins + bins / kSortSeg) * sizeof(uint32_t)));
+            RCCHK(buf_grow(ctx, ctx->d_sort_hist, ctx->sort_bits_alloc, ctx->wb.sort_bits, rt_bin_plan::hist_words(plan) * sizeof(uint32_t)));
             ctx->wb.sort_hist = ctx->d_sort_hist; ctx->wb.sort_hist_other = ctx->d_sort_hist;      // (set per binned bounce: launch_wavefront)
-            set_bin_cells(ctx);
+            set_bin_cells(ctx, plan);
         }
-        ctx->wb.hybrid_div = 3u;          // (measured on C2 / C5: every 7th claimed 707 / 752 Mpaths/s, every 3rd 720 / 776, every 2nd 724 / 777, all of them 677 / 737)
-        if (const char *e = getenv("RTGL_AMD_HYBRID_DIV")) { const int v = atoi(e); if (v >= 1 && v <= 64) ctx->wb.hybrid_div = (uint32_t)v; }      // (tuning)
+        ctx->wb.hybrid_div = rt_scan_items::kHybridDivDefault;          // (measured on C2 / C5: every 7th claimed 707 / 752 Mpaths/s, every 3rd 720 / 776, every 2nd 724 / 777, all of them 677 / 737;
+                                                                        // the "every 2nd" figures were taken while a wave could reuse a record of its turns in the tail at that
+                                                                        // setting (one granule scanned twice, one never: rt_scan_items.hpp) -- unverified since)
+        if (const char *e = getenv("RTGL_AMD_HYBRID_DIV")) { const long v = atol(e); if (rt_scan_items::hybrid_div_accepted(v)) ctx->wb.hybrid_div = (uint32_t)v; }      // (tuning)
         ctx->wb.items = reinterpret_cast<uint32_t *>(ctx->d_items); ctx->wb.item_counts = reinterpret_cast<uint32_t *>(ctx->d_items);     // (allocated by the first culled launch)
         ctx->wb.cand = ctx->d_cand;
         ctx->wb.cand_counts = reinterpret_cast<uint32_t *>(ctx->d_cand + (size_t)ctx->cand_regions * ctx->cand_region_pairs);
@@ -1304,9 +1286,10 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                 const rt_shade_launch::Launch shade = rt_shade_launch::launch(ctx->opt_shade_pass, n0, estimate_rays(ctx, n0, b), bin_next);
                 if (bin_next) {
                     // two sets of bin counters take turns: the move (sort_place_kernel or sort_scatter_kernel) zeroes the one the next binned bounce will count in
-                    const size_t bins = (size_t)1 << ctx->wb.sort_bits, set_words = bins + bins / kSortSeg;
+                    const rt_bin_plan::Plan plan = {ctx->wb.sort_ob, ctx->wb.sort_cells.db, ctx->wb.sort_bits, ctx->wb.sort_cells.T, false};
+                    const size_t bins = rt_bin_plan::bins(plan), set_words = rt_bin_plan::set_words(plan);
                     if (!ctx->sort_sets_clean || ctx->sort_set_bits != ctx->wb.sort_bits) {
-                        HIPCHK(ctx, hipMemsetAsync(ctx->d_sort_hist, 0, 2 * set_words * sizeof(uint32_t), ctx->stream));
+                        HIPCHK(ctx, hipMemsetAsync(ctx->d_sort_hist, 0, rt_bin_plan::hist_words(plan) * sizeof(uint32_t), ctx->stream));
                         ctx->sort_set = 0; ctx->sort_set_bits = ctx->wb.sort_bits;
                     }
                     ctx->sort_sets_clean = false;              // (true again once this bounce's launches are in the stream)
@@ -1315,8 +1298,8 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     ctx->wb.sort_hist_other = ctx->d_sort_hist + (size_t)(ctx->sort_set ^ 1) * set_words;
                     if (lean && b == 0u) launch_shade_camera<true>(ctx, n0, sc, P, im, rng_out);
                     else launch_shade<true>(ctx, shade, sc, P, im, b, rng_out, aov_b);
-                    hipLaunchKernelGGL(sort_sums_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
-                    hipLaunchKernelGGL(sort_prefix_kernel, dim3((unsigned)(bins / kSortSeg)), dim3(256), 0, ctx->stream, ctx->wb);
+                    hipLaunchKernelGGL(sort_sums_kernel, dim3(rt_bin_plan::sums_grid(plan)), dim3(256), 0, ctx->stream, ctx->wb);
+                    hipLaunchKernelGGL(sort_prefix_kernel, dim3(rt_bin_plan::sums_grid(plan)), dim3(256), 0, ctx->stream, ctx->wb);
                     // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
                     if (ctx->opt_sort_move == 1) hipLaunchKernelGGL(sort_place_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     else hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
