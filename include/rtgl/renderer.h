@@ -715,6 +715,18 @@ public:
         if (summary) *summary = s;
         return done;
     }
+    // ---- robust denoise (rtgl_robust_denoise, include/rtgl_amd.h; extension): the resolve of the open session and the variance-guided filter
+    // in one call, the luminance tolerance of every pixel taken from the spread of its own buckets; the result is read with read_denoised()
+    // and read_denoise_variance(), or tone-mapped with source 1.  nullptr: its defaults (passes 5, sigma_lum 4, sigma_normal 0.3,
+    // sigma_position 0.05, gain 1, demodulate on).  Needs as many frames as buckets and the first-hit planes the parameters use.  The session,
+    // the image and the planes are only read.  Prints and returns false on failure.
+    bool robust_denoise(const rtgl_robust_denoise_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_denoise(m_ctx, params);
+        check(rc);
+        return rc == RTGL_OK;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

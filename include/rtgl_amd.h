@@ -812,6 +812,59 @@ int rtgl_robust_error_estimate(rtgl_context *ctx, const rtgl_robust_error_params
 int rtgl_read_robust_error_summary(rtgl_context *ctx, rtgl_error_summary *out);
 int rtgl_read_robust_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, uint32_t *tx, uint32_t *ty);
 void *rtgl_device_robust_error_tiles(rtgl_context *ctx);
+
+/* -- robust denoise: the resolve of an open robust session and the filter of rtgl_denoise_guided in one call, the luminance tolerance of
+ * every pixel taken from the spread of its own K bucket means.  rtgl_denoise_guided sees one picture and estimates a pixel's variance
+ * from a 7 x 7 window of that picture's luminance: fine texture counts as noise there and is blurred, and a noisy but locally flat region
+ * gets too tight a tolerance.  The K buckets are K independent estimates of the pixel itself; Yuen's variance of the trimmed mean (robust
+ * error estimate, step 7) is the variance of the very picture being filtered, per pixel.  No reference counterpart.  Every existing kernel,
+ * option and entry point is untouched.  DEFINED bit for bit under the rules of its neighbours (tests/robust_denoise_mirror.py restates
+ * it): binary32, one rounding per operation in the order written, no contraction, correctly rounded divide, subnormals kept, integers
+ * exact.
+ *   Per pixel, with K, N and the bucket planes b_j of the open session, A, N and P the first-hit planes as they are on the stream:
+ *     1. steps 1-9 of rtgl_robust_resolve with THIS call's gain: l_j, key_j, rank_j, t, the kept buckets and out, all four components
+ *     2. d = the divisor of rtgl_denoise, per channel (A > 2^-10) ? A : 2^-10;  c0 = out.rgb / d when RTGL_DENOISE_DEMODULATE is set,
+ *        else c0 = out.rgb
+ *     3. x_j = lum(b_j.r / d.r, b_j.g / d.g, b_j.b / d.b) when demodulating, else x_j = l_j;  then x_j = +inf if it is not finite
+ *        (lum of rtgl_denoise_guided)
+ *     4. lo = the x of the bucket with rank t;  hi = the x of the bucket with rank K - 1 - t;
+ *        w_j = lo if rank_j < t;  hi if rank_j > K - 1 - t;  else x_j      (winsorized by the RESOLVE's ranks: with a per-channel albedo
+ *        the order of the x can differ from the order of the keys, and the trim must be the resolve's)
+ *     5. M, mw and D as in steps 4-5 of the robust error estimate, over these w_j;  h = K - 2 t;  v = D / (float)(h (h - 1));
+ *        v0 = v if v - v == 0, else +0.   Without demodulation v is, bit for bit, the v of rtgl_robust_error_estimate step 7 for the
+ *        same gain.
+ *     6. the NEAR neighbours of rtgl_denoise_guided: those of the 3 x 3 about p inside the image with geometric weight g > 0, the same g
+ *     7. the passes of rtgl_denoise_guided, unchanged, over the records {c0, v0} in place of {c1, v0}: "Pass L = 0 .. passes-1" there.
+ *        Result: rgb = demodulating ? c d : c,  a = out.w.  The VARIANCE buffer holds {lum(c0), v0, var after the last pass, (float)h}.
+ *   There is no firefly clamp and no spatial estimate: the trim is the session's treatment of fireflies.  passes = 0 without
+ *   demodulation gives the DENOISED buffer equal to the resolve's out, bit for bit.
+ *   The result is in the DENOISED and the VARIANCE buffer of the denoisers: rtgl_read_denoised_f32, rtgl_device_denoised,
+ *   rtgl_read_denoise_variance_f32, rtgl_device_denoise_variance and source 1 of rtgl_tonemap take it as they take rtgl_denoise_guided's.
+ *   The call submits held frames first, enqueues on the context's stream and returns without waiting.  It writes the denoised buffer, the
+ *   two scratch buffers, the variance buffer and the near buffer (allocated by the first call that needs them, freed with the context) and
+ *   nothing else: the buckets, the output plane and the session's error records are only read or not touched, and so are the image, the
+ *   first-hit planes, the snapshot of rtgl_error_estimate and an adaptive session.  The session goes on.
+ * Defaults (rtgl_robust_denoise_defaults, and a NULL params): passes 5, sigma_lum 4, sigma_normal 0.3, sigma_position 0.05, gain 1,
+ * demodulate on.
+ * RTGL_ERR_INVALID: NULL context, passes > 8, a non-finite sigma, sigma_lum <= 0, gain NaN, negative or infinite, unknown flag bits,
+ * non-zero reserved words.
+ * RTGL_ERR_STATE: no session; N < K (an empty bucket has no luminance); a tiled or multi-device context; a plane the parameters need is
+ * not enabled; a plane is needed and no frame has been rendered since the planes last restarted (the conditions of rtgl_denoise_guided).
+ * Limits: a session renders every frame with reset_flag = 1, so the first-hit planes hold the LATEST frame's jittered hit, not a mean
+ * over the session: edges of the guides are one sample's.  Accumulating the guides over a session is out of scope.  The variance is of
+ * the luminance only; K = 4 gives 3 degrees of freedom or fewer per pixel, and the passes' own 3 x 3 blur of the variance is what
+ * steadies it. */
+typedef struct rtgl_robust_denoise_params {
+    uint32_t passes;          /* 0..8 */
+    float    sigma_lum;       /* > 0: luminance tolerance in standard deviations */
+    float    sigma_normal;    /* <= 0: the normal term is off */
+    float    sigma_position;  /* <= 0: the position term is off; relative to the hit distance */
+    float    gain;            /* finite, >= 0: the resolve's gain */
+    uint32_t flags;           /* RTGL_DENOISE_DEMODULATE */
+    uint32_t reserved[2];     /* must be 0 */
+} rtgl_robust_denoise_params; /* 32 bytes */
+int rtgl_robust_denoise_defaults(rtgl_robust_denoise_params *out);
+int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_params *params);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

@@ -30,6 +30,8 @@
 #include "rt_robust_plan.hpp"
 #include "rt_spread.hpp"
 #include "rt_spread_plan.hpp"
+#include "rt_bucket_guide.hpp"
+#include "rt_bucket_guide_plan.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
@@ -2779,6 +2781,85 @@ extern "C" void *rtgl_device_robust_error_tiles(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->rb_active || !ctx->has_rb_error) { ctx->error = std::string("rtgl_device_robust_error_tiles") + kNoRobustError; return nullptr; }
     return (void *)ctx->d_rbe_tiles;
+}
+
+// ---- rtgl_robust_denoise: the session's resolve and the guided filter in one call (rt_bucket_guide.hpp, rt_bucket_guide_plan.hpp) -------------
+static_assert(sizeof(rtgl_robust_denoise_params) == sizeof(rt_bucket_guide_plan::Params) && offsetof(rtgl_robust_denoise_params, gain) == offsetof(rt_bucket_guide_plan::Params, gain)
+              && offsetof(rtgl_robust_denoise_params, flags) == offsetof(rt_bucket_guide_plan::Params, flags) && rt_bucket_guide_plan::kFlagDemodulate == (uint32_t)RTGL_DENOISE_DEMODULATE
+              && rt_bucket_guide_plan::kPlaneAlbedo == (uint32_t)RTGL_AOV_ALBEDO && rt_bucket_guide_plan::kPlaneNormal == (uint32_t)RTGL_AOV_NORMAL
+              && rt_bucket_guide_plan::kPlanePosition == (uint32_t)RTGL_AOV_POSITION && rt_bucket_guide_plan::kLdsBytes == 6u * kBgN * sizeof(float)
+              && rt_bucket_guide_plan::kHaloW == (uint32_t)kBgW && rt_bucket_guide_plan::kHaloH == (uint32_t)kBgH, "the layouts of the header and of the kernel");
+
+extern "C" int rtgl_robust_denoise_defaults(rtgl_robust_denoise_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    const rt_bucket_guide_plan::Params p = rt_bucket_guide_plan::default_params();
+    memcpy(out, &p, sizeof p);
+    return RTGL_OK;
+}
+
+template <int K>
+static void launch_bucket_guide(rtgl_context *ctx, const BucketGuideArgs &a, bool demod)
+{
+    const dim3 grid(rt_bucket_guide_plan::tiles_x(a.width), rt_bucket_guide_plan::tiles_y(a.height));
+    if (demod) hipLaunchKernelGGL((bucket_guide_kernel<K, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((bucket_guide_kernel<K, false>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_params *params)
+{
+    ENTER(ctx);
+    rt_bucket_guide_plan::Params P = rt_bucket_guide_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_bucket_guide_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_denoise: ") + why);
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_denoise: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
+                                         "render on a single-device context");
+    if (const char *why = rt_bucket_guide_plan::refused(ctx->rb_active, ctx->rb_N, ctx->rb_K)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_denoise: ") + why);
+    if (const char *why = rt_bucket_guide_plan::planes_refused(rt_bucket_guide_plan::planes_needed(P), (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_denoise: ") + why);
+    const size_t n = rt_bucket_guide_plan::pixels(ctx->local_rows, ctx->width);
+    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_denoise: this context holds no pixels");
+    const bool demod = rt_bucket_guide_plan::demodulates(P), use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
+    // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer) and, for the last pass's alpha, the resolved pixel into the
+    // denoised buffer; pass k reads scratch k & 1 and writes scratch (k + 1) & 1 or, as the last, the denoised buffer: rtgl_denoise_guided's turns
+    RCCHK(buf_ensure(ctx, ctx->d_denoised, rt_bucket_guide_plan::record_bytes(n)));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_variance, rt_bucket_guide_plan::record_bytes(n)));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_near, rt_bucket_guide_plan::near_bytes(n)));
+    for (uint32_t k = 0; k < rt_bucket_guide_plan::scratch_buffers(P.passes); ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], rt_bucket_guide_plan::record_bytes(n)));
+    BucketGuideArgs b{};
+    b.buckets = ctx->d_rb_buckets; b.plane = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width);
+    b.albedo = demod ? ctx->d_aov[0] : nullptr; b.normal = use_n ? ctx->d_aov[1] : nullptr; b.position = use_p ? ctx->d_aov[2] : nullptr;
+    b.dst = P.passes == 0u ? ctx->d_denoised : ctx->d_dn_scratch[0]; b.resolved = ctx->d_denoised;
+    b.variance = ctx->d_dn_variance; b.near = ctx->d_dn_near;
+    b.width = ctx->width; b.height = ctx->local_rows; b.frames = ctx->rb_N; b.gain = P.gain;
+    b.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
+    b.sigma_position = P.sigma_position;
+    b.use_normal = use_n; b.use_position = use_p; b.final_image = P.passes == 0u;
+    if (ctx->rb_K == 4u) launch_bucket_guide<4>(ctx, b, demod);
+    else if (ctx->rb_K == 8u) launch_bucket_guide<8>(ctx, b, demod);
+    else launch_bucket_guide<16>(ctx, b, demod);
+    HIPCHK(ctx, hipGetLastError());
+    GuidedArgs a{};
+    a.image = ctx->d_denoised;                            // (the last pass reads only its own pixel's alpha there, before it writes that pixel)
+    a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
+    a.albedo = b.albedo; a.normal = b.normal; a.position = b.position;
+    a.width = b.width; a.height = b.height;
+    a.lum2 = P.sigma_lum * P.sigma_lum;
+    a.inv_normal = b.inv_normal; a.sigma_position = P.sigma_position;
+    a.use_normal = use_n; a.use_position = use_p; a.demodulate = demod;
+    for (uint32_t k = 0; k < P.passes; ++k) {
+        const bool last = k + 1u == P.passes;
+        a.src = ctx->d_dn_scratch[k & 1u];
+        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[(k + 1u) & 1u];
+        a.step = 1 << k; a.step_log2 = (int)k;
+        if (last && demod) launch_guided<true, true>(ctx, a);
+        else if (last) launch_guided<true, false>(ctx, a);
+        else launch_guided<false, false>(ctx, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_denoised = true; ctx->has_dn_variance = true;
+    return RTGL_OK;
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

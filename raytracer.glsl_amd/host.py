@@ -47,6 +47,8 @@ ROBUST_DEFAULTS = dict(buckets=8, gain=1.0, dest=0)
 ROBUST_DEST_BUFFER, ROBUST_DEST_IMAGE = 0, 1
 # rtgl_robust_error_estimate
 ROBUST_ERROR_DEFAULTS = dict(threshold=0.05, floor=0.01, gain=1.0, quantile_permille=950)
+# rtgl_robust_denoise
+ROBUST_DENOISE_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, gain=1.0, demodulate=True)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -74,6 +76,7 @@ ABI_SYMBOLS = [
     "rtgl_read_robust_f32", "rtgl_read_robust_bucket_f32",
     "rtgl_robust_error_defaults", "rtgl_robust_error_estimate", "rtgl_read_robust_error_summary", "rtgl_read_robust_error_tiles",
     "rtgl_device_robust_error_tiles",
+    "rtgl_robust_denoise_defaults", "rtgl_robust_denoise",
 ]
 
 
@@ -172,6 +175,12 @@ class CRobustErrorParams(C.Structure):
     """rtgl_robust_error_params"""
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("gain", C.c_float), ("quantile_permille", C.c_uint32), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32 * 3)]
+
+
+class CRobustDenoiseParams(C.Structure):
+    """rtgl_robust_denoise_params"""
+    _fields_ = [("passes", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("gain", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 def build_library(force: bool = False) -> str:
@@ -273,6 +282,8 @@ def load_library() -> C.CDLL:
     L.rtgl_read_robust_error_summary.argtypes = [vp, C.POINTER(CErrorSummary)]
     L.rtgl_read_robust_error_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     L.rtgl_device_robust_error_tiles.argtypes = [vp]; L.rtgl_device_robust_error_tiles.restype = vp
+    L.rtgl_robust_denoise_defaults.argtypes = [C.POINTER(CRobustDenoiseParams)]
+    L.rtgl_robust_denoise.argtypes = [vp, C.POINTER(CRobustDenoiseParams)]
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -795,6 +806,24 @@ class Context:
         """Device pointer of those records (0 before the session's first successful robust_error_estimate(): see the context's last error)."""
         return int(self.lib.rtgl_device_robust_error_tiles(self.h) or 0)
 
+    # --- robust denoise
+    def robust_denoise(self, passes=None, sigma_lum=None, sigma_normal=None, sigma_position=None, gain=None, demodulate=None):
+        """Enqueue the resolve of the open robust session and the variance-guided filter over it in one call (rtgl_robust_denoise; does
+        not wait): the luminance tolerance of every pixel comes from the spread of its own buckets.  It writes the buffer read_denoised()
+        returns and the variance buffer {lum(c0), v0, variance after the last pass, buckets kept}; the session, the image and the
+        first-hit planes are only read.  Needs at least as many frames as buckets.  An argument left at None keeps the library's default
+        (ROBUST_DENOISE_DEFAULTS); sigma_normal or sigma_position <= 0 switches that term off."""
+        p = CRobustDenoiseParams()
+        self._chk(self.lib.rtgl_robust_denoise_defaults(C.byref(p)))
+        if passes is not None:
+            p.passes = int(passes)
+        for name, value in (("sigma_lum", sigma_lum), ("sigma_normal", sigma_normal), ("sigma_position", sigma_position), ("gain", gain)):
+            if value is not None:
+                setattr(p, name, float(value))
+        if demodulate is not None:
+            p.flags = (p.flags & ~DENOISE_DEMODULATE) | (DENOISE_DEMODULATE if demodulate else 0)
+        self._chk(self.lib.rtgl_robust_denoise(self.h, C.byref(p)))
+
 
 class FrameLoop:
     """Pure host logic of the reference's Window::run + Renderer::render frame bookkeeping (no GPU):
@@ -929,6 +958,9 @@ class HeadlessRenderer(FrameLoop):
 
     def read_robust_error_summary(self) -> dict:
         return self.ctx.read_robust_error_summary()
+
+    def robust_denoise(self, **params):
+        self.ctx.robust_denoise(**params)
 
     def render_robust_until(self, threshold: float, max_frames: int, check_every: int = 16, buckets: int = 8, gain: float = 1.0, to_image: bool = False, **params):
         """Render a robust session until its resolved picture is this clean: session frames as render_robust() makes them, a
