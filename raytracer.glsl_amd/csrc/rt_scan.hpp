@@ -18,13 +18,15 @@
 //
 // Around the stream: a block stages the A tiles of a chunk of <= 32 quads in LDS and its waves work through (granule of 128 rays,
 // chunk) items -- handed out in fixed turns or claimed from counters (scan_solo_kernel below); survivors go to a per-wave LDS queue
-// and from there, as dense records, to the wave's own region of the candidate buffer, which the wave itself drains at its end
-// (drain_region; narrow_phase_kernel where the host asks for the separate launch; what does not fit is tested in place); packet_cull_kernel certifies, per granule and quad, that every ray misses every triangle by the reference's own
+// and from there, as dense records, to the wave's own region of the candidate buffer, which the wave itself drains at its end:
+// the records' masks expanded into (ray, triangle) pairs in that same LDS queue, 256 pairs tested per round trip (drain_region,
+// rt_drain_pairs.hpp; narrow_phase_kernel where the host asks for the separate launch; what does not fit is tested in place); packet_cull_kernel certifies, per granule and quad, that every ray misses every triangle by the reference's own
 // arithmetic (rt_mfma.hpp, MfCull) so that the scan can skip the quad.
 #pragma once
 #include <type_traits>
 #include "rt_mfma.hpp"
 #include "rt_scan_items.hpp"
+#include "rt_drain_pairs.hpp"
 
 #pragma clang fp contract(off)
 
@@ -243,10 +245,21 @@ __device__ __forceinline__ void exact_and_merge_at(const MfView &mf, const RayQu
 // ---- tail drain of a scan wave (scan_solo_kernel, `narrow_fused`): the wave tests the n_rec records of its own candidate region,
 // exactly as narrow_phase_kernel would (mask expanded, positions behind the last triangle skipped, the same exact test and merge).
 // narrow_phase_kernel is a chain of dependent round trips per record (record -> ray and triangle -> merge) with ONE record per lane
-// in flight; here a lane takes kDrainFly records per turn: their loads are issued back to back, then their rays', then -- once per
-// set bit of the fullest mask -- the triangle records of all of them.  A turn is 64 x kDrainFly records, the mean region of C2 two
-// turns.  Every load is unconditional, from a clamped index (a guarded load is an EXEC-masked block that waits for itself before the
-// next one starts), and the triangle records are copied out before the test's early exits can make their loads dependent.
+// in flight.  Here the unit is the PAIR (ray slot, storage position), one per set bit of a record's mask; the exact tests of a region
+// are independent pairs, and a turn tests 64 x kDrainFly of them, kDrainFly per lane:
+//   * the wave holds a window of 64 x kDrainFly records in registers and expands their masks, in order, into a list of pairs in its own
+//     LDS queue (free behind the wave's last flush() and the last block-wide barrier; ballots, mbcnt and popcounts place the pairs;
+//     wave_lds_sync() orders the wave's own LDS traffic, no block barrier: static waves end independently).  A record whose bits do
+//     not all fit the list keeps the rest in its mask for the next turn; a window that is used up is replaced, inside the turn, by
+//     the next one, whose records were loaded a turn ahead -- they travel under the tests.  rt_drain_pairs.hpp holds the arithmetic
+//     (tests/cpp/drain_pairs_check.cpp: every set bit exactly once, ceil(pairs / 256) turns);
+//   * every load of a turn is issued from the pair alone, back to back: the ray's `a` and `b`, the 7 x 16 bytes of the triangle
+//     (TriEdges 80 B, TriPlane 32 B) and its visit index -- ONE round trip per turn, where the per-record form (RT_DRAIN_RECORDS, below)
+//     takes one for the records, one for the rays and one per set bit of the fullest of 256 masks, most lanes testing a dummy in all
+//     but the first.
+// Every load is unconditional, from a clamped index (a guarded load is an EXEC-masked block that waits for itself before the
+// next one starts), and all of them are pinned into registers before the first test (tri_exact leaves after each failed edge: the
+// compiler otherwise sinks the later rows' loads behind those exits).
 //
 // Read-back of the records.  This wave wrote them in flush() with store_through (global_store ... sc0 sc1: written through to memory
 // at system scope, no dirty line left in the L2).  What the drain relies on: (1) the caller's s_waitcnt vmcnt(0) between the last
@@ -257,8 +270,13 @@ __device__ __forceinline__ void exact_and_merge_at(const MfView &mf, const RayQu
 constexpr int kDrainFly = 4;
 typedef float drain_f4 __attribute__((ext_vector_type(4)));
 static_assert(sizeof(TriEdges) == 80 && sizeof(TriPlane) == 32 && alignof(TriEdges) == 16 && alignof(TriPlane) == 16, "drain_region reads these as rows of 16 bytes");
+static_assert(kDrainFly == (int)rt_drain_pairs::kFly, "a lane tests kDrainFly pairs per turn");
+#ifdef RT_DRAIN_RECORDS
+// The per-record form (diagnostics build `make records`: the off arm of profiles/drain_pairs_c2).  A lane takes kDrainFly RECORDS per
+// turn: their loads are issued back to back, then their rays', then -- once per set bit of the fullest mask -- the triangle records
+// of all of them.  A turn is 64 x kDrainFly records and 2 + (set bits of the fullest mask) round trips.
 __device__ __forceinline__ void drain_region(const SceneView &sc, const MfView &mf, const RayQueue &qin, unsigned long long *best,
-                                             const unsigned long long *recs, uint32_t n_rec, uint32_t lane)
+                                             const unsigned long long *recs, uint32_t n_rec, uint32_t lane, uint2 *, uint32_t)
 {
     constexpr int K = kDrainFly;
     const uint32_t last_tri = sc.n_tri_visits - 1u;               // (n_rec > 0: there are triangles)
@@ -320,6 +338,98 @@ __device__ __forceinline__ void drain_region(const SceneView &sc, const MfView &
         }
     }
 }
+#else
+__device__ __forceinline__ void drain_region(const SceneView &sc, const MfView &mf, const RayQueue &qin, unsigned long long *best,
+                                             const unsigned long long *recs, uint32_t n_rec, uint32_t lane, uint2 *list, uint32_t scratch_entry)
+{
+    namespace dp = rt_drain_pairs;
+    constexpr int K = kDrainFly;
+    const uint32_t last_tri = sc.n_tri_visits - 1u;               // (n_rec > 0: there are triangles)
+    uint32_t slot[K], pos5[K], um[K];                             // the window: batch j = records base + 64 j + lane, masks with the bits still to test
+    unsigned long long nxt[K];                                    // the records of the window behind it
+    auto load_window = [&](uint32_t at) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) nxt[j] = __hip_atomic_load(recs + dp::load_record(at, (uint32_t)j, lane, n_rec), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto take_window = [&](uint32_t at) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const uint32_t hi = (uint32_t)(nxt[j] >> 32);
+            slot[j] = (uint32_t)nxt[j]; pos5[j] = hi >> 5;
+            um[j] = dp::record_in_region(at, (uint32_t)j, lane, n_rec) ? hi & 31u : 0u;      // (behind the last record: the last record's ray, no triangle)
+        }
+    };
+    uint32_t base = 0u;                                           // wave-uniform: the window's first record
+    load_window(0u); take_window(0u);
+    load_window(dp::kWindow);                                     // (clamped: a region of one window loads its last record again and never looks at it)
+    for (;;) {
+        // ---- the turn's list: the window's remaining bits in record order, and the next window's where this one runs out
+        uint32_t fill = 0u;                                       // wave-uniform
+        wave_lds_sync();                                          // (the previous turn's reads of the list are behind us)
+        for (;;) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t pc = (uint32_t)__builtin_popcount(um[j]);
+                const unsigned long long b0 = __builtin_amdgcn_ballot_w64((pc & 1u) != 0u), b1 = __builtin_amdgcn_ballot_w64((pc & 2u) != 0u), b2 = __builtin_amdgcn_ballot_w64((pc & 4u) != 0u);
+                const uint32_t batch_bits = dp::bits_from_ballots((uint32_t)__popcll(b0), (uint32_t)__popcll(b1), (uint32_t)__popcll(b2));
+                if (batch_bits == 0u || dp::turn_full(fill)) continue;
+                auto below = [&](unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
+                uint32_t at = dp::first_pair(fill, dp::bits_from_ballots(below(b0), below(b1), below(b2)));
+                const uint32_t deepest = b2 ? dp::kMaskBits : (b1 ? 3u : 1u);          // no mask of the batch holds more bits
+#pragma unroll
+                for (uint32_t k = 0; k < dp::kMaskBits; ++k) {
+                    if (k >= deepest) break;
+                    const bool put = um[j] != 0u && dp::pair_fits(at);
+                    const uint32_t bit = um[j] ? (uint32_t)__builtin_ctz(um[j]) : 0u;
+                    list[dp::list_entry(put, at, scratch_entry)] = make_uint2(slot[j], pos5[j] + bit);
+                    if (put) { um[j] &= um[j] - 1u; ++at; }
+                }
+                fill = dp::fill_behind(fill, batch_bits);
+            }
+            if (dp::turn_full(fill) || !dp::window_behind(base, n_rec)) break;
+            base += dp::kWindow;                                  // (fill < 256: every bit of the window went into the list)
+            take_window(base); load_window(base + dp::kWindow);
+        }
+        if (fill == 0u) break;
+        wave_lds_sync();
+        // ---- the turn's tests: pairs lane, lane + 64, ... of the list (neighbouring lanes: the same ray, neighbouring triangles)
+        uint32_t ps[K], p[K], v[K]; bool on[K]; drain_f4 a[K], b[K], e[K][5], pl[K][2];
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const uint2 pr = list[dp::lane_entry(lane, (uint32_t)q, fill)];
+            ps[q] = pr.x;
+            on[q] = dp::lane_has_pair(lane, (uint32_t)q, fill) && pr.y < sc.n_tri_visits;      // (padding rows behind the last triangle)
+            p[q] = min(pr.y, last_tri);
+        }
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const drain_f4 *const ep = reinterpret_cast<const drain_f4 *>(mf.edges_s + p[q]), *const pp = reinterpret_cast<const drain_f4 *>(mf.planes_s + p[q]);
+            a[q] = *reinterpret_cast<const drain_f4 *>(qin.a + ps[q]); b[q] = *reinterpret_cast<const drain_f4 *>(qin.b + ps[q]);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) e[q][k] = ep[k];
+            pl[q][0] = pp[0]; pl[q][1] = pp[1]; v[q] = mf.order[p[q]];
+        }
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) asm volatile("" : "+v"(e[q][k]));
+            asm volatile("" : "+v"(a[q]), "+v"(b[q]), "+v"(pl[q][0]), "+v"(pl[q][1]), "+v"(v[q]));
+        }
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            TriRay tr; TriEdges T; TriPlane P;
+            tr.o = mk(a[q].x, a[q].y, a[q].z); tr.d = mk(a[q].w, b[q].x, b[q].y); tr.cv = cross3(tr.d, tr.o); tr.ncv = tr.nd = 0.0f;
+            T.e0x = e[q][0].x; T.e0y = e[q][0].y; T.e0z = e[q][0].z; T.e1x = e[q][0].w; T.e1y = e[q][1].x; T.e1z = e[q][1].y; T.e2x = e[q][1].z; T.e2y = e[q][1].w; T.e2z = e[q][2].x;
+            T.m0x = e[q][2].y; T.m0y = e[q][2].z; T.m0z = e[q][2].w; T.m1x = e[q][3].x; T.m1y = e[q][3].y; T.m1z = e[q][3].z; T.m2x = e[q][3].w; T.m2y = e[q][4].x; T.m2z = e[q][4].y;
+            T.bound_e = e[q][4].z; T.bound_m = e[q][4].w;
+            P.nx = pl[q][0].x; P.ny = pl[q][0].y; P.nz = pl[q][0].z; P.v0x = pl[q][0].w; P.v0y = pl[q][1].x; P.v0z = pl[q][1].y; P.material = 0; P.pad = 0;
+            const float t = tri_exact(T, P, tr);
+            if (on[q] && kEps < t && t < kInf) atomicMin(&best[ps[q]], ((unsigned long long)__float_as_uint(t) << 32) | v[q]);
+        }
+        if (!dp::turn_full(fill)) break;                          // (a short turn: the region had no more)
+    }
+}
+#endif
 
 constexpr int kSoloSets = 4;                                      // 32-ray sets per wave: 512 rays per block of four waves
 struct SoloCfg {
@@ -1150,11 +1260,40 @@ scan_solo_kernel(SceneView sc, WaveBuffers wb, MfView mf, uint32_t bounce, uint3
     // takes are behind it -- and its region is complete: it tests its own records here, beside the matrix work of the waves that are
     // still scanning, instead of leaving them to a narrow_phase_kernel launch that cannot start before the slowest wave has ended.
     // Pairs that did not fit the region were tested by flush() and are not among the records.
-    if (narrow_fused) {
+#ifdef RT_SOLO_STAMPS
+    constexpr bool kDrainTally = true;                         // (the stamps builds launch narrow_phase_kernel: the tally looks at the regions all the same)
+#else
+    constexpr bool kDrainTally = false;
+#endif
+    if (narrow_fused || kDrainTally) {
         const uint32_t n_rec = (uint32_t)(appended < (unsigned long long)wb.cand_region ? appended : (unsigned long long)wb.cand_region);
         if (n_rec) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the records' write-through stores have completed (drain_region)
-            drain_region(sc, mf, qin, best, reinterpret_cast<const unsigned long long *>(cand), n_rec, (uint32_t)lane);
+#ifdef RT_SOLO_STAMPS
+            // what the region holds, per bounce (printed at rtgl_destroy): regions, records, pairs, windows of 64 x kDrainFly records, the
+            // set bits of every window's fullest mask (the per-record form takes one round trip for each), and the pair form's turns
+            if (mf.dbg_log && bounce < 64u) {
+                const unsigned long long *const recs = reinterpret_cast<const unsigned long long *>(cand);
+                unsigned long long t_pairs = 0, t_deep = 0, t_windows = 0;
+                for (uint32_t i0 = 0; i0 < n_rec; i0 += rt_drain_pairs::kWindow) {
+                    uint32_t bits = 0u, deep = 0u;
+                    for (uint32_t j = 0; j < rt_drain_pairs::kFly; ++j) {
+                        const unsigned long long r = __hip_atomic_load(recs + rt_drain_pairs::load_record(i0, j, (uint32_t)lane, n_rec), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const uint32_t pc = rt_drain_pairs::record_in_region(i0, j, (uint32_t)lane, n_rec) ? (uint32_t)__builtin_popcount((uint32_t)(r >> 32) & 31u) : 0u;
+                        bits += pc; deep = max(deep, pc);
+                    }
+                    for (int off = 32; off > 0; off >>= 1) { bits += (uint32_t)__shfl_xor((int)bits, off); deep = max(deep, (uint32_t)__shfl_xor((int)deep, off)); }
+                    t_pairs += bits; t_deep += deep; ++t_windows;
+                }
+                if (lane == 0) {
+                    unsigned long long *d = reinterpret_cast<unsigned long long *>(mf.dbg_log) + 1024ull + 8ull * bounce;
+                    atomicAdd(d + 0, 1ull); atomicAdd(d + 1, (unsigned long long)n_rec); atomicAdd(d + 2, t_pairs); atomicAdd(d + 3, t_windows); atomicAdd(d + 4, t_deep);
+                    atomicAdd(d + 5, (unsigned long long)rt_drain_pairs::turns_of(t_pairs));
+                }
+            }
+#endif
+            static_assert(rt_drain_pairs::kTurnPairs < Cfg::kQueue, "the turn's list and the scratch entry behind it lie in the wave's queue");
+            if (narrow_fused) drain_region(sc, mf, qin, best, reinterpret_cast<const unsigned long long *>(cand), n_rec, (uint32_t)lane, queue, Cfg::kQueue - 1u);
         }
     }
 #ifdef RT_SOLO_STAMPS

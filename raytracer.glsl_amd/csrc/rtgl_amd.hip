@@ -534,6 +534,17 @@ extern "C" void rtgl_destroy(rtgl_context *ctx)
             if (ticks > 0) fprintf(stderr, "rtgl clock: in-kernel shader clock of scan_solo_kernel, wave-time weighted over all launches: %.3f GHz\n", cyc / ticks * 0.1);
         }
 #endif
+        // the tail drain (narrow_fused): what the waves' regions held.  A window is 64 x 4 records; the per-record form takes 2 + (set bits of
+        // the window's fullest mask) round trips for it, the pair form one per 256 pairs of the region
+        unsigned long long dr[8 * 64];
+        if (hipMemcpy(dr, reinterpret_cast<unsigned long long *>(ctx->d_dbg_log) + 1024, sizeof dr, hipMemcpyDeviceToHost) == hipSuccess)
+            for (int b = 0; b < 64; ++b) {
+                const unsigned long long *d = dr + 8 * b;
+                if (!d[0]) continue;
+                fprintf(stderr, "rtgl drain bounce %2d: regions %llu records %llu pairs %llu (%.3f per record)  windows %llu, fullest mask of a window %.2f bits: %.2f round trips per region by records, %.2f by pairs\n",
+                        b, d[0], d[1], d[2], d[1] ? (double)d[2] / (double)d[1] : 0.0, d[3], d[3] ? (double)d[4] / (double)d[3] : 0.0,
+                        (double)(2 * d[3] + d[4]) / (double)d[0], (double)d[5] / (double)d[0]);
+            }
         // static launches: mean wave time per chunk, relative to the bounce's mean (what an uneven cost of the chunks loses)
         std::vector<unsigned long long> pc(16 * 64 * 2 * 16);
         if (hipMemcpy(pc.data(), reinterpret_cast<unsigned long long *>(ctx->d_dbg_log) + 2048, pc.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
