@@ -3,9 +3,9 @@ tests/post_sequence_inputs.py.  A helper, not a test; numpy, no device.
 
 PostModel(h, w) composes the mirrors the suite already has -- denoise_mirror, denoise_guided_mirror, temporal_mirror,
 temporal_moments_mirror, temporal_clip_mirror, tonemap_mirror.Tonemapper, error_mirror.Estimator, adaptive_mirror.Session,
-robust_mirror.Session, robust_error_mirror.estimate -- and adds no arithmetic of its own: what it adds is WHICH buffer a call reads, which
-state a call drops, and when a call is refused, each taken from a sentence of the header (quoted where it is used).  It never reads
-rtgl_amd.hip and is never fed anything the context under test produced.
+robust_mirror.Session, robust_error_mirror.estimate, robust_denoise_mirror.robust_denoise -- and adds no arithmetic of its own: what it
+adds is WHICH buffer a call reads, which state a call drops, and when a call is refused, each taken from a sentence of the header (quoted
+where it is used).  It never reads rtgl_amd.hip and is never fed anything the context under test produced.
 
   status_of(step)          the status the header gives the step in the current state: 0, -1 (RTGL_ERR_INVALID) or -4 (RTGL_ERR_STATE).
                            A bad argument is reported before the state (header, "rtgl_status").
@@ -24,6 +24,7 @@ import adaptive_mirror as am
 import denoise_guided_mirror as dgm
 import denoise_mirror as dm
 import error_mirror as em
+import robust_denoise_mirror as rdm
 import robust_error_mirror as rem
 import robust_mirror as rm
 import temporal_clip_mirror as tcm
@@ -175,6 +176,17 @@ class PostModel:
             return STATE
         return OK
 
+    def _status_robust_denoise(self, a):
+        # "RTGL_ERR_INVALID: ... passes > 8, a non-finite sigma, sigma_lum <= 0, gain NaN, negative or infinite"
+        if not rdm.valid_params(a["passes"], a["sigma_lum"], a["sigma_normal"], a["sigma_position"], a["gain"]):
+            return INVALID
+        # "RTGL_ERR_STATE: no session; N < K (an empty bucket has no luminance); a tiled or multi-device context; ..."
+        if self.tiled or self.robust is None or self.robust.N < self.robust.K:
+            return STATE
+        # "... a plane the parameters need is not enabled; a plane is needed and no frame has been rendered since the planes last
+        # restarted (the conditions of rtgl_denoise_guided)": with no plane needed the restart does not refuse
+        return self._planes_state(self._denoiser_planes(a))
+
     # -------------------------------------------------------------------------------------------- events several calls share
     def _image_replaced(self):
         """what rtgl_write_image_f32 does on the host, and with it rtgl_clear_image, rtgl_bind_device_image and rtgl_robust_resolve into
@@ -318,6 +330,15 @@ class PostModel:
 
     def _do_robust_error_estimate(self, a, traced):
         self.robust_error = rem.estimate(self.robust.planes, self.robust.N, threshold=a["threshold"], floor=a["floor"], gain=a["gain"])
+
+    def _do_robust_denoise(self, a, traced):
+        # "The result is in the DENOISED and the VARIANCE buffer of the denoisers ... and nothing else: the buckets, the output plane and
+        # the session's error records are only read or not touched, and so are the image, the first-hit planes, the snapshot of
+        # rtgl_error_estimate and an adaptive session.  The session goes on."  It filters the buckets, never the image or the history:
+        # "denoise_source" and "denoise_variance" do not enter
+        self.denoised, self.variance = rdm.robust_denoise(self.robust.planes, self.robust.N, self._plane(A), self._plane(N), self._plane(P), passes=a["passes"],
+                                                          sigma_lum=a["sigma_lum"], sigma_normal=a["sigma_normal"], sigma_position=a["sigma_position"],
+                                                          gain=a["gain"], demodulate=a["demodulate"])
 
     # -------------------------------------------------------------------------------------------- read-outs
     def readouts(self):

@@ -8,7 +8,7 @@ of ordinary frames of the twin is held to the CPU oracle, and every one-frame sa
 adaptive_mirror's).  Every comparison is of bits, a NaN counting as one word; there is no tolerance anywhere.  One printed line per
 differing step.
 
-POST_SEQ_CASES (default 9: three per size) and POST_SEQ_SEED (default 0) choose the sequences, as FUZZ_CASES and FUZZ_SEED do elsewhere.
+POST_SEQ_CASES (default 15: five per size) and POST_SEQ_SEED (default 0) choose the sequences, as FUZZ_CASES and FUZZ_SEED do elsewhere.
 Twin, oracle and model run once per seed and are shared by the tests."""
 import os
 import re
@@ -129,7 +129,7 @@ def apply(ctx, seq, step, rows=None, bound=0, sync=None):
         "error_estimate": lambda: ctx.error_estimate(**a), "error_reset": ctx.error_reset,
         "adaptive_begin": lambda: ctx.adaptive_begin(**a), "adaptive_set_mask": lambda: ctx.adaptive_set_mask(a["tiles"]),
         "robust_begin": lambda: ctx.robust_begin(a["buckets"]), "robust_accumulate": ctx.robust_accumulate, "robust_resolve": lambda: ctx.robust_resolve(**a),
-        "robust_end": ctx.robust_end, "robust_error_estimate": lambda: ctx.robust_error_estimate(**a),
+        "robust_end": ctx.robust_end, "robust_error_estimate": lambda: ctx.robust_error_estimate(**a), "robust_denoise": lambda: ctx.robust_denoise(**a),
     }[k]
     return status_of(call)[0], None
 
@@ -293,6 +293,8 @@ def run_blind(rt, seq, steps, walk, who, options=()):
 
 def test_every_step_matches_the_model(rt, oracle):
     t0, bad, steps_run, refused = time.perf_counter(), 0, 0, 0
+    rd = {K: 0 for K in ps.BUCKETS}
+    rd.update({pm.INVALID: 0, pm.STATE: 0})                            # robust_denoise: accepted per K of the session, and the two refusals
     for seed in seeds():
         seq, steps, walk, _ = expected(rt, oracle, seed)
         t1 = time.perf_counter()
@@ -301,10 +303,16 @@ def test_every_step_matches_the_model(rt, oracle):
         bad += len(lines)
         steps_run += len(steps)
         refused += sum(st != 0 for st, _, _ in walk)
+        for s, (st, out, _) in zip(steps, walk):
+            if s.kind == "robust_denoise":
+                rd[st if st else out["robust_frames"][1]] += 1
         print(f"sequence {seed} {seq.W} x {seq.H}: {len(steps)} steps, device part {time.perf_counter() - t1:.2f} s", flush=True)
     print(f"sequences {len(seeds())} steps {steps_run} refused {refused} | differing steps: {bad} | {time.perf_counter() - t0:.2f} s with twin, oracle and model", flush=True)
+    print("robust_denoise: accepted " + ", ".join(f"{rd[K]} at K = {K}" for K in ps.BUCKETS) + f"; {rd[pm.INVALID]} times -1, {rd[pm.STATE]} times -4", flush=True)
     assert bad == 0, f"{bad} steps of {len(seeds())} sequences differ from the model (see the lines printed above)"
     assert refused * 10 >= steps_run, "hardly a step was refused"
+    if len(seeds()) >= len(ps.ROWS):                                   # every row is among them
+        assert all(rd[k] >= 1 for k in rd), rd
 
 
 def test_the_same_sequence_without_intermediate_read_outs_ends_on_the_same_bits(rt, oracle):
@@ -339,9 +347,10 @@ def test_bound_image_on_a_torch_stream_changes_nothing(rt, oracle):
     dev = torch.device("cuda", 0)
     for seed in seeds():
         seq, steps, walk, _ = expected(rt, oracle, seed)
-        if (seq.W, seq.H) in done:
+        key = (seq.W, seq.H, any(s.kind == "robust_denoise" and st == 0 for s, (st, _, _) in zip(steps, walk)))
+        if key in done:                                                # per size: the first sequence, and the first in which rtgl_robust_denoise is accepted
             continue
-        done.add((seq.W, seq.H))
+        done.add(key)
         tensor = torch.zeros((seq.H, seq.W, 4), dtype=torch.float32, device=dev)
         side = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(side):
@@ -358,7 +367,9 @@ def test_bound_image_on_a_torch_stream_changes_nothing(rt, oracle):
         ctx.close()
         bad += len(lines)
     print(f"bound image: {len(done)} sequences, {time.perf_counter() - t0:.2f} s", flush=True)
-    assert bad == 0 and len(done) == min(len(ps.SIZES), len(seeds())), f"{bad} differing steps (see the lines printed above)"
+    assert bad == 0 and len({k[:2] for k in done}) == min(len(ps.SIZES), len(seeds())), f"{bad} differing steps (see the lines printed above)"
+    if len(seeds()) >= len(ps.ROWS):
+        assert sum(k[2] for k in done) == len(ps.SIZES), "rtgl_robust_denoise on a torch stream at every size"
 
 
 def test_a_tiled_context_refuses_or_works_as_the_header_says(rt, oracle):
@@ -367,13 +378,13 @@ def test_a_tiled_context_refuses_or_works_as_the_header_says(rt, oracle):
     t0, bad, n, robust_ok, refused = time.perf_counter(), 0, 0, 0, 0
     tiling = dict(rank=1, world=2, strip_rows=8)
     for seed in seeds():
-        if ps.size_of(seed) != (48, 40) or n == 3:
+        if ps.size_of(seed) != (48, 40) or n == ps.DEFAULT_SEQUENCES // len(ps.SIZES):
             continue
         n += 1
         seq, steps, walk, rows = expected(rt, oracle, seed, tiling)
         assert len(rows) == 16 and (rows == np.r_[8:16, 24:32]).all()
         for s, (st, out, _) in zip(steps, walk):
-            if s.kind in ("denoise", "denoise_guided", "temporal_accumulate", "temporal_clip", "tonemap", "error_estimate", "robust_error_estimate") or s.kind.startswith("adaptive"):
+            if s.kind in ("denoise", "denoise_guided", "temporal_accumulate", "temporal_clip", "tonemap", "error_estimate", "robust_error_estimate", "robust_denoise") or s.kind.startswith("adaptive"):
                 assert st in (pm.STATE, pm.INVALID), (s.kind, st)
                 refused += st == pm.STATE
             robust_ok += st == 0 and s.kind in ("robust_accumulate", "robust_resolve")

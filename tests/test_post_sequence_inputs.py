@@ -13,6 +13,8 @@ import error_inputs as ei
 import error_mirror as em
 import post_sequence_inputs as ps
 import post_sequence_model as pm
+import robust_denoise_inputs as rdi
+import robust_denoise_mirror as rdm
 import robust_error_mirror as rem
 import robust_inputs as ri
 import robust_mirror as rm
@@ -92,9 +94,37 @@ def test_every_alphabet_entry_and_every_hazard_twice(start):
     assert all(ps.MIN_STEPS <= len(q.steps) <= ps.MAX_STEPS for q in seqs)
 
 
-def test_three_default_sequences_per_size():
+def test_five_default_sequences_per_size():
     sizes = [(q.W, q.H) for q in (ps.sequence(s) for s in ps.default_seeds())]
-    assert sorted(set(sizes)) == sorted(ps.SIZES) and all(sizes.count(s) == 3 for s in ps.SIZES)
+    assert sorted(set(sizes)) == sorted(ps.SIZES) and all(sizes.count(s) == 5 for s in ps.SIZES)
+    assert ps.DEFAULT_SEQUENCES == len(ps.ROWS) == 5 * len(ps.SIZES)
+
+
+def test_the_robust_denoise_hazards_read_the_context_as_the_model_does():
+    """the predicates of post_sequence_inputs.RD_HAZARDS work out from the steps whether a call is accepted; the model says the same of
+    every one, so a hazard that is met is met with the statuses its name promises"""
+    n = accepted = 0
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        for c in ps._rd_calls(seq.steps):
+            assert (walk[c.i][0] == 0) == ps._rd_accepted(c), (seed, c.i)
+            assert walk[c.i][0] in (0, pm.STATE)
+            n += 1
+            accepted += walk[c.i][0] == 0
+    # six of the hazards ask for a refusal (three restarts, N < K, after robust_end, a second begin), each in two sequences; every one of
+    # the nineteen asks for an accepted call, some share one
+    assert n - accepted >= 12 and accepted >= 24, (n, accepted)
+
+
+def test_the_buckets_of_an_accepted_robust_denoise_differ_for_every_K():
+    """a fill that folded one frame K times would give v0 = 0 everywhere and a filter with nothing to go by"""
+    spread = {K: 0 for K in ps.BUCKETS}
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        for s, (status, out, _) in zip(seq.steps, walk):
+            if s.kind == "robust_denoise" and status == 0:
+                spread[out["robust_frames"][1]] += bool((out["variance"][..., 1] != 0).any())
+    assert all(spread[K] >= 1 for K in ps.BUCKETS), spread
 
 
 def test_both_refusal_classes_are_predicted_for_every_feature():
@@ -272,3 +302,51 @@ def test_the_robust_session_alone(K):
         assert same(a["robust_output"], alone.resolve(gain)) and same(c["image"], alone.resolve(gain, rm.DEST_IMAGE))
         assert em.same_result(b["robust_error_summary"], rem.estimate(alone.planes, alone.N, gain=gain)) == []
         assert c["robust_frames"] == (alone.N, K)
+
+
+@pytest.mark.parametrize("K", rm.BUCKETS)
+def test_robust_denoise_alone(K):
+    """begin, frames and folds, rtgl_robust_denoise: what robust_denoise_mirror gives when fed robust_mirror.Session's planes; the three
+    RTGL_ERR_STATE reasons and RTGL_ERR_INVALID"""
+    for buckets, guides in (("ragged", "benign"), ("specials", "edges")):
+        case = rdi.make(buckets, guides, H, W, K)
+        alb, nrm, pos = case["albedo"], case["normal"], case["position"]
+        frames = [dict(image=s, planes=planes_of(alb, nrm, pos)) for s in case["samples"]]
+        call = lambda **over: S("robust_denoise", **dict(rdm.DEFAULTS, **over))
+        alone = rm.Session(H, W, K)
+        steps = [S("set_aov", mask=7), call(), S("robust_begin", buckets=K)]
+        want = [None, pm.STATE, None]                                  # no session
+        for k, smp in enumerate(case["samples"]):
+            steps += [render(), S("robust_accumulate"), call(passes=1)]
+            alone.accumulate(smp)
+            want += [None, None, rdm.robust_denoise(alone.planes, alone.N, alb, nrm, pos, **dict(rdm.DEFAULTS, passes=1)) if k + 1 >= K else pm.STATE]      # N < K
+        for ps_ in case["params"]:
+            for passes in rdi.PASSES:
+                steps.append(call(passes=passes, **ps_))
+                want.append(rdm.robust_denoise(alone.planes, alone.N, alb, nrm, pos, **dict(rdm.DEFAULTS, passes=passes, **ps_)))
+        steps += [call(passes=9), call(sigma_lum=0.0), call(gain=-1.0), call(sigma_normal=float("inf")), S("set_aov", mask=5), call(),
+                  call(sigma_normal=0.0), render(), call(sigma_normal=0.0), S("set_aov", mask=0), call(sigma_normal=0.0, sigma_position=0.0, demodulate=False),
+                  S("robust_end"), call(sigma_normal=0.0, sigma_position=0.0, demodulate=False)]
+        plain = dict(rdm.DEFAULTS, sigma_normal=0.0, sigma_position=0.0, demodulate=False)
+        want += [pm.INVALID] * 4 + [None, pm.STATE,                    # the normal plane is not enabled
+                                    pm.STATE, None,                    # the planes restarted
+                                    rdm.robust_denoise(alone.planes, alone.N, alb, None, pos, **dict(rdm.DEFAULTS, sigma_normal=0.0)), None,
+                                    rdm.robust_denoise(alone.planes, alone.N, **plain),      # no plane needed: the restart does not refuse
+                                    None, pm.STATE]
+        walk = drive(pm.PostModel(H, W), steps, frames + [frames[-1]])
+        assert len(walk) == len(want)
+        last, checked = None, 0
+        for k, ((status, out, _), w) in enumerate(zip(walk, want)):
+            if w is None:
+                assert status == 0, k
+            elif isinstance(w, int):
+                assert status == w, (k, status, w)
+            else:
+                assert status == 0 and same(out["denoised"], w[0]) and same(out["variance"], w[1]), k
+                last, checked = w, checked + 1
+                continue
+            if last is not None:                                       # a refused call, and every other one, leaves the two buffers as they were
+                assert same(out["denoised"], last[0]) and same(out["variance"], last[1]), k
+        assert checked >= len(case["samples"]) - K + 1 + len(case["params"]) * len(rdi.PASSES) + 2
+        tiled = drive(pm.PostModel(H, W, tiled=True), steps[:3 + 3 * K], frames)
+        assert all(status == pm.STATE for (status, _, _), s in zip(tiled, steps) if s.kind == "robust_denoise")
