@@ -727,6 +727,136 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
+    // ---- robust adaptive sampling (rtgl_robust_adaptive_*, include/rtgl_amd.h; extension): a session whose sample count is per 16 x 16 tile
+    // and whose samples go into bucket means: frames trace only the tiles that are still noisy, and fireflies decide neither the picture nor
+    // when a tile stops.  It holds its own buffers beside an adaptive and a robust session and does not touch the image.
+    // robust_adaptive_begin() opens a session (nullptr: the defaults, buckets 8, threshold 0.05, floor 0.01, gain 1, min_samples 32,
+    // max_samples 1024, flags 0); robust_adaptive_frame() renders one sample over the active tiles with the uniforms render() would send (one
+    // rand() per frame; the frame count is not advanced and a pending reset_buffer() stays pending for the next render()) and folds it into
+    // the bucket of each tile's next sample; robust_adaptive_accumulate() folds the image as it stands; robust_adaptive_update() estimates
+    // the tiles whose count has moved, sets the mask and returns the summary; robust_adaptive_resolve() writes the trimmed mean, every pixel
+    // with its tile's count (nullptr: the defaults, gain 1, dest 0, flags 0), to the session's output plane (read_robust_adaptive()) or, with
+    // dest RTGL_ROBUST_DEST_IMAGE, to the accumulation image; robust_adaptive_end() frees the buffers.  Each prints and returns false on failure.
+    bool robust_adaptive_begin(const rtgl_robust_adaptive_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        rtgl_robust_adaptive_params p;
+        rtgl_robust_adaptive_defaults(&p);
+        if (params) p = *params;
+        const int rc = rtgl_robust_adaptive_begin(m_ctx, &p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_adaptive_frame()
+    {
+        if (!m_ctx) return false;
+        const rtgl_frame_params p = frame_params(0, 0);        // (rtgl_robust_adaptive_frame ignores frames and reset_flag)
+        int rc = rtgl_set_frame_params(m_ctx, &p);
+        if (rc == RTGL_OK) rc = rtgl_robust_adaptive_frame(m_ctx);
+        if (rc == RTGL_OK) record(p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_adaptive_accumulate()
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_adaptive_accumulate(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_adaptive_update(rtgl_adaptive_summary *summary = nullptr)
+    {
+        rtgl_adaptive_summary s{};
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_adaptive_update(m_ctx, &s);
+        check(rc);
+        if (summary) *summary = s;
+        return rc == RTGL_OK;
+    }
+    // the mask, ceil(width / 16) x ceil(height / 16) bytes, row by row, non-zero = active; set: until the next robust_adaptive_update()
+    bool robust_adaptive_set_mask(const std::vector<uint8_t> &tiles)
+    {
+        if (!m_ctx || tiles.size() != (size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16)) return false;
+        const int rc = rtgl_robust_adaptive_set_mask(m_ctx, tiles.data());
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    std::vector<uint8_t> robust_adaptive_get_mask() const
+    {
+        if (!m_ctx) return {};
+        std::vector<uint8_t> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
+        if (rtgl_robust_adaptive_get_mask(m_ctx, tiles.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
+    bool robust_adaptive_resolve(const rtgl_robust_resolve_params *params = nullptr)
+    {
+        if (!m_ctx) return false;
+        rtgl_robust_resolve_params p;
+        rtgl_robust_defaults(nullptr, &p);
+        if (params) p = *params;
+        const int rc = rtgl_robust_adaptive_resolve(m_ctx, &p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool robust_adaptive_end()
+    {
+        if (!m_ctx) return false;
+        const int rc = rtgl_robust_adaptive_end(m_ctx);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    // the output plane of the latest robust_adaptive_resolve() with dest RTGL_ROBUST_DEST_BUFFER, RGBA32F, row 0 = bottom, a = the Gini
+    // coefficient of the pixel's bucket luminances; empty (and a message) before one
+    std::vector<float> read_robust_adaptive() const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_robust_adaptive_f32(m_ctx, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // the mean of the samples bucket j holds, RGBA32F
+    std::vector<float> read_robust_adaptive_bucket(uint32_t j) const
+    {
+        if (!m_ctx) return {};
+        std::vector<float> img((size_t)m_width * rtgl_local_rows(m_ctx) * 4);
+        if (rtgl_read_robust_adaptive_bucket_f32(m_ctx, j, img.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return img;
+    }
+    // the session's tile records, row by row; empty (and a message) without a session
+    std::vector<rtgl_adaptive_tile> read_robust_adaptive_tiles() const
+    {
+        if (!m_ctx) return {};
+        std::vector<rtgl_adaptive_tile> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
+        if (rtgl_read_robust_adaptive_tiles(m_ctx, tiles.data(), nullptr, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
+    // "render until every tile of the picture without its fireflies is this clean": a robust adaptive session of masked frames with a
+    // robust_adaptive_update() after every check_every of them, until no tile is active (each is at or below `threshold`, a relative RMSE of
+    // the picture resolved with `gain`, or holds max_samples samples) or m_quit is set; then robust_adaptive_resolve() with the same gain.
+    // min_samples 0: the default.  Returns the frames rendered; `summary` (if not null) receives the latest summary; with to_image the
+    // accumulation image holds the picture, otherwise read_robust_adaptive() gives it.
+    long render_robust_adaptive(float threshold, uint32_t max_samples, uint32_t min_samples = 0, long check_every = 16, uint32_t buckets = 8, float gain = 1.0f,
+                                bool to_image = false, rtgl_adaptive_summary *summary = nullptr)
+    {
+        rtgl_robust_adaptive_params p;
+        rtgl_robust_resolve_params rp;
+        rtgl_robust_adaptive_defaults(&p);
+        rtgl_robust_defaults(nullptr, &rp);
+        p.buckets = buckets; p.threshold = threshold; p.gain = gain; p.max_samples = max_samples;
+        if (min_samples) p.min_samples = min_samples;
+        rp.gain = gain; rp.dest = to_image ? RTGL_ROBUST_DEST_IMAGE : RTGL_ROBUST_DEST_BUFFER;
+        rtgl_adaptive_summary s{};
+        long done = 0;
+        bool ok = check_every > 0 && robust_adaptive_begin(&p) && robust_adaptive_update(&s);
+        const bool begun = ok;
+        while (ok && !m_quit && !s.converged) {
+            for (long i = 0; ok && i < check_every; ++i) { ok = robust_adaptive_frame(); if (ok) ++done; }
+            ok = ok && robust_adaptive_update(&s);
+        }
+        if (begun) robust_adaptive_resolve(&rp);
+        if (summary) *summary = s;
+        return done;
+    }
     // the history, RGBA32F, row 0 = bottom, a = the history length; empty (and a message) before the first successful temporal_accumulate()
     std::vector<float> read_temporal() const
     {

@@ -865,6 +865,94 @@ typedef struct rtgl_robust_denoise_params {
 } rtgl_robust_denoise_params; /* 32 bytes */
 int rtgl_robust_denoise_defaults(rtgl_robust_denoise_params *out);
 int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_params *params);
+
+/* -- robust adaptive sampling: a session whose sample count is per 16 x 16 tile AND whose samples go into K bucket means.  Adaptive
+ * sampling spends frames only where the picture is noisy but keeps every firefly in a running mean and stops on two moments of that mean;
+ * a robust session removes the fireflies and estimates the noise of the picture it makes, but traces the whole picture every frame.  This
+ * is the third kind of session, next to those two: masked frames (the ordinary per-bounce pipeline behind a block list, as in adaptive
+ * sampling) folded into the bucket of each tile's own next sample, the spread estimate per tile whose count has moved, the mask rule of
+ * adaptive sampling, and a resolve that takes every pixel's N from its tile.  No reference counterpart.  No existing kernel, option or
+ * entry point changes; rtgl_adaptive_tile, rtgl_adaptive_summary and rtgl_robust_resolve_params are reused as they are.  DEFINED bit for
+ * bit under the rules of its neighbours (tests/robust_adaptive_mirror.py restates it): binary32, one rounding per operation in the order
+ * written, no contraction, correctly rounded divide, subnormals kept, integers exact; (float) of every count is exact (max_samples <=
+ * 2^24).  Where a result is a NaN is defined; the NaN's sign and payload are not.
+ *   Shapes, footprint, tiles and blocks are those of adaptive sampling.  Single-device, untiled contexts only.
+ *   State of a session, all of it the session's own, allocated by rtgl_robust_adaptive_begin and freed by rtgl_robust_adaptive_end: K
+ *   bucket planes of the image's size (float4, bucket-major), a count n[t] and an estimate count m[t] per tile, the tile records, a sample
+ *   buffer and an output plane of the image's size; on the host the mask active[t], the block list and the tile list.  The session is
+ *   independent of an adaptive session and of a robust session: either may be open beside it, and neither is read or written.  The events
+ *   that end an adaptive session do not end this one: only rtgl_robust_adaptive_end does.
+ *   rtgl_robust_adaptive_begin validates the parameters, allocates what is missing (a second begin restarts the session and reallocates
+ *   only if K changed), zeroes the buckets, n, m and the records and sets active every tile that holds a footprint pixel.  It does not
+ *   touch the image.
+ *   rtgl_robust_adaptive_frame renders one frame of one sample over the active tiles, exactly as rtgl_adaptive_frame does (the same
+ *   uniforms taken and ignored, the same block indirection, the same sample for an active pixel whatever the mask, RTGL_KERNEL_WAVEFRONT
+ *   where the effective kernel would be RTGL_KERNEL_MEGA, no kept camera bits used or left), traced with reset_flag = 1, frames = 0 into
+ *   the session's sample buffer, and then runs the FOLD with that buffer as the source.  It writes neither the image nor anything of
+ *   rtgl_error_estimate.  With an empty list the call enqueues nothing and returns RTGL_OK.  Frames a batching context holds are submitted
+ *   first.  rtgl_last_frame_ms covers generation through the fold.
+ *   The FOLD: per active tile t and per footprint pixel of it, with n = n[t], j = n mod K, k = n div K, x the source pixel and b the pixel
+ *   of bucket j:
+ *     b' = (x + b (float)k) / (float)(k + 1) per component, w included        (rtgl_robust_accumulate's operations)
+ *   then n[t] = n + 1.  Pixels of inactive tiles and pixels outside the footprint are not written.
+ *   rtgl_robust_adaptive_accumulate submits held frames, then runs the fold with the accumulation image AS IT STANDS as the source: for
+ *   frames the caller rendered some other way.
+ *   rtgl_robust_adaptive_update first runs, per tile with n != m:
+ *     n < K:  the record is {0, 0, 0, 0, n, n}: not valid.
+ *     n >= K: steps 1-9 of rtgl_robust_error_estimate per footprint pixel, with the session's gain and floor (t is never zeroed: every
+ *       bucket holds a sample; the buckets are taken as equally weighted);  sum = the e of the pixels that count by the 256-leaf tree over
+ *       the tile's row-major indices, the others and positions outside the footprint contributing +0;  count = the counting pixels;
+ *       mse = sum / (float)count;  converged = count > 0 and mse <= threshold threshold;  count == 0: {0, 0, 0, 0}.  The record is
+ *       {sum, mse, count, converged, n, n}; it is VALID iff count > 0.
+ *     In both cases m = n afterwards.
+ *   A tile with n == m keeps its record and is not read: a stopped tile costs nothing per update.
+ *   It then synchronises, reads the records, sets the mask by the rule of rtgl_adaptive_update with min_samples and max_samples, rebuilds
+ *   and uploads the lists and fills the summary as rtgl_adaptive_update does.
+ *   rtgl_robust_adaptive_set_mask, rtgl_robust_adaptive_get_mask and rtgl_read_robust_adaptive_tiles behave as their rtgl_adaptive_*
+ *   namesakes, on this session.  rtgl_device_robust_adaptive_tiles: the records on the device, valid until rtgl_robust_adaptive_end; NULL
+ *   without a session.
+ *   rtgl_robust_adaptive_resolve, per pixel of the image, with N = n[t] of the pixel's tile:
+ *     a pixel outside the footprint, or with N == 0, gets {+0, +0, +0, +0} (G = +0);
+ *     otherwise steps 1-9 of rtgl_robust_resolve with that N: n_j = N div K + (j < N mod K ? 1 : 0), t = 0 while N < K, empty buckets
+ *     not kept.
+ *   dest = RTGL_ROBUST_DEST_BUFFER stores {out.x, out.y, out.z, G} in the session's output plane, which rtgl_read_robust_adaptive_f32
+ *   reads; nothing else changes.  dest = RTGL_ROBUST_DEST_IMAGE stores all four components in the accumulation image and does on the host
+ *   exactly what rtgl_robust_resolve with dest IMAGE does: an adaptive session ends, the snapshot of rtgl_error_estimate is dropped.  The
+ *   session goes on after either.
+ *   rtgl_read_robust_adaptive_bucket_f32 copies the plane of one bucket (synchronises).
+ * Defaults (rtgl_robust_adaptive_defaults): buckets 8, threshold 0.05, floor 0.01, gain 1, min_samples 32, max_samples 1024, flags 0.
+ * RTGL_ERR_INVALID: NULL context, params or output pointer; buckets not 4, 8 or 16; threshold or floor not finite or not > 0; gain NaN,
+ * negative or infinite; min_samples < K; max_samples < min_samples or > 16777216; non-zero flags or reserved; bucket >= K; dest > 1; at
+ * rtgl_robust_adaptive_frame: samples != 1 or max_bounce == 0 in the frame parameters.
+ * RTGL_ERR_STATE: no session (every call but begin and defaults); a tiled or multi-device context; rtgl_read_robust_adaptive_f32 before a
+ * resolve with dest BUFFER; rtgl_robust_adaptive_frame without frame parameters or with option "aov" or "rng_state" non-zero.
+ * Every refusal sets a text in rtgl_last_error that names the call.
+ * Limits: those of both parents -- the trim loses energy where it trims; the estimate reads low while a firefly has not been drawn, so
+ * min_samples matters; a stopped tile is never re-examined; seams between tiles of different counts; rtgl_robust_denoise and
+ * rtgl_robust_error_estimate serve the plain robust session only; memory is 16 (K + 2) bytes per pixel. */
+typedef struct rtgl_robust_adaptive_params {
+    uint32_t buckets;            /* K: 4, 8 or 16 */
+    float    threshold;          /* > 0, finite: relative RMSE at or below which a tile stops */
+    float    floor;              /* > 0, finite */
+    float    gain;               /* finite, >= 0: the resolve's gain; the estimate is of THAT picture */
+    uint32_t min_samples;        /* >= K */
+    uint32_t max_samples;        /* min_samples .. 16777216, so that (float) of every count is exact */
+    uint32_t flags;              /* none defined: must be 0 */
+    uint32_t reserved;           /* must be 0 */
+} rtgl_robust_adaptive_params;   /* 32 bytes */
+int rtgl_robust_adaptive_defaults(rtgl_robust_adaptive_params *out);
+int rtgl_robust_adaptive_begin(rtgl_context *ctx, const rtgl_robust_adaptive_params *params);
+int rtgl_robust_adaptive_frame(rtgl_context *ctx);
+int rtgl_robust_adaptive_accumulate(rtgl_context *ctx);
+int rtgl_robust_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summary *summary_out);
+int rtgl_robust_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles);
+int rtgl_robust_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles);
+int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params);
+int rtgl_robust_adaptive_end(rtgl_context *ctx);
+int rtgl_read_robust_adaptive_f32(rtgl_context *ctx, float *rgba);
+int rtgl_read_robust_adaptive_bucket_f32(rtgl_context *ctx, uint32_t bucket, float *rgba);
+int rtgl_read_robust_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty);
+void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
  * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads

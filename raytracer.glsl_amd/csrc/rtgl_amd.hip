@@ -30,6 +30,8 @@
 #include "rt_robust_plan.hpp"
 #include "rt_spread.hpp"
 #include "rt_spread_plan.hpp"
+#include "rt_robust_tiles.hpp"
+#include "rt_robust_tiles_plan.hpp"
 #include "rt_bucket_guide.hpp"
 #include "rt_bucket_guide_plan.hpp"
 #include "rt_node_walk.hpp"
@@ -331,6 +333,13 @@ struct rtgl_context {
     // rtgl_robust_error_estimate (rt_spread.hpp, rt_spread_plan.hpp): the tile records and the summary of the session, allocated by its
     // first estimate and freed by rtgl_robust_end.  has_rb_error: an estimate of THIS session has succeeded
     uint4 *d_rbe_tiles = nullptr; uint32_t *d_rbe_summary = nullptr; bool has_rb_error = false;
+    // a robust adaptive session (rt_robust_tiles.hpp, rt_robust_tiles_plan.hpp), allocated by rtgl_robust_adaptive_begin and freed by
+    // rtgl_robust_adaptive_end: the ra_K bucket planes (bucket-major), the sample buffer a masked frame traces into, the output plane, the
+    // tile records, the counts (n per tile, then m per tile) and the two lists (the active blocks, then the active tiles).  ra_active: a
+    // session is open; ra_resolved: the output plane holds a resolve; the mask and the lists as they are on the device
+    float4 *d_ra_buckets = nullptr, *d_ra_samples = nullptr, *d_ra_out = nullptr; uint4 *d_ra_records = nullptr; uint32_t *d_ra_counts = nullptr, *d_ra_lists = nullptr;
+    uint32_t ra_K = 0; bool ra_active = false, ra_resolved = false; rt_robust_tiles_plan::Params ra_params{};
+    std::vector<uint8_t> ra_mask; std::vector<uint32_t> ra_blocks, ra_tiles;
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -2431,17 +2440,18 @@ extern "C" int rtgl_adaptive_defaults(rtgl_adaptive_params *out)
 static_assert(sizeof(rtgl_adaptive_params) == 32 && sizeof(rtgl_adaptive_tile) == sizeof(rt_adaptive_plan::Tile) && sizeof(rtgl_adaptive_summary) == sizeof(rt_adaptive_plan::Summary)
               && offsetof(rtgl_adaptive_summary, samples_total) == offsetof(rt_adaptive_plan::Summary, samples_total) && rt_adaptive_plan::kTile == kErrTile, "the layouts of the header");
 
-// the mask as it stands -> the two lists on the device (the active blocks, then the active tiles); synchronises: the host vectors are free again
-static int adaptive_upload_lists(rtgl_context *ctx)
+// a mask as it stands -> its two lists on the device (the active blocks, then the active tiles); synchronises: the host vectors are free again
+static int upload_tile_lists(rtgl_context *ctx, const std::vector<uint8_t> &mask, std::vector<uint32_t> &blocks, std::vector<uint32_t> &tiles, uint32_t *d_lists)
 {
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    rt_adaptive_plan::build_lists(sh, ctx->ad_mask, ctx->ad_blocks, ctx->ad_tiles);
+    rt_adaptive_plan::build_lists(sh, mask, blocks, tiles);
     const size_t n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
-    if (!ctx->ad_blocks.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ad_lists, ctx->ad_blocks.data(), ctx->ad_blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (!ctx->ad_tiles.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ad_lists + n_blocks, ctx->ad_tiles.data(), ctx->ad_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!blocks.empty()) HIPCHK(ctx, hipMemcpyAsync(d_lists, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!tiles.empty()) HIPCHK(ctx, hipMemcpyAsync(d_lists + n_blocks, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RTGL_OK;
 }
+static int adaptive_upload_lists(rtgl_context *ctx) { return upload_tile_lists(ctx, ctx->ad_mask, ctx->ad_blocks, ctx->ad_tiles, ctx->d_ad_lists); }
 
 extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params *params)
 {
@@ -2477,16 +2487,11 @@ extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params
     return RTGL_OK;
 }
 
-extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
+// One masked frame (rt_adaptive.hpp): the blocks of `list` (n0 = 64 x its length > 0) traced as a one-frame image into `samples`, from the
+// start event of rtgl_last_frame_ms up to the last kernel of the pipeline.  The caller has checked the frame parameters; it folds the
+// sample buffer and records the end event.
+static int masked_frame(rtgl_context *ctx, float4 *samples, const uint32_t *list, uint32_t n0)
 {
-    ENTER(ctx);
-    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
-    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
-    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
-    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
-    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: max_bounce must be > 0");
-    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
-    if (ctx->ad_blocks.empty()) return RTGL_OK;
     if (ctx->visits_dirty) RCCHK(rebuild_sphere_visits(ctx));
     if (ctx->tris_dirty) RCCHK(rebuild_triangles(ctx));
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
@@ -2497,11 +2502,10 @@ extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
     if (!ctx->d_env) P.use_envmap = 0;
     P.frames = 0; P.reset_flag = 1;
     ImageView im{};
-    im.pixels = ctx->d_ad_samples; im.width = ctx->width; im.height = ctx->height;
+    im.pixels = samples; im.width = ctx->width; im.height = ctx->height;
     im.disp_w = sh.fw; im.disp_h = sh.fh;
     im.local_rows = ctx->local_rows; im.rank = ctx->rank; im.world = ctx->world; im.strip_rows = ctx->strip_rows;
     if (ctx->opt_counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
-    const uint32_t n0 = (uint32_t)ctx->ad_blocks.size() * 64u;
     // the per-bounce pipeline whatever the scene: where an ordinary frame would take the megakernel, RTGL_KERNEL_WAVEFRONT
     const int effective = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt_kernel;
     const int saved_kernel = ctx->opt_kernel;
@@ -2515,11 +2519,25 @@ extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
         rc = (int)hipEventRecord(ctx->ev0, ctx->stream) ? fail(ctx, RTGL_ERR_DEVICE, "hipEventRecord failed") : RTGL_OK;
     }
     if (!rc) {
-        rc = launch_wavefront(ctx, sc, frames, im, n0, nullptr, nullptr, ctx->d_ad_lists);
+        rc = launch_wavefront(ctx, sc, frames, im, n0, nullptr, nullptr, list);
         if (rc) ctx->keep0_valid = false;                 // (as in render_batch: a frame that failed half way vouches for nothing it left behind)
     }
     ctx->opt_kernel = saved_kernel;
-    if (rc) return rc;
+    return rc;
+}
+
+extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
+    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
+    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
+    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: max_bounce must be > 0");
+    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
+    if (ctx->ad_blocks.empty()) return RTGL_OK;
+    RCCHK(masked_frame(ctx, ctx->d_ad_samples, ctx->d_ad_lists, (uint32_t)ctx->ad_blocks.size() * 64u));
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
     AdaptiveMergeArgs a{};
     a.image = ctx->d_image; a.samples = ctx->d_ad_samples; a.n = ctx->d_ad_counts;
     a.tiles = ctx->d_ad_lists + (size_t)sh.blocks_x * sh.blocks_y;
@@ -2792,6 +2810,221 @@ extern "C" void *rtgl_device_robust_error_tiles(rtgl_context *ctx)
     if (!ctx) return nullptr;
     if (!ctx->rb_active || !ctx->has_rb_error) { ctx->error = std::string("rtgl_device_robust_error_tiles") + kNoRobustError; return nullptr; }
     return (void *)ctx->d_rbe_tiles;
+}
+
+// ---- a robust adaptive session: masked frames folded into per-tile bucket means (rt_robust_tiles.hpp, rt_robust_tiles_plan.hpp) ------------
+static_assert(sizeof(rtgl_robust_adaptive_params) == sizeof(rt_robust_tiles_plan::Params) && offsetof(rtgl_robust_adaptive_params, gain) == offsetof(rt_robust_tiles_plan::Params, gain)
+              && offsetof(rtgl_robust_adaptive_params, max_samples) == offsetof(rt_robust_tiles_plan::Params, max_samples), "the layouts of the header");
+
+extern "C" int rtgl_robust_adaptive_defaults(rtgl_robust_adaptive_params *out)
+{
+    if (!out) return RTGL_ERR_INVALID;
+    const rt_robust_tiles_plan::Params p = rt_robust_tiles_plan::default_params();
+    memcpy(out, &p, sizeof p);
+    return RTGL_OK;
+}
+
+static int robust_adaptive_upload_lists(rtgl_context *ctx) { return upload_tile_lists(ctx, ctx->ra_mask, ctx->ra_blocks, ctx->ra_tiles, ctx->d_ra_lists); }
+
+extern "C" int rtgl_robust_adaptive_begin(rtgl_context *ctx, const rtgl_robust_adaptive_params *params)
+{
+    ENTER(ctx);
+    if (!params) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_begin: params is NULL");
+    rt_robust_tiles_plan::Params P;
+    memcpy(&P, params, sizeof P);
+    if (const char *why = rt_robust_tiles_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_adaptive_begin: ") + why);
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_begin: a tiled or multi-device context holds strips, and the tiles are the whole picture's (out of scope): render on a single-device context");
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t px = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height), n_tiles = (size_t)sh.tx * sh.ty, n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
+    if ((uint64_t)n_blocks * 64ull > 0xFFFFFFF0ull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_begin: the footprint does not fit 32-bit ray slots");
+    if (ctx->ra_active) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (work in flight uses the planes and the lists)
+    ctx->ra_active = false; ctx->ra_resolved = false;
+    if (ctx->ra_K != P.buckets) { RCCHK(buf_release(ctx, ctx->d_ra_buckets)); ctx->ra_K = 0; }
+    RCCHK(buf_ensure(ctx, ctx->d_ra_buckets, rt_robust_tiles_plan::bucket_bytes(px, P.buckets)));
+    ctx->ra_K = P.buckets;
+    RCCHK(buf_ensure(ctx, ctx->d_ra_samples, rt_robust_tiles_plan::plane_bytes(px)));
+    RCCHK(buf_ensure(ctx, ctx->d_ra_out, rt_robust_tiles_plan::plane_bytes(px)));
+    RCCHK(buf_ensure(ctx, ctx->d_ra_records, rt_robust_tiles_plan::record_bytes(n_tiles)));
+    RCCHK(buf_ensure(ctx, ctx->d_ra_counts, rt_robust_tiles_plan::count_bytes(n_tiles)));
+    RCCHK(buf_ensure(ctx, ctx->d_ra_lists, rt_robust_tiles_plan::list_bytes(n_blocks, n_tiles)));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_buckets, 0, rt_robust_tiles_plan::bucket_bytes(px, P.buckets), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_samples, 0, rt_robust_tiles_plan::plane_bytes(px), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_out, 0, rt_robust_tiles_plan::plane_bytes(px), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_records, 0, rt_robust_tiles_plan::record_bytes(n_tiles), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_counts, 0, rt_robust_tiles_plan::count_bytes(n_tiles), ctx->stream));
+    ctx->ra_params = P;
+    rt_adaptive_plan::explicit_mask(sh, std::vector<uint8_t>(n_tiles, 1).data(), ctx->ra_mask);
+    RCCHK(robust_adaptive_upload_lists(ctx));
+    ctx->ra_active = true;
+    return RTGL_OK;
+}
+
+static const char *const kNoRobustAdaptiveSession = ": no session (rtgl_robust_adaptive_begin has not been called, or rtgl_robust_adaptive_end has)";
+
+// the fold of `source` into the bucket of every active tile's next sample; nothing with an empty list
+static int robust_adaptive_fold(rtgl_context *ctx, const float4 *source)
+{
+    if (ctx->ra_tiles.empty()) return RTGL_OK;
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    TileBucketsFoldArgs a{};
+    a.source = source; a.buckets = ctx->d_ra_buckets; a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height);
+    a.n = ctx->d_ra_counts; a.tiles = ctx->d_ra_lists + (size_t)sh.blocks_x * sh.blocks_y; a.K = ctx->ra_K;
+    a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh; a.tx = sh.tx;
+    hipLaunchKernelGGL(tile_buckets_fold_kernel, dim3((unsigned)ctx->ra_tiles.size()), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_adaptive_frame(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_frame") + kNoRobustAdaptiveSession);
+    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_frame: rtgl_set_frame_params has not been called");
+    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
+    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
+    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_frame: max_bounce must be > 0");
+    if (ctx->ra_blocks.empty()) return RTGL_OK;
+    RCCHK(masked_frame(ctx, ctx->d_ra_samples, ctx->d_ra_lists, (uint32_t)ctx->ra_blocks.size() * 64u));
+    RCCHK(robust_adaptive_fold(ctx, ctx->d_ra_samples));
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->timed = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_adaptive_accumulate(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_accumulate") + kNoRobustAdaptiveSession);
+    return robust_adaptive_fold(ctx, ctx->d_image);
+}
+
+extern "C" int rtgl_robust_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summary *summary_out)
+{
+    ENTER(ctx);
+    if (!summary_out) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_update: summary_out is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_update") + kNoRobustAdaptiveSession);
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t n_tiles = (size_t)sh.tx * sh.ty;
+    TileBucketsEstimateArgs a{};
+    a.buckets = ctx->d_ra_buckets; a.records = ctx->d_ra_records; a.n = ctx->d_ra_counts; a.m = ctx->d_ra_counts + n_tiles;
+    a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height);
+    a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh;
+    a.gain = ctx->ra_params.gain; a.floor_ = ctx->ra_params.floor; a.threshold = ctx->ra_params.threshold;
+    const dim3 grid((unsigned)sh.tx, (unsigned)sh.ty);
+    if (ctx->ra_K == 4u) hipLaunchKernelGGL(tile_buckets_estimate_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
+    else if (ctx->ra_K == 8u) hipLaunchKernelGGL(tile_buckets_estimate_kernel<8>, grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(tile_buckets_estimate_kernel<16>, grid, dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<rt_adaptive_plan::Tile> records(n_tiles);
+    HIPCHK(ctx, hipMemcpyAsync(records.data(), ctx->d_ra_records, n_tiles * sizeof(rt_adaptive_plan::Tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t t = 0; t < (uint32_t)n_tiles; ++t) ctx->ra_mask[t] = rt_adaptive_plan::active(sh, t, records[t], ctx->ra_params.min_samples, ctx->ra_params.max_samples) ? 1 : 0;
+    RCCHK(robust_adaptive_upload_lists(ctx));
+    const rt_adaptive_plan::Summary s = rt_adaptive_plan::summary(sh, records.data(), ctx->ra_mask, (uint32_t)ctx->ra_blocks.size(), ctx->ra_params.max_samples);
+    memcpy(summary_out, &s, sizeof s);
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_set_mask: tiles is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_set_mask") + kNoRobustAdaptiveSession);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (frames in flight read the lists about to be replaced)
+    rt_adaptive_plan::explicit_mask(rt_adaptive_plan::shape(ctx->width, ctx->height), tiles, ctx->ra_mask);
+    return robust_adaptive_upload_lists(ctx);
+}
+
+extern "C" int rtgl_robust_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_get_mask: tiles is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_get_mask") + kNoRobustAdaptiveSession);
+    memcpy(tiles, ctx->ra_mask.data(), ctx->ra_mask.size());
+    return RTGL_OK;
+}
+
+template <int K>
+static void launch_tile_buckets_resolve(rtgl_context *ctx, const TileBucketsResolveArgs &a, const dim3 &grid, bool to_image)
+{
+    if (to_image) hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+extern "C" int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params)
+{
+    ENTER(ctx);
+    if (!params) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_resolve: params is NULL");
+    rt_robust_plan::ResolveParams P;
+    memcpy(&P, params, sizeof P);
+    if (const char *why = rt_robust_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_adaptive_resolve: ") + why);
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_resolve") + kNoRobustAdaptiveSession);
+    const bool to_image = P.dest == rt_robust_plan::kDestImage;
+    if (to_image) {                                       // on the host, what rtgl_robust_resolve with dest IMAGE does
+        ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
+        ctx->ad_active = false;                           // (adaptive sampling: ... and the session ends)
+    }
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    TileBucketsResolveArgs a{};
+    a.buckets = ctx->d_ra_buckets; a.out = to_image ? ctx->d_image : ctx->d_ra_out;
+    a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height); a.n = ctx->d_ra_counts;
+    a.width = ctx->width; a.height = ctx->height; a.fw = sh.fw; a.fh = sh.fh; a.gain = P.gain;
+    const dim3 grid((unsigned)sh.tx, (unsigned)sh.ty);
+    if (ctx->ra_K == 4u) launch_tile_buckets_resolve<4>(ctx, a, grid, to_image);
+    else if (ctx->ra_K == 8u) launch_tile_buckets_resolve<8>(ctx, a, grid, to_image);
+    else launch_tile_buckets_resolve<16>(ctx, a, grid, to_image);
+    HIPCHK(ctx, hipGetLastError());
+    if (!to_image) ctx->ra_resolved = true;
+    return RTGL_OK;
+}
+
+extern "C" int rtgl_robust_adaptive_end(rtgl_context *ctx)
+{
+    ENTER(ctx);
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_end") + kNoRobustAdaptiveSession);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (frames, folds and resolves in flight use the buffers)
+    ctx->ra_active = false; ctx->ra_resolved = false; ctx->ra_K = 0;
+    ctx->ra_mask.clear(); ctx->ra_blocks.clear(); ctx->ra_tiles.clear();
+    return buf_release(ctx, ctx->d_ra_buckets, ctx->d_ra_samples, ctx->d_ra_out, ctx->d_ra_records, ctx->d_ra_counts, ctx->d_ra_lists);
+}
+
+extern "C" int rtgl_read_robust_adaptive_f32(rtgl_context *ctx, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_f32: rgba is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_f32") + kNoRobustAdaptiveSession);
+    if (!ctx->ra_resolved) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_robust_adaptive_f32: no rtgl_robust_adaptive_resolve with dest RTGL_ROBUST_DEST_BUFFER since rtgl_robust_adaptive_begin");
+    return read_rows(ctx, rgba, ctx->d_ra_out, 16);
+}
+
+extern "C" int rtgl_read_robust_adaptive_bucket_f32(rtgl_context *ctx, uint32_t bucket, float *rgba)
+{
+    ENTER(ctx);
+    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_bucket_f32: rgba is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_bucket_f32") + kNoRobustAdaptiveSession);
+    if (bucket >= ctx->ra_K) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_bucket_f32: bucket >= buckets");
+    return read_rows(ctx, rgba, ctx->d_ra_buckets + (size_t)bucket * rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height), 16);
+}
+
+extern "C" int rtgl_read_robust_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty)
+{
+    ENTER(ctx);
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_tiles: tiles is NULL");
+    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_tiles") + kNoRobustAdaptiveSession);
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_ra_records, (size_t)sh.tx * sh.ty * sizeof(rtgl_adaptive_tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tx) *tx = (uint32_t)sh.tx;
+    if (ty) *ty = (uint32_t)sh.ty;
+    return RTGL_OK;
+}
+
+extern "C" void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx)
+{
+    if (!ctx) return nullptr;
+    if (!ctx->ra_active) { ctx->error = std::string("rtgl_device_robust_adaptive_tiles") + kNoRobustAdaptiveSession; return nullptr; }
+    return (void *)ctx->d_ra_records;
 }
 
 // ---- rtgl_robust_denoise: the session's resolve and the guided filter in one call (rt_bucket_guide.hpp, rt_bucket_guide_plan.hpp) -------------

@@ -49,6 +49,8 @@ ROBUST_DEST_BUFFER, ROBUST_DEST_IMAGE = 0, 1
 ROBUST_ERROR_DEFAULTS = dict(threshold=0.05, floor=0.01, gain=1.0, quantile_permille=950)
 # rtgl_robust_denoise
 ROBUST_DENOISE_DEFAULTS = dict(passes=5, sigma_lum=4.0, sigma_normal=0.3, sigma_position=0.05, gain=1.0, demodulate=True)
+# a robust adaptive session (rtgl_robust_adaptive_*)
+ROBUST_ADAPTIVE_DEFAULTS = dict(buckets=8, threshold=0.05, floor=0.01, gain=1.0, min_samples=32, max_samples=1024)
 
 # every symbol include/rtgl_amd.h declares
 ABI_SYMBOLS = [
@@ -77,6 +79,10 @@ ABI_SYMBOLS = [
     "rtgl_robust_error_defaults", "rtgl_robust_error_estimate", "rtgl_read_robust_error_summary", "rtgl_read_robust_error_tiles",
     "rtgl_device_robust_error_tiles",
     "rtgl_robust_denoise_defaults", "rtgl_robust_denoise",
+    "rtgl_robust_adaptive_defaults", "rtgl_robust_adaptive_begin", "rtgl_robust_adaptive_frame", "rtgl_robust_adaptive_accumulate",
+    "rtgl_robust_adaptive_update", "rtgl_robust_adaptive_set_mask", "rtgl_robust_adaptive_get_mask", "rtgl_robust_adaptive_resolve",
+    "rtgl_robust_adaptive_end", "rtgl_read_robust_adaptive_f32", "rtgl_read_robust_adaptive_bucket_f32", "rtgl_read_robust_adaptive_tiles",
+    "rtgl_device_robust_adaptive_tiles",
 ]
 
 
@@ -183,6 +189,12 @@ class CRobustDenoiseParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class CRobustAdaptiveParams(C.Structure):
+    """rtgl_robust_adaptive_params"""
+    _fields_ = [("buckets", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float), ("gain", C.c_float), ("min_samples", C.c_uint32),
+                ("max_samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def build_library(force: bool = False) -> str:
     """hipcc-compile the HIP kernels + C ABI for gfx950 into librtgl_amd.so (in-tree)."""
     srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith((".hip", ".hpp", ".h"))]
@@ -284,6 +296,19 @@ def load_library() -> C.CDLL:
     L.rtgl_device_robust_error_tiles.argtypes = [vp]; L.rtgl_device_robust_error_tiles.restype = vp
     L.rtgl_robust_denoise_defaults.argtypes = [C.POINTER(CRobustDenoiseParams)]
     L.rtgl_robust_denoise.argtypes = [vp, C.POINTER(CRobustDenoiseParams)]
+    L.rtgl_robust_adaptive_defaults.argtypes = [C.POINTER(CRobustAdaptiveParams)]
+    L.rtgl_robust_adaptive_begin.argtypes = [vp, C.POINTER(CRobustAdaptiveParams)]
+    L.rtgl_robust_adaptive_frame.argtypes = [vp]
+    L.rtgl_robust_adaptive_accumulate.argtypes = [vp]
+    L.rtgl_robust_adaptive_update.argtypes = [vp, C.POINTER(CAdaptiveSummary)]
+    L.rtgl_robust_adaptive_set_mask.argtypes = [vp, vp]
+    L.rtgl_robust_adaptive_get_mask.argtypes = [vp, vp]
+    L.rtgl_robust_adaptive_resolve.argtypes = [vp, C.POINTER(CRobustResolveParams)]
+    L.rtgl_robust_adaptive_end.argtypes = [vp]
+    L.rtgl_read_robust_adaptive_f32.argtypes = [vp, vp]
+    L.rtgl_read_robust_adaptive_bucket_f32.argtypes = [vp, u32, vp]
+    L.rtgl_read_robust_adaptive_tiles.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.rtgl_device_robust_adaptive_tiles.argtypes = [vp]; L.rtgl_device_robust_adaptive_tiles.restype = vp
     L.rtgl_set_option.argtypes = [vp, C.c_char_p, i]
     L.rtgl_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i)]
     L.rtgl_last_frame_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -806,6 +831,91 @@ class Context:
         """Device pointer of those records (0 before the session's first successful robust_error_estimate(): see the context's last error)."""
         return int(self.lib.rtgl_device_robust_error_tiles(self.h) or 0)
 
+    # --- a robust adaptive session
+    def robust_adaptive_begin(self, buckets=None, threshold=None, floor=None, gain=None, min_samples=None, max_samples=None):
+        """Open a robust adaptive session (rtgl_robust_adaptive_begin): zeroed bucket planes, every tile active and without a sample; the
+        image is not touched.  None keeps the library's default (ROBUST_ADAPTIVE_DEFAULTS)."""
+        p = CRobustAdaptiveParams()
+        self._chk(self.lib.rtgl_robust_adaptive_defaults(C.byref(p)))
+        for name, value in (("threshold", threshold), ("floor", floor), ("gain", gain)):
+            if value is not None:
+                setattr(p, name, float(value))
+        for name, value in (("buckets", buckets), ("min_samples", min_samples), ("max_samples", max_samples)):
+            if value is not None:
+                setattr(p, name, int(value))
+        self._chk(self.lib.rtgl_robust_adaptive_begin(self.h, C.byref(p)))
+
+    def robust_adaptive_frame(self, p: FrameParams | None = None, sync: bool = True):
+        """One frame of one sample over the active tiles, folded into the bucket of each tile's next sample (rtgl_robust_adaptive_frame),
+        with the parameters `p` if given."""
+        if p is not None:
+            self.set_params(p)
+        self._chk(self.lib.rtgl_robust_adaptive_frame(self.h))
+        if sync:
+            self._chk(self.lib.rtgl_synchronize(self.h))
+
+    def robust_adaptive_accumulate(self):
+        """The fold with the image as it stands as the sample of every active tile (rtgl_robust_adaptive_accumulate)."""
+        self._chk(self.lib.rtgl_robust_adaptive_accumulate(self.h))
+
+    def robust_adaptive_update(self) -> dict:
+        """Estimate the tiles whose count has moved, set the mask from the records (rtgl_robust_adaptive_update; synchronises) and return
+        the summary as adaptive_update() does."""
+        s = CAdaptiveSummary()
+        self._chk(self.lib.rtgl_robust_adaptive_update(self.h, C.byref(s)))
+        out = {k: int(getattr(s, k)) for k in ("tiles_total", "tiles_active", "tiles_converged", "tiles_capped", "blocks_active", "samples_min",
+                                               "samples_max", "converged", "samples_total")}
+        out["max_tile_mse"] = np.frombuffer(bytes(s), np.float32)[10]      # (the bits, not a round trip through a Python float)
+        return out
+
+    def robust_adaptive_set_mask(self, tiles):
+        """An explicit mask (ty, tx), non-zero = active, until the next robust_adaptive_update()."""
+        t = np.ascontiguousarray(np.asarray(tiles) != 0, np.uint8)
+        assert t.shape == self._tiles_shape()
+        self._chk(self.lib.rtgl_robust_adaptive_set_mask(self.h, _ptr(t)))
+
+    def robust_adaptive_get_mask(self) -> np.ndarray:
+        out = np.zeros(self._tiles_shape(), np.uint8)
+        self._chk(self.lib.rtgl_robust_adaptive_get_mask(self.h, _ptr(out)))
+        return out
+
+    def robust_adaptive_resolve(self, gain=None, dest=None):
+        """The trimmed mean of the buckets with every pixel's N taken from its tile (rtgl_robust_adaptive_resolve) into the session's output
+        plane (dest ROBUST_DEST_BUFFER: read_robust_adaptive()) or into the accumulation image (ROBUST_DEST_IMAGE)."""
+        p = CRobustResolveParams()
+        self._chk(self.lib.rtgl_robust_defaults(None, C.byref(p)))
+        if gain is not None:
+            p.gain = float(gain)
+        if dest is not None:
+            p.dest = int(dest)
+        self._chk(self.lib.rtgl_robust_adaptive_resolve(self.h, C.byref(p)))
+
+    def robust_adaptive_end(self):
+        self._chk(self.lib.rtgl_robust_adaptive_end(self.h))
+
+    def read_robust_adaptive(self) -> np.ndarray:
+        """The output plane of the latest robust_adaptive_resolve() with dest ROBUST_DEST_BUFFER: RGB and the Gini coefficient."""
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_robust_adaptive_f32(self.h, _ptr(out)))
+        return out
+
+    def read_robust_adaptive_bucket(self, j: int) -> np.ndarray:
+        out = np.zeros((self.local_rows, self.width, 4), np.float32)
+        self._chk(self.lib.rtgl_read_robust_adaptive_bucket_f32(self.h, int(j), _ptr(out)))
+        return out
+
+    def read_robust_adaptive_tiles(self) -> np.ndarray:
+        """The session's tile records as a structured array (ty, tx) of ADAPTIVE_TILE_DTYPE; tile row 0 = image row 0."""
+        out = np.zeros(self._tiles_shape(), ADAPTIVE_TILE_DTYPE)
+        nx, ny = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.rtgl_read_robust_adaptive_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
+        assert (int(ny.value), int(nx.value)) == out.shape
+        return out
+
+    def device_robust_adaptive_tiles_ptr(self) -> int:
+        """Device pointer of those records (0 without a session: see the context's last error)."""
+        return int(self.lib.rtgl_device_robust_adaptive_tiles(self.h) or 0)
+
     # --- robust denoise
     def robust_denoise(self, passes=None, sigma_lum=None, sigma_normal=None, sigma_position=None, gain=None, demodulate=None):
         """Enqueue the resolve of the open robust session and the variance-guided filter over it in one call (rtgl_robust_denoise; does
@@ -984,6 +1094,24 @@ class HeadlessRenderer(FrameLoop):
                     break
         self.ctx.robust_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
         return done, summary, (self.ctx.read_image() if to_image else self.ctx.read_robust())
+
+    def render_robust_adaptive(self, threshold: float, max_samples: int, min_samples=None, check_every: int = 16, buckets: int = 8,
+                               gain: float = 1.0, to_image: bool = False, floor=None):
+        """Render until the picture robust_adaptive_resolve(gain=gain) makes is at or below `threshold` (a relative RMSE) in every tile, or
+        the tile holds `max_samples` samples: a robust adaptive session (robust_adaptive_begin) of masked frames with the uniforms of
+        session_frame(), a robust_adaptive_update() after every `check_every` of them, until no tile is active; then the resolve.  Returns
+        (frames rendered, the latest summary, the resolved picture as render_robust() returns it).  The session stays open."""
+        if check_every < 1:
+            raise ValueError("render_robust_adaptive: check_every must be >= 1")
+        self.ctx.robust_adaptive_begin(buckets=buckets, threshold=threshold, floor=floor, gain=gain, min_samples=min_samples, max_samples=max_samples)
+        done, summary = 0, self.ctx.robust_adaptive_update()
+        while not summary["converged"]:
+            for _ in range(check_every):
+                self.ctx.robust_adaptive_frame(self.session_frame(), sync=False)
+                done += 1
+            summary = self.ctx.robust_adaptive_update()
+        self.ctx.robust_adaptive_resolve(gain=gain, dest=ROBUST_DEST_IMAGE if to_image else ROBUST_DEST_BUFFER)
+        return done, summary, (self.ctx.read_image() if to_image else self.ctx.read_robust_adaptive())
 
     def read_temporal(self) -> np.ndarray:
         return self.ctx.read_temporal()
