@@ -515,16 +515,7 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
-    bool adaptive_frame()
-    {
-        if (!m_ctx) return false;
-        const rtgl_frame_params p = frame_params(0, 0);        // (rtgl_adaptive_frame ignores frames and reset_flag)
-        int rc = rtgl_set_frame_params(m_ctx, &p);
-        if (rc == RTGL_OK) rc = rtgl_adaptive_frame(m_ctx);
-        if (rc == RTGL_OK) record(p);
-        check(rc);
-        return rc == RTGL_OK;
-    }
+    bool adaptive_frame() { return masked_frame(rtgl_adaptive_frame); }
     bool adaptive_update(rtgl_adaptive_summary *summary = nullptr)
     {
         rtgl_adaptive_summary s{};
@@ -535,28 +526,10 @@ public:
         return rc == RTGL_OK;
     }
     // the mask, ceil(width / 16) x ceil(height / 16) bytes, row by row, non-zero = active; set: until the next adaptive_update()
-    bool adaptive_set_mask(const std::vector<uint8_t> &tiles)
-    {
-        if (!m_ctx || tiles.size() != (size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16)) return false;
-        const int rc = rtgl_adaptive_set_mask(m_ctx, tiles.data());
-        check(rc);
-        return rc == RTGL_OK;
-    }
-    std::vector<uint8_t> adaptive_get_mask() const
-    {
-        if (!m_ctx) return {};
-        std::vector<uint8_t> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
-        if (rtgl_adaptive_get_mask(m_ctx, tiles.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
-        return tiles;
-    }
+    bool adaptive_set_mask(const std::vector<uint8_t> &tiles) { return set_tile_mask(rtgl_adaptive_set_mask, tiles); }
+    std::vector<uint8_t> adaptive_get_mask() const { return get_tile_mask(rtgl_adaptive_get_mask); }
     // the tile records, row by row; empty (and a message) before the first adaptive_begin()
-    std::vector<rtgl_adaptive_tile> read_adaptive_tiles() const
-    {
-        if (!m_ctx) return {};
-        std::vector<rtgl_adaptive_tile> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
-        if (rtgl_read_adaptive_tiles(m_ctx, tiles.data(), nullptr, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
-        return tiles;
-    }
+    std::vector<rtgl_adaptive_tile> read_adaptive_tiles() const { return read_tile_records(rtgl_read_adaptive_tiles); }
     // "render until every tile is this clean": a session of masked frames with an adaptive_update() after every check_every of them, until
     // no tile is active (each is at or below `threshold`, a relative RMSE, or holds max_samples samples) or m_quit is set.  Returns the
     // frames rendered; `summary` (if not null) receives the latest summary.
@@ -747,16 +720,7 @@ public:
         check(rc);
         return rc == RTGL_OK;
     }
-    bool robust_adaptive_frame()
-    {
-        if (!m_ctx) return false;
-        const rtgl_frame_params p = frame_params(0, 0);        // (rtgl_robust_adaptive_frame ignores frames and reset_flag)
-        int rc = rtgl_set_frame_params(m_ctx, &p);
-        if (rc == RTGL_OK) rc = rtgl_robust_adaptive_frame(m_ctx);
-        if (rc == RTGL_OK) record(p);
-        check(rc);
-        return rc == RTGL_OK;
-    }
+    bool robust_adaptive_frame() { return masked_frame(rtgl_robust_adaptive_frame); }
     bool robust_adaptive_accumulate()
     {
         if (!m_ctx) return false;
@@ -774,20 +738,8 @@ public:
         return rc == RTGL_OK;
     }
     // the mask, ceil(width / 16) x ceil(height / 16) bytes, row by row, non-zero = active; set: until the next robust_adaptive_update()
-    bool robust_adaptive_set_mask(const std::vector<uint8_t> &tiles)
-    {
-        if (!m_ctx || tiles.size() != (size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16)) return false;
-        const int rc = rtgl_robust_adaptive_set_mask(m_ctx, tiles.data());
-        check(rc);
-        return rc == RTGL_OK;
-    }
-    std::vector<uint8_t> robust_adaptive_get_mask() const
-    {
-        if (!m_ctx) return {};
-        std::vector<uint8_t> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
-        if (rtgl_robust_adaptive_get_mask(m_ctx, tiles.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
-        return tiles;
-    }
+    bool robust_adaptive_set_mask(const std::vector<uint8_t> &tiles) { return set_tile_mask(rtgl_robust_adaptive_set_mask, tiles); }
+    std::vector<uint8_t> robust_adaptive_get_mask() const { return get_tile_mask(rtgl_robust_adaptive_get_mask); }
     bool robust_adaptive_resolve(const rtgl_robust_resolve_params *params = nullptr)
     {
         if (!m_ctx) return false;
@@ -823,13 +775,7 @@ public:
         return img;
     }
     // the session's tile records, row by row; empty (and a message) without a session
-    std::vector<rtgl_adaptive_tile> read_robust_adaptive_tiles() const
-    {
-        if (!m_ctx) return {};
-        std::vector<rtgl_adaptive_tile> tiles((size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16));
-        if (rtgl_read_robust_adaptive_tiles(m_ctx, tiles.data(), nullptr, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
-        return tiles;
-    }
+    std::vector<rtgl_adaptive_tile> read_robust_adaptive_tiles() const { return read_tile_records(rtgl_read_robust_adaptive_tiles); }
     // "render until every tile of the picture without its fireflies is this clean": a robust adaptive session of masked frames with a
     // robust_adaptive_update() after every check_every of them, until no tile is active (each is at or below `threshold`, a relative RMSE of
     // the picture resolved with `gain`, or holds max_samples samples) or m_quit is set; then robust_adaptive_resolve() with the same gain.
@@ -947,6 +893,39 @@ private:
         ++m_recorded;
     }
     void check(int rc) const { if (rc != RTGL_OK) std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; }
+    // ---- what the adaptive_*() and robust_adaptive_*() twins share; `fn` is the library call of the caller's kind
+    size_t tile_count() const { return (size_t)((m_width + 15) / 16) * (size_t)((m_height + 15) / 16); }
+    bool masked_frame(int (*fn)(rtgl_context *))
+    {
+        if (!m_ctx) return false;
+        const rtgl_frame_params p = frame_params(0, 0);        // (a masked frame ignores frames and reset_flag)
+        int rc = rtgl_set_frame_params(m_ctx, &p);
+        if (rc == RTGL_OK) rc = fn(m_ctx);
+        if (rc == RTGL_OK) record(p);
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    bool set_tile_mask(int (*fn)(rtgl_context *, const uint8_t *), const std::vector<uint8_t> &tiles)
+    {
+        if (!m_ctx || tiles.size() != tile_count()) return false;
+        const int rc = fn(m_ctx, tiles.data());
+        check(rc);
+        return rc == RTGL_OK;
+    }
+    std::vector<uint8_t> get_tile_mask(int (*fn)(rtgl_context *, uint8_t *)) const
+    {
+        if (!m_ctx) return {};
+        std::vector<uint8_t> tiles(tile_count());
+        if (fn(m_ctx, tiles.data()) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
+    std::vector<rtgl_adaptive_tile> read_tile_records(int (*fn)(rtgl_context *, rtgl_adaptive_tile *, uint32_t *, uint32_t *)) const
+    {
+        if (!m_ctx) return {};
+        std::vector<rtgl_adaptive_tile> tiles(tile_count());
+        if (fn(m_ctx, tiles.data(), nullptr, nullptr) != RTGL_OK) { std::cerr << "rtgl: " << rtgl_last_error(m_ctx) << std::endl; return {}; }
+        return tiles;
+    }
 
     rtgl_context *m_ctx = nullptr;
     rtgl_frame_params m_last_params{};

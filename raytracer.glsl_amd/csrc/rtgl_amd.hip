@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <condition_variable>
 #include <memory>
 
@@ -201,6 +202,15 @@ struct PartWorker {
 static int device_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
 static int device_free(void *p) { return (int)hipFree(p); }
 
+// What a session of masked tiles owns, whichever kind it is (rt_adaptive_plan.hpp): the sample buffer a masked frame traces into, the tile
+// records, the counts (n per tile, then m per tile) and the two lists a frame reads (the active blocks, then the active tiles).
+// active: a session is open; the mask and the lists as they are on the device
+struct TileSession {
+    float4 *d_samples = nullptr; uint4 *d_records = nullptr; uint32_t *d_counts = nullptr, *d_lists = nullptr;
+    bool active = false;
+    std::vector<uint8_t> mask; std::vector<uint32_t> blocks, tiles;
+};
+
 struct rtgl_context {
     int device = 0;
     int width = 0, height = 0;
@@ -320,12 +330,10 @@ struct rtgl_context {
     // err_fm, err_first: the snapshot's `frames` and first_frames; err_rendered, err_fn: a frame has been rendered, and its `frames`
     float *d_err_snapshot = nullptr; uint4 *d_err_tiles = nullptr; uint32_t *d_err_summary = nullptr;
     uint64_t err_epoch = 1, err_snap_epoch = 0; int32_t err_fm = 0, err_first = 0, err_fn = 0; bool err_rendered = false, has_error = false;
-    // adaptive sampling (rt_adaptive.hpp, rt_adaptive_plan.hpp), all allocated by the first rtgl_adaptive_begin: the sample buffer a masked
-    // frame traces into, the snapshot plane, the tile records, the counts (n per tile, then m per tile) and the two lists a frame reads (the
-    // active blocks, then the active tiles).  ad_active: a session is open; the mask and the lists as they are on the device
-    float4 *d_ad_samples = nullptr; float *d_ad_snapshot = nullptr; uint4 *d_ad_records = nullptr; uint32_t *d_ad_counts = nullptr, *d_ad_lists = nullptr;
-    bool ad_active = false, has_adaptive = false; rtgl_adaptive_params ad_params{};
-    std::vector<uint8_t> ad_mask; std::vector<uint32_t> ad_blocks, ad_tiles;
+    // adaptive sampling (rt_adaptive.hpp, rt_adaptive_plan.hpp), all allocated by the first rtgl_adaptive_begin: the session's masked tiles
+    // and the snapshot plane.  has_adaptive: a begin has succeeded, so the tile records can be read
+    TileSession ad; float *d_ad_snapshot = nullptr;
+    bool has_adaptive = false; rtgl_adaptive_params ad_params{};
     // robust accumulation (rt_robust.hpp, rt_robust_plan.hpp), allocated by rtgl_robust_begin and freed by rtgl_robust_end: the rb_K bucket
     // planes (bucket-major) and the output plane.  rb_active: a session is open; rb_N: the frames folded; rb_resolved: the output plane holds a resolve
     float4 *d_rb_buckets = nullptr, *d_rb_out = nullptr;
@@ -334,12 +342,10 @@ struct rtgl_context {
     // first estimate and freed by rtgl_robust_end.  has_rb_error: an estimate of THIS session has succeeded
     uint4 *d_rbe_tiles = nullptr; uint32_t *d_rbe_summary = nullptr; bool has_rb_error = false;
     // a robust adaptive session (rt_robust_tiles.hpp, rt_robust_tiles_plan.hpp), allocated by rtgl_robust_adaptive_begin and freed by
-    // rtgl_robust_adaptive_end: the ra_K bucket planes (bucket-major), the sample buffer a masked frame traces into, the output plane, the
-    // tile records, the counts (n per tile, then m per tile) and the two lists (the active blocks, then the active tiles).  ra_active: a
-    // session is open; ra_resolved: the output plane holds a resolve; the mask and the lists as they are on the device
-    float4 *d_ra_buckets = nullptr, *d_ra_samples = nullptr, *d_ra_out = nullptr; uint4 *d_ra_records = nullptr; uint32_t *d_ra_counts = nullptr, *d_ra_lists = nullptr;
-    uint32_t ra_K = 0; bool ra_active = false, ra_resolved = false; rt_robust_tiles_plan::Params ra_params{};
-    std::vector<uint8_t> ra_mask; std::vector<uint32_t> ra_blocks, ra_tiles;
+    // rtgl_robust_adaptive_end: the session's masked tiles, the ra_K bucket planes (bucket-major) and the output plane.
+    // ra_resolved: the output plane holds a resolve
+    TileSession ra; float4 *d_ra_buckets = nullptr, *d_ra_out = nullptr;
+    uint32_t ra_K = 0; bool ra_resolved = false; rt_robust_tiles_plan::Params ra_params{};
     FrameParams params{};
     bool have_params = false;
     int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
@@ -1411,7 +1417,7 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
     FANOUT(ctx, rtgl_render_frame(part));
     if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
     if (ctx->params.samples == 0) return fail(ctx, RTGL_ERR_INVALID, "u_samples == 0 divides by zero in the reference; refused");
-    ctx->ad_active = false;                              // (adaptive sampling: an ordinary frame ends the session; one refused above does not)
+    ctx->ad.active = false;                              // (adaptive sampling: an ordinary frame ends the session; one refused above does not)
     // frame batching: hold the frame back until the batch is full.  Only what the batched pipeline covers: one sample per frame, the
     // per-bounce pipeline (a scene with triangles), no per-frame read-outs (counters, RNG states)
     const bool batchable = ctx->opt_frame_batch > 1 && ctx->params.samples == 1 && ctx->params.max_bounce > 0 && !ctx->opt_counters && !ctx->opt_rng_state
@@ -1613,7 +1619,7 @@ extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
     ++ctx->err_epoch;                                   // (rtgl_error_estimate: another image, the snapshot is dropped)
-    ctx->ad_active = false;                             // (adaptive sampling: ... and the session ends)
+    ctx->ad.active = false;                             // (adaptive sampling: ... and the session ends)
     if (!ctx->parts.empty()) {                          // scatter the rows to their owners
         ctx->gathered = false;
         std::vector<float> local;
@@ -1638,7 +1644,7 @@ extern "C" int rtgl_clear_image(rtgl_context *ctx)
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;                              // the first-hit planes' mean restarts with the next frame (their contents stay)
     ++ctx->err_epoch;                                     // (rtgl_error_estimate: the snapshot is dropped)
-    ctx->ad_active = false;                               // (adaptive sampling: the session ends)
+    ctx->ad.active = false;                               // (adaptive sampling: the session ends)
     return RTGL_OK;
 }
 
@@ -1682,7 +1688,7 @@ extern "C" int rtgl_bind_device_image(rtgl_context *ctx, void *dptr)
     if (!ctx->parts.empty()) return fail(ctx, RTGL_ERR_STATE, "a multi-device context renders into its own per-device tile buffers");
     ctx->d_image = dptr ? (float4 *)dptr : ctx->d_image_own;
     ++ctx->err_epoch;                                     // (rtgl_error_estimate: another image, the snapshot is dropped)
-    ctx->ad_active = false;                               // (adaptive sampling: ... and the session ends)
+    ctx->ad.active = false;                               // (adaptive sampling: ... and the session ends)
     return RTGL_OK;
 }
 
@@ -1852,9 +1858,8 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
         return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
                                          "render on a single-device context, or filter the gathered image yourself");
     const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_c = P.sigma_color > 0.0f, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const int need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: a first-hit plane these parameters need is not enabled (option \"aov\": albedo to demodulate, normal for sigma_normal > 0, position for sigma_position > 0)");
-    if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: no frame has been rendered since the first-hit planes last restarted");
+    const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
+    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: this context holds no pixels");
     const float4 *input = denoise_input(ctx);
@@ -1927,6 +1932,24 @@ static void launch_guided(rtgl_context *ctx, const GuidedArgs &a)
     else hipLaunchKernelGGL((guided_kernel<kLast, kRemod, false>), grid, dim3(256), lds, ctx->stream, a);
 }
 
+// the guided passes behind a prepare kernel that wrote scratch 0: pass k of `passes` reads scratch k & 1 and writes scratch (k + 1) & 1 or,
+// as the last, the denoised buffer; with every launch taken, the denoised and the variance buffers are there to read
+static int launch_guided_passes(rtgl_context *ctx, GuidedArgs a, uint32_t passes, bool demod)
+{
+    for (uint32_t k = 0; k < passes; ++k) {
+        const bool last = k + 1u == passes;
+        a.src = ctx->d_dn_scratch[k & 1u];
+        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[(k + 1u) & 1u];
+        a.step = 1 << k; a.step_log2 = (int)k;
+        if (last && demod) launch_guided<true, true>(ctx, a);
+        else if (last) launch_guided<true, false>(ctx, a);
+        else launch_guided<false, false>(ctx, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ctx->has_denoised = true; ctx->has_dn_variance = true;
+    return RTGL_OK;
+}
+
 extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_params *params)
 {
     ENTER(ctx);
@@ -1943,9 +1966,8 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
         return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
                                          "render on a single-device context, or filter the gathered image yourself");
     const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const int need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: a first-hit plane these parameters need is not enabled (option \"aov\": albedo to demodulate, normal for sigma_normal > 0, position for sigma_position > 0)");
-    if (need && (ctx->aov_restart || ctx->aov_n == 0u)) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: no frame has been rendered since the first-hit planes last restarted");
+    const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
+    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
     const float4 *input = denoise_input(ctx);
@@ -1980,18 +2002,7 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
         t.g = a; t.moments = ctx->d_tm_moments[ctx->tm_cur];
         hipLaunchKernelGGL(guided_prepare_tvar_kernel, prep_grid, dim3(256), kPrepLdsBytes, ctx->stream, t);
     } else hipLaunchKernelGGL(guided_prepare_kernel, prep_grid, dim3(256), kPrepLdsBytes, ctx->stream, a);
-    for (uint32_t k = 0; k < P.passes; ++k) {
-        const bool last = k + 1u == P.passes;
-        a.src = ctx->d_dn_scratch[k & 1u];
-        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[(k + 1u) & 1u];
-        a.step = 1 << k; a.step_log2 = (int)k;
-        if (last && demod) launch_guided<true, true>(ctx, a);
-        else if (last) launch_guided<true, false>(ctx, a);
-        else launch_guided<false, false>(ctx, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    ctx->has_denoised = true; ctx->has_dn_variance = true;
-    return RTGL_OK;
+    return launch_guided_passes(ctx, a, P.passes, demod);
 }
 
 extern "C" int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba)
@@ -2440,18 +2451,106 @@ extern "C" int rtgl_adaptive_defaults(rtgl_adaptive_params *out)
 static_assert(sizeof(rtgl_adaptive_params) == 32 && sizeof(rtgl_adaptive_tile) == sizeof(rt_adaptive_plan::Tile) && sizeof(rtgl_adaptive_summary) == sizeof(rt_adaptive_plan::Summary)
               && offsetof(rtgl_adaptive_summary, samples_total) == offsetof(rt_adaptive_plan::Summary, samples_total) && rt_adaptive_plan::kTile == kErrTile, "the layouts of the header");
 
-// a mask as it stands -> its two lists on the device (the active blocks, then the active tiles); synchronises: the host vectors are free again
-static int upload_tile_lists(rtgl_context *ctx, const std::vector<uint8_t> &mask, std::vector<uint32_t> &blocks, std::vector<uint32_t> &tiles, uint32_t *d_lists)
+// ---- a session of masked tiles on the host (TileSession): what rtgl_adaptive_* and rtgl_robust_adaptive_* both do, told neither kind.  `who`
+// is the entry point's name and `no_session` its kind's wording, for the messages ------------------------------------------------------
+static const char *const kNoAdaptiveSession = ": no session (rtgl_adaptive_begin has not been called, or the session has ended)";
+static const char *const kNoRobustAdaptiveSession = ": no session (rtgl_robust_adaptive_begin has not been called, or rtgl_robust_adaptive_end has)";
+
+// the mask as it stands -> its two lists on the device (the active blocks, then the active tiles); synchronises: the host vectors are free again
+static int upload_tile_lists(rtgl_context *ctx, TileSession &s)
 {
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    rt_adaptive_plan::build_lists(sh, mask, blocks, tiles);
+    rt_adaptive_plan::build_lists(sh, s.mask, s.blocks, s.tiles);
     const size_t n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
-    if (!blocks.empty()) HIPCHK(ctx, hipMemcpyAsync(d_lists, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (!tiles.empty()) HIPCHK(ctx, hipMemcpyAsync(d_lists + n_blocks, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!s.blocks.empty()) HIPCHK(ctx, hipMemcpyAsync(s.d_lists, s.blocks.data(), s.blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!s.tiles.empty()) HIPCHK(ctx, hipMemcpyAsync(s.d_lists + n_blocks, s.tiles.data(), s.tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RTGL_OK;
 }
-static int adaptive_upload_lists(rtgl_context *ctx) { return upload_tile_lists(ctx, ctx->ad_mask, ctx->ad_blocks, ctx->ad_tiles, ctx->d_ad_lists); }
+
+// a context that cannot hold a session is refused; otherwise the four buffers at its size (rt_robust_tiles_plan.hpp: a plane of samples, a
+// record and two counts per tile, a word per block and per tile), where one that is live stays
+static int tile_session_reserve(rtgl_context *ctx, TileSession &s, const char *who)
+{
+    if (!ctx->parts.empty() || ctx->world > 1)
+        return fail(ctx, RTGL_ERR_STATE, std::string(who) + ": a tiled or multi-device context holds strips, and the tiles are the whole picture's (out of scope): render on a single-device context");
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t n_tiles = (size_t)sh.tx * sh.ty, n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
+    if ((uint64_t)n_blocks * 64ull > 0xFFFFFFF0ull) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": the footprint does not fit 32-bit ray slots");
+    RCCHK(buf_ensure(ctx, s.d_samples, rt_robust_tiles_plan::plane_bytes(rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height))));
+    RCCHK(buf_ensure(ctx, s.d_records, rt_robust_tiles_plan::record_bytes(n_tiles)));
+    RCCHK(buf_ensure(ctx, s.d_counts, rt_robust_tiles_plan::count_bytes(n_tiles)));
+    RCCHK(buf_ensure(ctx, s.d_lists, rt_robust_tiles_plan::list_bytes(n_blocks, n_tiles)));
+    return RTGL_OK;
+}
+
+// the reserved session opens: no record, no sample counted, every tile active and the lists on the device
+static int tile_session_open(rtgl_context *ctx, TileSession &s)
+{
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t n_tiles = (size_t)sh.tx * sh.ty;
+    HIPCHK(ctx, hipMemsetAsync(s.d_records, 0, rt_robust_tiles_plan::record_bytes(n_tiles), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(s.d_counts, 0, rt_robust_tiles_plan::count_bytes(n_tiles), ctx->stream));
+    rt_adaptive_plan::explicit_mask(sh, std::vector<uint8_t>(n_tiles, 1).data(), s.mask);
+    RCCHK(upload_tile_lists(ctx, s));
+    s.active = true;
+    return RTGL_OK;
+}
+
+// the tail of an update, behind the kind's estimate kernel: the records it wrote to the host, the mask rule per tile, the lists of the new
+// mask to the device, the summary
+static int tile_session_update(rtgl_context *ctx, TileSession &s, uint32_t min_samples, uint32_t max_samples, rtgl_adaptive_summary *summary_out)
+{
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    const size_t n_tiles = (size_t)sh.tx * sh.ty;
+    std::vector<rt_adaptive_plan::Tile> records(n_tiles);
+    HIPCHK(ctx, hipMemcpyAsync(records.data(), s.d_records, n_tiles * sizeof(rt_adaptive_plan::Tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t t = 0; t < (uint32_t)n_tiles; ++t) s.mask[t] = rt_adaptive_plan::active(sh, t, records[t], min_samples, max_samples) ? 1 : 0;
+    RCCHK(upload_tile_lists(ctx, s));
+    const rt_adaptive_plan::Summary sum = rt_adaptive_plan::summary(sh, records.data(), s.mask, (uint32_t)s.blocks.size(), max_samples);
+    memcpy(summary_out, &sum, sizeof sum);
+    return RTGL_OK;
+}
+
+static int tile_session_set_mask(rtgl_context *ctx, TileSession &s, const char *who, const char *no_session, const uint8_t *tiles)
+{
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": tiles is NULL");
+    if (!s.active) return fail(ctx, RTGL_ERR_STATE, std::string(who) + no_session);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (frames in flight read the lists about to be replaced)
+    rt_adaptive_plan::explicit_mask(rt_adaptive_plan::shape(ctx->width, ctx->height), tiles, s.mask);
+    return upload_tile_lists(ctx, s);
+}
+
+static int tile_session_get_mask(rtgl_context *ctx, const TileSession &s, const char *who, const char *no_session, uint8_t *tiles)
+{
+    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": tiles is NULL");
+    if (!s.active) return fail(ctx, RTGL_ERR_STATE, std::string(who) + no_session);
+    memcpy(tiles, s.mask.data(), s.mask.size());
+    return RTGL_OK;
+}
+
+// the tile records and the tile grid; the caller has checked `tiles` and that the records are there
+static int tile_session_read_tiles(rtgl_context *ctx, const TileSession &s, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty)
+{
+    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
+    HIPCHK(ctx, hipMemcpyAsync(tiles, s.d_records, (size_t)sh.tx * sh.ty * sizeof(rtgl_adaptive_tile), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tx) *tx = (uint32_t)sh.tx;
+    if (ty) *ty = (uint32_t)sh.ty;
+    return RTGL_OK;
+}
+
+// what a masked frame asks of the session and of the context; `no_params`: the kind's wording of the second refusal
+static int masked_frame_refused(rtgl_context *ctx, const TileSession &s, const char *who, const char *no_session, const char *no_params)
+{
+    if (!s.active) return fail(ctx, RTGL_ERR_STATE, std::string(who) + no_session);
+    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, no_params);
+    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, std::string(who) + ": a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
+    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": a masked frame is one sample per pixel: samples must be 1");
+    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": max_bounce must be > 0");
+    return RTGL_OK;
+}
 
 extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params *params)
 {
@@ -2463,28 +2562,15 @@ extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params
     if (P.min_samples < 1u || P.max_samples < P.min_samples) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: 1 <= min_samples <= max_samples is required");
     if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: no flag is defined");
     for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: reserved fields must be 0");
-    if (!ctx->parts.empty() || ctx->world > 1)
-        return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_begin: a tiled or multi-device context holds strips, and the tiles are the whole picture's (out of scope): render on a single-device context");
-    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    const size_t px = (size_t)ctx->height * ctx->width, n_tiles = (size_t)sh.tx * sh.ty, n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
-    if ((uint64_t)n_blocks * 64ull > 0xFFFFFFF0ull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_begin: the footprint does not fit 32-bit ray slots");
-    ctx->ad_active = false;
-    RCCHK(buf_ensure(ctx, ctx->d_ad_samples, px * sizeof(float4)));
-    RCCHK(buf_ensure(ctx, ctx->d_ad_snapshot, px * sizeof(float)));
-    RCCHK(buf_ensure(ctx, ctx->d_ad_records, n_tiles * sizeof(rtgl_adaptive_tile)));
-    RCCHK(buf_ensure(ctx, ctx->d_ad_counts, 2 * n_tiles * sizeof(uint32_t)));
-    RCCHK(buf_ensure(ctx, ctx->d_ad_lists, (n_blocks + n_tiles) * sizeof(uint32_t)));
+    RCCHK(tile_session_reserve(ctx, ctx->ad, "rtgl_adaptive_begin"));
+    ctx->ad.active = false;
+    RCCHK(buf_ensure(ctx, ctx->d_ad_snapshot, (size_t)ctx->height * ctx->width * sizeof(float)));
     // the image as rtgl_clear_image leaves it
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;
     ++ctx->err_epoch;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ad_records, 0, n_tiles * sizeof(rtgl_adaptive_tile), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ad_counts, 0, 2 * n_tiles * sizeof(uint32_t), ctx->stream));
     ctx->ad_params = P; ctx->has_adaptive = true;
-    rt_adaptive_plan::explicit_mask(sh, std::vector<uint8_t>(n_tiles, 1).data(), ctx->ad_mask);
-    RCCHK(adaptive_upload_lists(ctx));
-    ctx->ad_active = true;
-    return RTGL_OK;
+    return tile_session_open(ctx, ctx->ad);
 }
 
 // One masked frame (rt_adaptive.hpp): the blocks of `list` (n0 = 64 x its length > 0) traced as a one-frame image into `samples`, from the
@@ -2529,20 +2615,16 @@ static int masked_frame(rtgl_context *ctx, float4 *samples, const uint32_t *list
 extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
 {
     ENTER(ctx);
-    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
-    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_set_frame_params has not been called");
-    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
-    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
-    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_frame: max_bounce must be > 0");
+    RCCHK(masked_frame_refused(ctx, ctx->ad, "rtgl_adaptive_frame", kNoAdaptiveSession, "rtgl_set_frame_params has not been called"));
     ++ctx->err_epoch;                                     // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
-    if (ctx->ad_blocks.empty()) return RTGL_OK;
-    RCCHK(masked_frame(ctx, ctx->d_ad_samples, ctx->d_ad_lists, (uint32_t)ctx->ad_blocks.size() * 64u));
+    if (ctx->ad.blocks.empty()) return RTGL_OK;
+    RCCHK(masked_frame(ctx, ctx->ad.d_samples, ctx->ad.d_lists, (uint32_t)ctx->ad.blocks.size() * 64u));
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
     AdaptiveMergeArgs a{};
-    a.image = ctx->d_image; a.samples = ctx->d_ad_samples; a.n = ctx->d_ad_counts;
-    a.tiles = ctx->d_ad_lists + (size_t)sh.blocks_x * sh.blocks_y;
+    a.image = ctx->d_image; a.samples = ctx->ad.d_samples; a.n = ctx->ad.d_counts;
+    a.tiles = ctx->ad.d_lists + (size_t)sh.blocks_x * sh.blocks_y;
     a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh; a.tx = sh.tx;
-    hipLaunchKernelGGL(adaptive_merge_kernel, dim3((unsigned)ctx->ad_tiles.size()), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(adaptive_merge_kernel, dim3((unsigned)ctx->ad.tiles.size()), dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->timed = true;
@@ -2553,43 +2635,28 @@ extern "C" int rtgl_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summary *su
 {
     ENTER(ctx);
     if (!summary_out) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_update: summary_out is NULL");
-    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_update: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
+    if (!ctx->ad.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_adaptive_update") + kNoAdaptiveSession);
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    const size_t n_tiles = (size_t)sh.tx * sh.ty;
     AdaptiveTilesArgs a{};
-    a.image = ctx->d_image; a.snapshot = ctx->d_ad_snapshot; a.records = ctx->d_ad_records;
-    a.n = ctx->d_ad_counts; a.m = ctx->d_ad_counts + n_tiles;
+    a.image = ctx->d_image; a.snapshot = ctx->d_ad_snapshot; a.records = ctx->ad.d_records;
+    a.n = ctx->ad.d_counts; a.m = ctx->ad.d_counts + (size_t)sh.tx * sh.ty;
     a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh;
     a.floor_ = ctx->ad_params.floor; a.threshold = ctx->ad_params.threshold;
     hipLaunchKernelGGL(adaptive_tiles_kernel, dim3((unsigned)sh.tx, (unsigned)sh.ty), dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
-    std::vector<rt_adaptive_plan::Tile> records(n_tiles);
-    HIPCHK(ctx, hipMemcpyAsync(records.data(), ctx->d_ad_records, n_tiles * sizeof(rt_adaptive_plan::Tile), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t t = 0; t < (uint32_t)n_tiles; ++t) ctx->ad_mask[t] = rt_adaptive_plan::active(sh, t, records[t], ctx->ad_params.min_samples, ctx->ad_params.max_samples) ? 1 : 0;
-    RCCHK(adaptive_upload_lists(ctx));
-    const rt_adaptive_plan::Summary s = rt_adaptive_plan::summary(sh, records.data(), ctx->ad_mask, (uint32_t)ctx->ad_blocks.size(), ctx->ad_params.max_samples);
-    memcpy(summary_out, &s, sizeof s);
-    return RTGL_OK;
+    return tile_session_update(ctx, ctx->ad, ctx->ad_params.min_samples, ctx->ad_params.max_samples, summary_out);
 }
 
 extern "C" int rtgl_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles)
 {
     ENTER(ctx);
-    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_set_mask: tiles is NULL");
-    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_set_mask: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (frames in flight read the lists about to be replaced)
-    rt_adaptive_plan::explicit_mask(rt_adaptive_plan::shape(ctx->width, ctx->height), tiles, ctx->ad_mask);
-    return adaptive_upload_lists(ctx);
+    return tile_session_set_mask(ctx, ctx->ad, "rtgl_adaptive_set_mask", kNoAdaptiveSession, tiles);
 }
 
 extern "C" int rtgl_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles)
 {
     ENTER(ctx);
-    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_adaptive_get_mask: tiles is NULL");
-    if (!ctx->ad_active) return fail(ctx, RTGL_ERR_STATE, "rtgl_adaptive_get_mask: no session (rtgl_adaptive_begin has not been called, or the session has ended)");
-    memcpy(tiles, ctx->ad_mask.data(), ctx->ad_mask.size());
-    return RTGL_OK;
+    return tile_session_get_mask(ctx, ctx->ad, "rtgl_adaptive_get_mask", kNoAdaptiveSession, tiles);
 }
 
 extern "C" int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty)
@@ -2597,19 +2664,14 @@ extern "C" int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *t
     ENTER(ctx);
     if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "tiles is NULL");
     if (!ctx->has_adaptive) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context");
-    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_ad_records, (size_t)sh.tx * sh.ty * sizeof(rtgl_adaptive_tile), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (tx) *tx = (uint32_t)sh.tx;
-    if (ty) *ty = (uint32_t)sh.ty;
-    return RTGL_OK;
+    return tile_session_read_tiles(ctx, ctx->ad, tiles, tx, ty);
 }
 
 extern "C" void *rtgl_device_adaptive_tiles(rtgl_context *ctx)
 {
     if (!ctx) return nullptr;
     if (!ctx->has_adaptive) { ctx->error = "rtgl_device_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_ad_records;
+    return (void *)ctx->ad.d_records;
 }
 
 // ---- robust accumulation: K bucket means and a Gini-trimmed resolve (rt_robust.hpp, rt_robust_plan.hpp) -----------------------------------
@@ -2663,12 +2725,14 @@ extern "C" int rtgl_robust_accumulate(rtgl_context *ctx)
     return RTGL_OK;
 }
 
-template <int K>
-static void launch_robust_resolve(rtgl_context *ctx, const RobustResolveArgs &a, bool to_image)
+// f(K) with a session's bucket count as a compile-time constant, for the <4>, <8> and <16> instantiations of a kernel.  The count is one
+// that *_plan::invalid let through at begin; with any other, nothing is launched
+template <typename F>
+static void with_buckets(uint32_t K, F &&f)
 {
-    const dim3 grid((unsigned)((a.n + 255u) / 256u));
-    if (to_image) hipLaunchKernelGGL((robust_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((robust_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+    if (K == 4u) f(std::integral_constant<int, 4>{});
+    else if (K == 8u) f(std::integral_constant<int, 8>{});
+    else if (K == 16u) f(std::integral_constant<int, 16>{});
 }
 
 extern "C" int rtgl_robust_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params)
@@ -2683,16 +2747,18 @@ extern "C" int rtgl_robust_resolve(rtgl_context *ctx, const rtgl_robust_resolve_
     const bool to_image = P.dest == rt_robust_plan::kDestImage;
     if (to_image) {                                       // on the host, what rtgl_write_image_f32 does
         ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
-        ctx->ad_active = false;                           // (adaptive sampling: ... and the session ends)
+        ctx->ad.active = false;                           // (adaptive sampling: ... and the session ends)
     }
     RobustResolveArgs a{};
     a.buckets = ctx->d_rb_buckets; a.out = to_image ? ctx->d_image : ctx->d_rb_out;
     a.plane = rt_robust_plan::plane_pixels(ctx->local_rows, ctx->width); a.n = (uint32_t)((size_t)ctx->local_rows * ctx->width);
     a.frames = ctx->rb_N; a.gain = P.gain;
     if (a.n) {
-        if (ctx->rb_K == 4u) launch_robust_resolve<4>(ctx, a, to_image);
-        else if (ctx->rb_K == 8u) launch_robust_resolve<8>(ctx, a, to_image);
-        else launch_robust_resolve<16>(ctx, a, to_image);
+        const dim3 grid((unsigned)((a.n + 255u) / 256u));
+        with_buckets(ctx->rb_K, [&](auto K) {
+            if (to_image) hipLaunchKernelGGL((robust_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((robust_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+        });
         HIPCHK(ctx, hipGetLastError());
     }
     if (!to_image) ctx->rb_resolved = true;
@@ -2770,9 +2836,7 @@ extern "C" int rtgl_robust_error_estimate(rtgl_context *ctx, const rtgl_robust_e
     s.frames_now = (int32_t)ctx->rb_N; s.frames_snapshot = 0;
     s.footprint = (uint32_t)rt_spread_plan::footprint(ctx->width, ctx->height); s.quantile_permille = P.quantile_permille; s.c = 1.0f;
     const dim3 grid(tx, ty);
-    if (ctx->rb_K == 4u) hipLaunchKernelGGL(spread_tiles_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
-    else if (ctx->rb_K == 8u) hipLaunchKernelGGL(spread_tiles_kernel<8>, grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(spread_tiles_kernel<16>, grid, dim3(256), 0, ctx->stream, a);
+    with_buckets(ctx->rb_K, [&](auto K) { hipLaunchKernelGGL(spread_tiles_kernel<K>, grid, dim3(256), 0, ctx->stream, a); });
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(error_solve_kernel, dim3(1), dim3(256), 0, ctx->stream, s);
     HIPCHK(ctx, hipGetLastError());
@@ -2824,8 +2888,6 @@ extern "C" int rtgl_robust_adaptive_defaults(rtgl_robust_adaptive_params *out)
     return RTGL_OK;
 }
 
-static int robust_adaptive_upload_lists(rtgl_context *ctx) { return upload_tile_lists(ctx, ctx->ra_mask, ctx->ra_blocks, ctx->ra_tiles, ctx->d_ra_lists); }
-
 extern "C" int rtgl_robust_adaptive_begin(rtgl_context *ctx, const rtgl_robust_adaptive_params *params)
 {
     ENTER(ctx);
@@ -2833,45 +2895,31 @@ extern "C" int rtgl_robust_adaptive_begin(rtgl_context *ctx, const rtgl_robust_a
     rt_robust_tiles_plan::Params P;
     memcpy(&P, params, sizeof P);
     if (const char *why = rt_robust_tiles_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_adaptive_begin: ") + why);
-    if (!ctx->parts.empty() || ctx->world > 1)
-        return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_begin: a tiled or multi-device context holds strips, and the tiles are the whole picture's (out of scope): render on a single-device context");
-    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    const size_t px = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height), n_tiles = (size_t)sh.tx * sh.ty, n_blocks = (size_t)sh.blocks_x * sh.blocks_y;
-    if ((uint64_t)n_blocks * 64ull > 0xFFFFFFF0ull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_begin: the footprint does not fit 32-bit ray slots");
-    if (ctx->ra_active) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (work in flight uses the planes and the lists)
-    ctx->ra_active = false; ctx->ra_resolved = false;
+    RCCHK(tile_session_reserve(ctx, ctx->ra, "rtgl_robust_adaptive_begin"));
+    const size_t px = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height);
+    if (ctx->ra.active) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (work in flight uses the planes and the lists)
+    ctx->ra.active = false; ctx->ra_resolved = false;
     if (ctx->ra_K != P.buckets) { RCCHK(buf_release(ctx, ctx->d_ra_buckets)); ctx->ra_K = 0; }
     RCCHK(buf_ensure(ctx, ctx->d_ra_buckets, rt_robust_tiles_plan::bucket_bytes(px, P.buckets)));
     ctx->ra_K = P.buckets;
-    RCCHK(buf_ensure(ctx, ctx->d_ra_samples, rt_robust_tiles_plan::plane_bytes(px)));
     RCCHK(buf_ensure(ctx, ctx->d_ra_out, rt_robust_tiles_plan::plane_bytes(px)));
-    RCCHK(buf_ensure(ctx, ctx->d_ra_records, rt_robust_tiles_plan::record_bytes(n_tiles)));
-    RCCHK(buf_ensure(ctx, ctx->d_ra_counts, rt_robust_tiles_plan::count_bytes(n_tiles)));
-    RCCHK(buf_ensure(ctx, ctx->d_ra_lists, rt_robust_tiles_plan::list_bytes(n_blocks, n_tiles)));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_buckets, 0, rt_robust_tiles_plan::bucket_bytes(px, P.buckets), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_samples, 0, rt_robust_tiles_plan::plane_bytes(px), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->ra.d_samples, 0, rt_robust_tiles_plan::plane_bytes(px), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_out, 0, rt_robust_tiles_plan::plane_bytes(px), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_records, 0, rt_robust_tiles_plan::record_bytes(n_tiles), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ra_counts, 0, rt_robust_tiles_plan::count_bytes(n_tiles), ctx->stream));
     ctx->ra_params = P;
-    rt_adaptive_plan::explicit_mask(sh, std::vector<uint8_t>(n_tiles, 1).data(), ctx->ra_mask);
-    RCCHK(robust_adaptive_upload_lists(ctx));
-    ctx->ra_active = true;
-    return RTGL_OK;
+    return tile_session_open(ctx, ctx->ra);
 }
-
-static const char *const kNoRobustAdaptiveSession = ": no session (rtgl_robust_adaptive_begin has not been called, or rtgl_robust_adaptive_end has)";
 
 // the fold of `source` into the bucket of every active tile's next sample; nothing with an empty list
 static int robust_adaptive_fold(rtgl_context *ctx, const float4 *source)
 {
-    if (ctx->ra_tiles.empty()) return RTGL_OK;
+    if (ctx->ra.tiles.empty()) return RTGL_OK;
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
     TileBucketsFoldArgs a{};
     a.source = source; a.buckets = ctx->d_ra_buckets; a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height);
-    a.n = ctx->d_ra_counts; a.tiles = ctx->d_ra_lists + (size_t)sh.blocks_x * sh.blocks_y; a.K = ctx->ra_K;
+    a.n = ctx->ra.d_counts; a.tiles = ctx->ra.d_lists + (size_t)sh.blocks_x * sh.blocks_y; a.K = ctx->ra_K;
     a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh; a.tx = sh.tx;
-    hipLaunchKernelGGL(tile_buckets_fold_kernel, dim3((unsigned)ctx->ra_tiles.size()), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(tile_buckets_fold_kernel, dim3((unsigned)ctx->ra.tiles.size()), dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
     return RTGL_OK;
 }
@@ -2879,14 +2927,10 @@ static int robust_adaptive_fold(rtgl_context *ctx, const float4 *source)
 extern "C" int rtgl_robust_adaptive_frame(rtgl_context *ctx)
 {
     ENTER(ctx);
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_frame") + kNoRobustAdaptiveSession);
-    if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_frame: rtgl_set_frame_params has not been called");
-    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_adaptive_frame: a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
-    if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_frame: a masked frame is one sample per pixel: samples must be 1");
-    if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_frame: max_bounce must be > 0");
-    if (ctx->ra_blocks.empty()) return RTGL_OK;
-    RCCHK(masked_frame(ctx, ctx->d_ra_samples, ctx->d_ra_lists, (uint32_t)ctx->ra_blocks.size() * 64u));
-    RCCHK(robust_adaptive_fold(ctx, ctx->d_ra_samples));
+    RCCHK(masked_frame_refused(ctx, ctx->ra, "rtgl_robust_adaptive_frame", kNoRobustAdaptiveSession, "rtgl_robust_adaptive_frame: rtgl_set_frame_params has not been called"));
+    if (ctx->ra.blocks.empty()) return RTGL_OK;
+    RCCHK(masked_frame(ctx, ctx->ra.d_samples, ctx->ra.d_lists, (uint32_t)ctx->ra.blocks.size() * 64u));
+    RCCHK(robust_adaptive_fold(ctx, ctx->ra.d_samples));
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->timed = true;
     return RTGL_OK;
@@ -2895,7 +2939,7 @@ extern "C" int rtgl_robust_adaptive_frame(rtgl_context *ctx)
 extern "C" int rtgl_robust_adaptive_accumulate(rtgl_context *ctx)
 {
     ENTER(ctx);
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_accumulate") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_accumulate") + kNoRobustAdaptiveSession);
     return robust_adaptive_fold(ctx, ctx->d_image);
 }
 
@@ -2903,53 +2947,29 @@ extern "C" int rtgl_robust_adaptive_update(rtgl_context *ctx, rtgl_adaptive_summ
 {
     ENTER(ctx);
     if (!summary_out) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_update: summary_out is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_update") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_update") + kNoRobustAdaptiveSession);
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    const size_t n_tiles = (size_t)sh.tx * sh.ty;
     TileBucketsEstimateArgs a{};
-    a.buckets = ctx->d_ra_buckets; a.records = ctx->d_ra_records; a.n = ctx->d_ra_counts; a.m = ctx->d_ra_counts + n_tiles;
+    a.buckets = ctx->d_ra_buckets; a.records = ctx->ra.d_records; a.n = ctx->ra.d_counts; a.m = ctx->ra.d_counts + (size_t)sh.tx * sh.ty;
     a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height);
     a.width = ctx->width; a.fw = sh.fw; a.fh = sh.fh;
     a.gain = ctx->ra_params.gain; a.floor_ = ctx->ra_params.floor; a.threshold = ctx->ra_params.threshold;
     const dim3 grid((unsigned)sh.tx, (unsigned)sh.ty);
-    if (ctx->ra_K == 4u) hipLaunchKernelGGL(tile_buckets_estimate_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
-    else if (ctx->ra_K == 8u) hipLaunchKernelGGL(tile_buckets_estimate_kernel<8>, grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(tile_buckets_estimate_kernel<16>, grid, dim3(256), 0, ctx->stream, a);
+    with_buckets(ctx->ra_K, [&](auto K) { hipLaunchKernelGGL(tile_buckets_estimate_kernel<K>, grid, dim3(256), 0, ctx->stream, a); });
     HIPCHK(ctx, hipGetLastError());
-    std::vector<rt_adaptive_plan::Tile> records(n_tiles);
-    HIPCHK(ctx, hipMemcpyAsync(records.data(), ctx->d_ra_records, n_tiles * sizeof(rt_adaptive_plan::Tile), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t t = 0; t < (uint32_t)n_tiles; ++t) ctx->ra_mask[t] = rt_adaptive_plan::active(sh, t, records[t], ctx->ra_params.min_samples, ctx->ra_params.max_samples) ? 1 : 0;
-    RCCHK(robust_adaptive_upload_lists(ctx));
-    const rt_adaptive_plan::Summary s = rt_adaptive_plan::summary(sh, records.data(), ctx->ra_mask, (uint32_t)ctx->ra_blocks.size(), ctx->ra_params.max_samples);
-    memcpy(summary_out, &s, sizeof s);
-    return RTGL_OK;
+    return tile_session_update(ctx, ctx->ra, ctx->ra_params.min_samples, ctx->ra_params.max_samples, summary_out);
 }
 
 extern "C" int rtgl_robust_adaptive_set_mask(rtgl_context *ctx, const uint8_t *tiles)
 {
     ENTER(ctx);
-    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_set_mask: tiles is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_set_mask") + kNoRobustAdaptiveSession);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (frames in flight read the lists about to be replaced)
-    rt_adaptive_plan::explicit_mask(rt_adaptive_plan::shape(ctx->width, ctx->height), tiles, ctx->ra_mask);
-    return robust_adaptive_upload_lists(ctx);
+    return tile_session_set_mask(ctx, ctx->ra, "rtgl_robust_adaptive_set_mask", kNoRobustAdaptiveSession, tiles);
 }
 
 extern "C" int rtgl_robust_adaptive_get_mask(rtgl_context *ctx, uint8_t *tiles)
 {
     ENTER(ctx);
-    if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_robust_adaptive_get_mask: tiles is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_get_mask") + kNoRobustAdaptiveSession);
-    memcpy(tiles, ctx->ra_mask.data(), ctx->ra_mask.size());
-    return RTGL_OK;
-}
-
-template <int K>
-static void launch_tile_buckets_resolve(rtgl_context *ctx, const TileBucketsResolveArgs &a, const dim3 &grid, bool to_image)
-{
-    if (to_image) hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+    return tile_session_get_mask(ctx, ctx->ra, "rtgl_robust_adaptive_get_mask", kNoRobustAdaptiveSession, tiles);
 }
 
 extern "C" int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust_resolve_params *params)
@@ -2959,21 +2979,22 @@ extern "C" int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust
     rt_robust_plan::ResolveParams P;
     memcpy(&P, params, sizeof P);
     if (const char *why = rt_robust_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_robust_adaptive_resolve: ") + why);
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_resolve") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_resolve") + kNoRobustAdaptiveSession);
     const bool to_image = P.dest == rt_robust_plan::kDestImage;
     if (to_image) {                                       // on the host, what rtgl_robust_resolve with dest IMAGE does
         ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
-        ctx->ad_active = false;                           // (adaptive sampling: ... and the session ends)
+        ctx->ad.active = false;                           // (adaptive sampling: ... and the session ends)
     }
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
     TileBucketsResolveArgs a{};
     a.buckets = ctx->d_ra_buckets; a.out = to_image ? ctx->d_image : ctx->d_ra_out;
-    a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height); a.n = ctx->d_ra_counts;
+    a.plane = rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height); a.n = ctx->ra.d_counts;
     a.width = ctx->width; a.height = ctx->height; a.fw = sh.fw; a.fh = sh.fh; a.gain = P.gain;
     const dim3 grid((unsigned)sh.tx, (unsigned)sh.ty);
-    if (ctx->ra_K == 4u) launch_tile_buckets_resolve<4>(ctx, a, grid, to_image);
-    else if (ctx->ra_K == 8u) launch_tile_buckets_resolve<8>(ctx, a, grid, to_image);
-    else launch_tile_buckets_resolve<16>(ctx, a, grid, to_image);
+    with_buckets(ctx->ra_K, [&](auto K) {
+        if (to_image) hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 1>), grid, dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((tile_buckets_resolve_kernel<K, 0>), grid, dim3(256), 0, ctx->stream, a);
+    });
     HIPCHK(ctx, hipGetLastError());
     if (!to_image) ctx->ra_resolved = true;
     return RTGL_OK;
@@ -2982,18 +3003,18 @@ extern "C" int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust
 extern "C" int rtgl_robust_adaptive_end(rtgl_context *ctx)
 {
     ENTER(ctx);
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_end") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_end") + kNoRobustAdaptiveSession);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (frames, folds and resolves in flight use the buffers)
-    ctx->ra_active = false; ctx->ra_resolved = false; ctx->ra_K = 0;
-    ctx->ra_mask.clear(); ctx->ra_blocks.clear(); ctx->ra_tiles.clear();
-    return buf_release(ctx, ctx->d_ra_buckets, ctx->d_ra_samples, ctx->d_ra_out, ctx->d_ra_records, ctx->d_ra_counts, ctx->d_ra_lists);
+    ctx->ra.active = false; ctx->ra_resolved = false; ctx->ra_K = 0;
+    ctx->ra.mask.clear(); ctx->ra.blocks.clear(); ctx->ra.tiles.clear();
+    return buf_release(ctx, ctx->d_ra_buckets, ctx->ra.d_samples, ctx->d_ra_out, ctx->ra.d_records, ctx->ra.d_counts, ctx->ra.d_lists);
 }
 
 extern "C" int rtgl_read_robust_adaptive_f32(rtgl_context *ctx, float *rgba)
 {
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_f32: rgba is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_f32") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_f32") + kNoRobustAdaptiveSession);
     if (!ctx->ra_resolved) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_robust_adaptive_f32: no rtgl_robust_adaptive_resolve with dest RTGL_ROBUST_DEST_BUFFER since rtgl_robust_adaptive_begin");
     return read_rows(ctx, rgba, ctx->d_ra_out, 16);
 }
@@ -3002,7 +3023,7 @@ extern "C" int rtgl_read_robust_adaptive_bucket_f32(rtgl_context *ctx, uint32_t 
 {
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_bucket_f32: rgba is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_bucket_f32") + kNoRobustAdaptiveSession);
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_bucket_f32") + kNoRobustAdaptiveSession);
     if (bucket >= ctx->ra_K) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_bucket_f32: bucket >= buckets");
     return read_rows(ctx, rgba, ctx->d_ra_buckets + (size_t)bucket * rt_robust_tiles_plan::plane_pixels(ctx->width, ctx->height), 16);
 }
@@ -3011,20 +3032,15 @@ extern "C" int rtgl_read_robust_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_
 {
     ENTER(ctx);
     if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "rtgl_read_robust_adaptive_tiles: tiles is NULL");
-    if (!ctx->ra_active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_tiles") + kNoRobustAdaptiveSession);
-    const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
-    HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_ra_records, (size_t)sh.tx * sh.ty * sizeof(rtgl_adaptive_tile), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (tx) *tx = (uint32_t)sh.tx;
-    if (ty) *ty = (uint32_t)sh.ty;
-    return RTGL_OK;
+    if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_read_robust_adaptive_tiles") + kNoRobustAdaptiveSession);
+    return tile_session_read_tiles(ctx, ctx->ra, tiles, tx, ty);
 }
 
 extern "C" void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx)
 {
     if (!ctx) return nullptr;
-    if (!ctx->ra_active) { ctx->error = std::string("rtgl_device_robust_adaptive_tiles") + kNoRobustAdaptiveSession; return nullptr; }
-    return (void *)ctx->d_ra_records;
+    if (!ctx->ra.active) { ctx->error = std::string("rtgl_device_robust_adaptive_tiles") + kNoRobustAdaptiveSession; return nullptr; }
+    return (void *)ctx->ra.d_records;
 }
 
 // ---- rtgl_robust_denoise: the session's resolve and the guided filter in one call (rt_bucket_guide.hpp, rt_bucket_guide_plan.hpp) -------------
@@ -3040,14 +3056,6 @@ extern "C" int rtgl_robust_denoise_defaults(rtgl_robust_denoise_params *out)
     const rt_bucket_guide_plan::Params p = rt_bucket_guide_plan::default_params();
     memcpy(out, &p, sizeof p);
     return RTGL_OK;
-}
-
-template <int K>
-static void launch_bucket_guide(rtgl_context *ctx, const BucketGuideArgs &a, bool demod)
-{
-    const dim3 grid(rt_bucket_guide_plan::tiles_x(a.width), rt_bucket_guide_plan::tiles_y(a.height));
-    if (demod) hipLaunchKernelGGL((bucket_guide_kernel<K, true>), grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((bucket_guide_kernel<K, false>), grid, dim3(256), 0, ctx->stream, a);
 }
 
 extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_params *params)
@@ -3080,9 +3088,11 @@ extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_
     b.inv_normal = use_n ? 1.0f / (P.sigma_normal * P.sigma_normal) : 0.0f;
     b.sigma_position = P.sigma_position;
     b.use_normal = use_n; b.use_position = use_p; b.final_image = P.passes == 0u;
-    if (ctx->rb_K == 4u) launch_bucket_guide<4>(ctx, b, demod);
-    else if (ctx->rb_K == 8u) launch_bucket_guide<8>(ctx, b, demod);
-    else launch_bucket_guide<16>(ctx, b, demod);
+    const dim3 grid(rt_bucket_guide_plan::tiles_x(b.width), rt_bucket_guide_plan::tiles_y(b.height));
+    with_buckets(ctx->rb_K, [&](auto K) {
+        if (demod) hipLaunchKernelGGL((bucket_guide_kernel<K, true>), grid, dim3(256), 0, ctx->stream, b);
+        else hipLaunchKernelGGL((bucket_guide_kernel<K, false>), grid, dim3(256), 0, ctx->stream, b);
+    });
     HIPCHK(ctx, hipGetLastError());
     GuidedArgs a{};
     a.image = ctx->d_denoised;                            // (the last pass reads only its own pixel's alpha there, before it writes that pixel)
@@ -3092,18 +3102,7 @@ extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_
     a.lum2 = P.sigma_lum * P.sigma_lum;
     a.inv_normal = b.inv_normal; a.sigma_position = P.sigma_position;
     a.use_normal = use_n; a.use_position = use_p; a.demodulate = demod;
-    for (uint32_t k = 0; k < P.passes; ++k) {
-        const bool last = k + 1u == P.passes;
-        a.src = ctx->d_dn_scratch[k & 1u];
-        a.dst = last ? ctx->d_denoised : ctx->d_dn_scratch[(k + 1u) & 1u];
-        a.step = 1 << k; a.step_log2 = (int)k;
-        if (last && demod) launch_guided<true, true>(ctx, a);
-        else if (last) launch_guided<true, false>(ctx, a);
-        else launch_guided<false, false>(ctx, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    ctx->has_denoised = true; ctx->has_dn_variance = true;
-    return RTGL_OK;
+    return launch_guided_passes(ctx, a, P.passes, demod);
 }
 
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)

@@ -694,6 +694,35 @@ class Context:
         """Device pointer of the tile records (0 before the first successful error_estimate(): see the context's last error)."""
         return int(self.lib.rtgl_device_error_tiles(self.h) or 0)
 
+    # --- masked tiles: what adaptive_* and robust_adaptive_* share; `fn` is the library function of the caller's kind
+    def _tiles_shape(self):
+        return (self.height + 15) // 16, (self.width + 15) // 16
+
+    def _tile_update(self, fn) -> dict:
+        s = CAdaptiveSummary()
+        self._chk(fn(self.h, C.byref(s)))
+        out = {k: int(getattr(s, k)) for k in ("tiles_total", "tiles_active", "tiles_converged", "tiles_capped", "blocks_active", "samples_min",
+                                               "samples_max", "converged", "samples_total")}
+        out["max_tile_mse"] = np.frombuffer(bytes(s), np.float32)[10]      # (the bits, not a round trip through a Python float)
+        return out
+
+    def _tile_set_mask(self, fn, tiles):
+        t = np.ascontiguousarray(np.asarray(tiles) != 0, np.uint8)
+        assert t.shape == self._tiles_shape()
+        self._chk(fn(self.h, _ptr(t)))
+
+    def _tile_get_mask(self, fn) -> np.ndarray:
+        out = np.zeros(self._tiles_shape(), np.uint8)
+        self._chk(fn(self.h, _ptr(out)))
+        return out
+
+    def _tile_records(self, fn) -> np.ndarray:
+        out = np.zeros(self._tiles_shape(), ADAPTIVE_TILE_DTYPE)
+        nx, ny = C.c_uint32(), C.c_uint32()
+        self._chk(fn(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
+        assert (int(ny.value), int(nx.value)) == out.shape
+        return out
+
     # --- adaptive sampling
     def adaptive_begin(self, threshold=None, floor=None, min_samples=None, max_samples=None):
         """Open a session of masked frames (rtgl_adaptive_begin): the image is cleared, every tile is active and has no sample.  None keeps
@@ -719,34 +748,18 @@ class Context:
     def adaptive_update(self) -> dict:
         """Estimate the tiles that were sampled since their snapshot, set the mask from the records (rtgl_adaptive_update; synchronises)
         and return the summary: ints, and max_tile_mse as np.float32."""
-        s = CAdaptiveSummary()
-        self._chk(self.lib.rtgl_adaptive_update(self.h, C.byref(s)))
-        out = {k: int(getattr(s, k)) for k in ("tiles_total", "tiles_active", "tiles_converged", "tiles_capped", "blocks_active", "samples_min",
-                                               "samples_max", "converged", "samples_total")}
-        out["max_tile_mse"] = np.frombuffer(bytes(s), np.float32)[10]      # (the bits, not a round trip through a Python float)
-        return out
-
-    def _tiles_shape(self):
-        return (self.height + 15) // 16, (self.width + 15) // 16
+        return self._tile_update(self.lib.rtgl_adaptive_update)
 
     def adaptive_set_mask(self, tiles):
         """An explicit mask (ty, tx), non-zero = active, until the next adaptive_update()."""
-        t = np.ascontiguousarray(np.asarray(tiles) != 0, np.uint8)
-        assert t.shape == self._tiles_shape()
-        self._chk(self.lib.rtgl_adaptive_set_mask(self.h, _ptr(t)))
+        self._tile_set_mask(self.lib.rtgl_adaptive_set_mask, tiles)
 
     def adaptive_get_mask(self) -> np.ndarray:
-        out = np.zeros(self._tiles_shape(), np.uint8)
-        self._chk(self.lib.rtgl_adaptive_get_mask(self.h, _ptr(out)))
-        return out
+        return self._tile_get_mask(self.lib.rtgl_adaptive_get_mask)
 
     def read_adaptive_tiles(self) -> np.ndarray:
         """The tile records as a structured array (ty, tx) of ADAPTIVE_TILE_DTYPE; tile row 0 = image row 0."""
-        out = np.zeros(self._tiles_shape(), ADAPTIVE_TILE_DTYPE)
-        nx, ny = C.c_uint32(), C.c_uint32()
-        self._chk(self.lib.rtgl_read_adaptive_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
-        assert (int(ny.value), int(nx.value)) == out.shape
-        return out
+        return self._tile_records(self.lib.rtgl_read_adaptive_tiles)
 
     def device_adaptive_tiles_ptr(self) -> int:
         """Device pointer of the tile records (0 before the first adaptive_begin(): see the context's last error)."""
@@ -766,16 +779,19 @@ class Context:
         """Fold the image as it stands, taken as one sample, into the next bucket (rtgl_robust_accumulate)."""
         self._chk(self.lib.rtgl_robust_accumulate(self.h))
 
-    def robust_resolve(self, gain=None, dest=None):
-        """The trimmed mean of the buckets (rtgl_robust_resolve) into the output plane (dest ROBUST_DEST_BUFFER: read_robust()) or into
-        the accumulation image (ROBUST_DEST_IMAGE).  None keeps the library's default."""
+    def _resolve(self, fn, gain, dest):      # (robust_resolve and robust_adaptive_resolve)
         p = CRobustResolveParams()
         self._chk(self.lib.rtgl_robust_defaults(None, C.byref(p)))
         if gain is not None:
             p.gain = float(gain)
         if dest is not None:
             p.dest = int(dest)
-        self._chk(self.lib.rtgl_robust_resolve(self.h, C.byref(p)))
+        self._chk(fn(self.h, C.byref(p)))
+
+    def robust_resolve(self, gain=None, dest=None):
+        """The trimmed mean of the buckets (rtgl_robust_resolve) into the output plane (dest ROBUST_DEST_BUFFER: read_robust()) or into
+        the accumulation image (ROBUST_DEST_IMAGE).  None keeps the library's default."""
+        self._resolve(self.lib.rtgl_robust_resolve, gain, dest)
 
     def robust_end(self):
         self._chk(self.lib.rtgl_robust_end(self.h))
@@ -861,34 +877,19 @@ class Context:
     def robust_adaptive_update(self) -> dict:
         """Estimate the tiles whose count has moved, set the mask from the records (rtgl_robust_adaptive_update; synchronises) and return
         the summary as adaptive_update() does."""
-        s = CAdaptiveSummary()
-        self._chk(self.lib.rtgl_robust_adaptive_update(self.h, C.byref(s)))
-        out = {k: int(getattr(s, k)) for k in ("tiles_total", "tiles_active", "tiles_converged", "tiles_capped", "blocks_active", "samples_min",
-                                               "samples_max", "converged", "samples_total")}
-        out["max_tile_mse"] = np.frombuffer(bytes(s), np.float32)[10]      # (the bits, not a round trip through a Python float)
-        return out
+        return self._tile_update(self.lib.rtgl_robust_adaptive_update)
 
     def robust_adaptive_set_mask(self, tiles):
         """An explicit mask (ty, tx), non-zero = active, until the next robust_adaptive_update()."""
-        t = np.ascontiguousarray(np.asarray(tiles) != 0, np.uint8)
-        assert t.shape == self._tiles_shape()
-        self._chk(self.lib.rtgl_robust_adaptive_set_mask(self.h, _ptr(t)))
+        self._tile_set_mask(self.lib.rtgl_robust_adaptive_set_mask, tiles)
 
     def robust_adaptive_get_mask(self) -> np.ndarray:
-        out = np.zeros(self._tiles_shape(), np.uint8)
-        self._chk(self.lib.rtgl_robust_adaptive_get_mask(self.h, _ptr(out)))
-        return out
+        return self._tile_get_mask(self.lib.rtgl_robust_adaptive_get_mask)
 
     def robust_adaptive_resolve(self, gain=None, dest=None):
         """The trimmed mean of the buckets with every pixel's N taken from its tile (rtgl_robust_adaptive_resolve) into the session's output
         plane (dest ROBUST_DEST_BUFFER: read_robust_adaptive()) or into the accumulation image (ROBUST_DEST_IMAGE)."""
-        p = CRobustResolveParams()
-        self._chk(self.lib.rtgl_robust_defaults(None, C.byref(p)))
-        if gain is not None:
-            p.gain = float(gain)
-        if dest is not None:
-            p.dest = int(dest)
-        self._chk(self.lib.rtgl_robust_adaptive_resolve(self.h, C.byref(p)))
+        self._resolve(self.lib.rtgl_robust_adaptive_resolve, gain, dest)
 
     def robust_adaptive_end(self):
         self._chk(self.lib.rtgl_robust_adaptive_end(self.h))
@@ -906,11 +907,7 @@ class Context:
 
     def read_robust_adaptive_tiles(self) -> np.ndarray:
         """The session's tile records as a structured array (ty, tx) of ADAPTIVE_TILE_DTYPE; tile row 0 = image row 0."""
-        out = np.zeros(self._tiles_shape(), ADAPTIVE_TILE_DTYPE)
-        nx, ny = C.c_uint32(), C.c_uint32()
-        self._chk(self.lib.rtgl_read_robust_adaptive_tiles(self.h, _ptr(out), C.byref(nx), C.byref(ny)))
-        assert (int(ny.value), int(nx.value)) == out.shape
-        return out
+        return self._tile_records(self.lib.rtgl_read_robust_adaptive_tiles)
 
     def device_robust_adaptive_tiles_ptr(self) -> int:
         """Device pointer of those records (0 without a session: see the context's last error)."""

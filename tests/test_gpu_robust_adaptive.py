@@ -342,13 +342,25 @@ def test_the_session_leaves_every_other_buffer_alone(rt, randoms):
     ctx.read_robust_adaptive_tiles()
     ctx.read_robust_adaptive_bucket(K - 1)
     unchanged("update, masks, resolve into the buffer, read-outs")
-    # the adaptive session is still its mirror's
+    # the adaptive session is still its mirror's under a mask of its own, and its mask, frame and update move nothing of the open robust
+    # adaptive session: the two kinds share their host code, not their state
+    def session():
+        return dict(mask=ctx.robust_adaptive_get_mask(), tiles=ctx.read_robust_adaptive_tiles(),
+                    buckets=np.stack([ctx.read_robust_adaptive_bucket(j) for j in range(K)]))
+    held = session()
+    masks = rai.named_masks(h, w)
+    own = next(m for m in (masks["one"], masks["checker"]) if m.tobytes() != held["mask"].tobytes())
+    ctx.adaptive_set_mask(own)
+    mirror.set_mask(own)
+    assert ctx.adaptive_get_mask().tobytes() == own.tobytes()
     ctx.adaptive_frame(base.replace(random=randoms[5]))
     ordinary.render(base.replace(frames=0, reset_flag=1, random=randoms[5]))
     mirror.frame(ordinary.read_image())
     assert same(ctx.read_image(), mirror.image)
     got, want = ctx.adaptive_update(), mirror.update()
     assert am.same_summary(got, want) == [] and ctx.read_adaptive_tiles().tobytes() == np.ascontiguousarray(mirror.records).tobytes()
+    for key, value in session().items():
+        assert value.tobytes() == held[key].tobytes(), f"adaptive set_mask, frame and update: {key}"
     # the resolve into the image: the picture is an image like any other, the adaptive session ends, the snapshot is dropped
     before = others()
     ctx.robust_adaptive_resolve(gain=1.0)

@@ -224,11 +224,26 @@ def test_plan_header_is_host_only_and_the_library_uses_it():
         code = "".join(re.sub(r"//.*", "", line) for line in f)
     for name in ("invalid", "default_params", "plane_pixels", "plane_bytes", "bucket_bytes", "count_bytes", "record_bytes", "list_bytes"):
         assert f"rt_robust_tiles_plan::{name}(" in code, name
-    # the session's shapes, mask rule, lists and summary are adaptive sampling's, and both kinds of masked frame share one body
-    section = code[code.index("rtgl_robust_adaptive_defaults"):]
-    for name in ("shape", "explicit_mask", "active", "summary"):
-        assert f"rt_adaptive_plan::{name}(" in section, name
-    assert "upload_tile_lists(ctx, ctx->ra_mask" in section and code.count("rt_adaptive_plan::build_lists(") == 1      # (one list builder for both sessions)
+    # the session's shapes, mask rule, lists and summary are adaptive sampling's, each used in one place that serves both kinds of session
+    for name in ("shape", "explicit_mask", "active", "summary", "build_lists"):
+        assert f"rt_adaptive_plan::{name}(" in code, name
+    for name in ("build_lists", "active", "summary"):
+        assert code.count(f"rt_adaptive_plan::{name}(") == 1, name
+    # the shared host bodies: defined once, taking the session, and called by the entry points of both kinds and by nothing else
+    def callers(helper):
+        assert len(re.findall(rf"^static int {helper}\(rtgl_context \*ctx, (?:const )?TileSession &s[,)]", code, re.M)) == 1, helper
+        found = []
+        for m in re.finditer(rf"\b{helper}\(ctx, ctx->(\w+)[,)]", code):
+            found.append((re.findall(r'^(?:extern "C" |static )\S+ \*?(\w+)\(', code[:m.start()], re.M)[-1], m.group(1)))
+        return sorted(found)
+    assert callers("tile_session_update") == [("rtgl_adaptive_update", "ad"), ("rtgl_robust_adaptive_update", "ra")]
+    assert callers("tile_session_set_mask") == [("rtgl_adaptive_set_mask", "ad"), ("rtgl_robust_adaptive_set_mask", "ra")]
+    assert callers("tile_session_get_mask") == [("rtgl_adaptive_get_mask", "ad"), ("rtgl_robust_adaptive_get_mask", "ra")]
+    assert callers("tile_session_read_tiles") == [("rtgl_read_adaptive_tiles", "ad"), ("rtgl_read_robust_adaptive_tiles", "ra")]
+    for helper in ("tile_session_update", "tile_session_set_mask", "tile_session_get_mask", "tile_session_read_tiles"):
+        assert len(re.findall(rf"\b{helper}\(", code)) == 3, helper      # (the definition and the two calls)
+    # neither kind keeps a mask, lists or shared buffers of its own beside the two sessions
+    assert len(re.findall(r"^\s*TileSession (ad|ra);", code, re.M)) == 2 and not re.search(r"\b(ad|ra)_(mask|blocks|tiles|active)\b|\bd_(ad|ra)_(samples|records|counts|lists)\b", code)
     assert len(re.findall(r"\bmasked_frame\(ctx,", code)) == 2 and len(re.findall(r"\blaunch_wavefront\(ctx, sc, frames, im, n0, nullptr, nullptr, list\)", code)) == 1
     with open(os.path.join(CSRC, "rt_robust_tiles.hpp")) as f:
         kernels = "".join(re.sub(r"//.*", "", line) for line in f)

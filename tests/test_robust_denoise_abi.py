@@ -182,10 +182,16 @@ def test_plan_header_is_host_only_and_the_library_uses_it():
     assert "#pragma clang fp contract(off)" in kernels and "atomic" not in kernels and "store_through(" in kernels
     stores = re.findall(r"^\s*(?:a\.\w+\[[^\]]*\]|\*\s*a\.\w+)\s*=", kernels, re.M)
     assert not stores, stores                                        # every global store goes through store_through
-    # the passes are the existing ones, launched as rtgl_denoise_guided launches them
-    body = code[code.index('extern "C" int rtgl_robust_denoise('):]
-    body = body[:body.index("\n}\n")]
-    assert body.count("launch_guided<") == 3 and "guided_prepare_kernel" not in body and "buf_ensure(" in body and "hipMalloc" not in body
+    # the passes are the existing ones, launched by the one function that launches them for rtgl_denoise_guided
+    def body_of(entry):
+        body = code[code.index(f'extern "C" int {entry}('):]
+        return body[:body.index("\n}\n")]
+    body = body_of("rtgl_robust_denoise")
+    assert body.count("launch_guided_passes(") == 1 and body_of("rtgl_denoise_guided").count("launch_guided_passes(") == 1
+    assert code.count("launch_guided_passes(") == 3 and code.count("launch_guided<") == 3      # (the definition and the two calls; the three forms of a pass)
+    passes = code[code.index("static int launch_guided_passes("):]
+    assert passes[:passes.index("\n}\n")].count("launch_guided<") == 3
+    assert "launch_guided<" not in body and "guided_prepare_kernel" not in body and "buf_ensure(" in body and "hipMalloc" not in body
 
 
 @pytest.fixture(scope="module")
