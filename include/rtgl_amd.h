@@ -954,7 +954,7 @@ int rtgl_read_robust_adaptive_bucket_f32(rtgl_context *ctx, uint32_t bucket, flo
 int rtgl_read_robust_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *tiles, uint32_t *tx, uint32_t *ty);
 void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx);
 /* keys: "kernel" (enum above), "wf_rays" (rays per lane 1/2/4/8), "wf_mode" (0 scalar-fed, 1 LDS tiles),
- * "wf_chunk" (triangles per work item of the split intersect kernel, multiple of 64), "wf_early" (leading bounces
+ * "wf_chunk" (triangles per work item of the split intersect kernel, a multiple of 64 in [64, 4096]), "wf_early" (leading bounces
  * that use the wave-level edge short circuit), "wf_packed" (v_pk_fma_f32 ray pairs on/off), "mf_chunk_quads" (kernel 4: 40-triangle quads
  * per work item = per block's LDS-resident chunk, 1..32), "scan_waves" (waves per SIMD of the kernel-4 scan: 0 default (= 2), 1, 2), "scan_dynamic" (work distribution of the kernel-4 scan: 0 chosen by the mesh (default), 1 static turns, 2 dynamic claims, 3 planned equal-cost intervals, 4 turns + a claimed tail),
  * "narrow_fused" (kernel 4, also RTGL_AMD_NARROW_FUSED, read when a context is created: who gives the survivors of the scan their exact test.  0: narrow_phase_kernel,
@@ -979,11 +979,17 @@ void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx);
  * point submits the waiting frames first, so the image a caller reads is always complete; frames that differ in samples, bounce limit,
  * environment switch or background close a batch early; with "counters", "rng_state", "aov" or "kernel_timing" on, with more than one sample
  * per frame and for scenes without triangles frames are rendered one by one; rtgl_destroy submits frames that are still waiting;
- * rtgl_device_image returns NULL when that submission fails) */
+ * rtgl_device_image returns NULL when that submission fails), "debug_skip_exact" (set only -- rtgl_get_option does not know it.  Timing
+ * diagnostics of kernel 4: 0 (default) off; 1 the scan's survivors are dropped instead of tested and 2 the broad phase rejects everything:
+ * the image is WRONG for both; 3 every segment goes through the list loop, image unchanged) */
 int rtgl_set_option(rtgl_context *ctx, const char *key, int value);
-/* rtgl_get_option also answers read-only keys: "kernel_in_use" (the variant the last frame ran); "camera_lean_frames" (the frames of this
- * context that took the lean camera bounce, option "camera_lean": tells a taken path from a fallback); "shade_pass_launches" (the shade
- * launches of this context that made one pass, option "shade_pass") */
+/* rtgl_get_option answers every key above but "debug_skip_exact" with the option's value, except "mf_group_quads": that is the value in use
+ * (the option takes effect when the next frame rebuilds the broad-phase data).  It also answers read-only keys: "kernel_in_use" (the
+ * variant the last frame ran, -1 before the first); "mf_sets" (kernel 4: the 32-ray sets per scan wave, a constant of the build);
+ * "camera_lean_frames" (the frames of this context that took the lean camera bounce, option "camera_lean": tells a taken path from a
+ * fallback); "shade_pass_launches" (the shade launches of this context that made one pass, option "shade_pass"); "cand_region_pairs"
+ * (kernel 4: the current capacity, in records, of one scan wave's region of the candidate buffer); "device_mbytes" (the device memory this
+ * context holds, MiB rounded up) */
 int rtgl_get_option(rtgl_context *ctx, const char *key, int *value);
 /* elapsed GPU milliseconds of the last rtgl_render_frame (HIP events on the context's stream) */
 int rtgl_last_frame_ms(rtgl_context *ctx, float *ms);

@@ -41,6 +41,7 @@
 #include "rt_scan_launch.hpp"
 #include "rt_shade_launch.hpp"
 #include "rt_camera_keep.hpp"
+#include "rt_options.hpp"
 
 #pragma clang fp contract(off)
 
@@ -262,18 +263,14 @@ struct rtgl_context {
     // the camera rays of two frames differ by the depth-of-field jitter only, so bits certified for one frame's rays with the packet bounds
     // widened by that jitter hold for all of them and packet_cull_kernel is skipped on bounce 0 (a third of its work)
     uint32_t *d_keep0 = nullptr; size_t keep0_capacity = 0; bool keep0_valid = false; rt_camera_keep::Camera keep0_camera{}; uint32_t keep0_n0 = 0, keep0_words = 0; uint64_t keep0_scene = 0;
-    int opt_camera_lean = 1;                                // the lean camera bounce on frames that reuse those bits (option "camera_lean", RTGL_AMD_CAMERA_LEAN; rt_wavefront.hpp, generate_rays_kernel)
-    uint32_t camera_lean_frames = 0;                        // frames of this context that took the lean camera bounce
-    int opt_shade_pass = 1;                                 // shade launches: 1 one pass where rt_shade_launch.hpp says so, 0 grid-stride passes everywhere (option "shade_pass", RTGL_AMD_SHADE_PASS)
-    uint32_t shade_pass_launches = 0;                       // launches of this context that took the one-pass shade_kernel
+    uint32_t camera_lean_frames = 0;                        // frames of this context that took the lean camera bounce (option "camera_lean")
+    uint32_t shade_pass_launches = 0;                       // launches of this context that took the one-pass shade_kernel (option "shade_pass")
     uint64_t scene_version = 0;
     void *d_plan = nullptr; size_t plan_capacity = 0;             // planned work distribution of culled scan launches: cost prefix sums per chunk
     void *d_stage = nullptr; size_t stage_capacity = 0;           // ray binning: the staging queue + (key, rank) and the source slot per slot
     uint32_t *d_sort_hist = nullptr; uint32_t sort_bits_alloc = 0;      // two sets of bin counters, used in turns
     bool bin_refusal_said = false;                                     // a refused RTGL_AMD_SORT_OB / _DB pair was reported on stderr
     int sort_set = 0; uint32_t sort_set_bits = 0; bool sort_sets_clean = false;      // the set the next binned bounce counts in; false: zero both first (fresh, or a frame was abandoned half way)
-    int opt_narrow_fused = 1;                // kernel 4: 1 (default) the scan waves test their own survivors at their end (rt_scan.hpp, tail drain), 0 narrow_phase_kernel does (RTGL_AMD_NARROW_FUSED)
-    int opt_sort_move = 1;                   // ray binning's move (rt_wavefront.hpp, WaveBuffers): 1 gathered by packet_cull_kernel, 0 scattered (RTGL_AMD_SORT_MOVE)
     float mesh_lo[3] = {0.0f, 0.0f, 0.0f}, mesh_hi[3] = {0.0f, 0.0f, 0.0f}, mesh_ext = 0.0f;       // box of the triangles' finite vertices (origin cells of the bin key)
     uint2 *d_cand = nullptr; uint32_t cand_regions = 0, cand_region_pairs = 0, cand_region_target = 0; bool cand_fixed = false;
     bool solo_attr_set = false;              // hipFuncAttributeMaxDynamicSharedMemorySize is per device: raised once per context (= per device binding)
@@ -348,8 +345,10 @@ struct rtgl_context {
     uint32_t ra_K = 0; bool ra_resolved = false; rt_robust_tiles_plan::Params ra_params{};
     FrameParams params{};
     bool have_params = false;
-    int opt_kernel = RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, opt_rng_state = 0, opt_counters = 0, opt_kernel_timing = 0, opt_wf_rays = 4, opt_wf_mode = kLds, opt_wf_chunk = 256, opt_wf_early = 0, opt_wf_packed = 0, opt_mf_chunk_quads = 32, opt_mf_group_quads = 32, opt_cull = 3, opt_sort_min_rays = 131072, opt_scan_waves = 0, opt_scan_dynamic = 0, opt_debug_skip_exact = 0, opt_frame_batch = 1, opt_aov = 0, opt_denoise_source = 0, opt_temporal_moments = 0, opt_denoise_variance = 0;
+    rt_options::Options opt;                 // every integer option, with its default (rt_options.hpp)
 };
+static_assert(rt_options::kKernelMega == RTGL_KERNEL_MEGA && rt_options::kKernelRemoved3 == RTGL_KERNEL_REMOVED_3 && rt_options::kKernelSolo == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && rt_options::kAovAll == RTGL_AOV_ALL && rt_options::kScalar == kScalar && rt_options::kLds == kLds, "rt_options.hpp");
+static_assert(rt_options::kBoundGroup == kBoundGroup && (uint32_t)rt_options::kMaxChunk == kMaxChunk && (uint32_t)rt_options::kMfMaxChunkQuads == kMfMaxChunkQuads && (uint32_t)rt_options::kMfMaxGroupQuads == kMfMaxGroupQuads && (uint32_t)rt_options::kBatchMax == kBatchMax, "rt_options.hpp");
 
 static int fail(rtgl_context *ctx, int code, const std::string &msg)
 {
@@ -489,15 +488,10 @@ extern "C" int rtgl_create_tiled(rtgl_context **out, int width, int height, int 
     CCHK(hipMemsetAsync(ctx->d_counters, 0, 64, ctx->stream));
     CCHK(hipStreamSynchronize(ctx->stream));
 #undef CCHK
-    // operational override of the default scan without touching the caller: RTGL_AMD_KERNEL=0, 1, 2 or 4 (rtgl_set_option still wins)
-    if (const char *k = getenv("RTGL_AMD_KERNEL")) { const int v = atoi(k); if (v >= RTGL_KERNEL_MEGA && v <= RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && v != RTGL_KERNEL_REMOVED_3) { ctx->opt_kernel = v; ctx->kernel_explicit = true; } }
-    if (const char *k = getenv("RTGL_AMD_SCAN_WAVES")) { const int v = atoi(k); if (v >= 0 && v <= 2) ctx->opt_scan_waves = v; }   // A/B of the scan's occupancy
-    if (const char *k = getenv("RTGL_AMD_FRAME_BATCH")) { const int v = atoi(k); if (v >= 1 && v <= (int)kBatchMax) ctx->opt_frame_batch = v; }
-    if (const char *k = getenv("RTGL_AMD_SCAN_DYNAMIC")) { const int v = atoi(k); if (v >= 0 && v <= 4) ctx->opt_scan_dynamic = v; }   // ... and of its work distribution
-    if (const char *k = getenv("RTGL_AMD_NARROW_FUSED")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_narrow_fused = v; }   // A/B of the scan's tail drain
-    if (const char *k = getenv("RTGL_AMD_SORT_MOVE")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_sort_move = v; }   // A/B of ray binning's move
-    if (const char *k = getenv("RTGL_AMD_CAMERA_LEAN")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_camera_lean = v; }   // A/B of the lean camera bounce
-    if (const char *k = getenv("RTGL_AMD_SHADE_PASS")) { const int v = atoi(k); if (v == 0 || v == 1) ctx->opt_shade_pass = v; }   // A/B of the one-pass shade launches
+    // the environment's spellings of the options (rt_options.hpp) change this context's defaults; rtgl_set_option still wins.  RTGL_AMD_KERNEL=0, 1, 2
+    // or 4: the operational override of the default scan without touching the caller
+    const uint32_t from_env = rt_options::read_environment(ctx->opt, [](const char *name) -> const char * { return getenv(name); });
+    if (from_env & rt_options::row_bit(&rt_options::Options::kernel)) ctx->kernel_explicit = true;
     *out = ctx;
     return RTGL_OK;
 }
@@ -908,7 +902,7 @@ static int rebuild_triangles(rtgl_context *ctx)
         // quads sharing one local origin: 32 (= a chunk: one ray set-up per work item of the scan) unless the caller chose.  Smaller
         // groups have tighter bounds and fewer survivors (C4: 89 M per frame at 8 quads against 111 M at 32), but every group of a
         // chunk costs the scan a ray set-up and a pipeline fill of its own: 28.4 against 30.0 Mpaths/s
-        ctx->mf_group_quads = ctx->group_explicit ? (uint32_t)ctx->opt_mf_group_quads : 32u;
+        ctx->mf_group_quads = ctx->group_explicit ? (uint32_t)ctx->opt.mf_group_quads : 32u;
         const uint32_t group_tris = ctx->mf_group_quads * kMfQuadTris;
         ctx->n_mf_groups = (ctx->n_tri_visits + group_tris - 1) / group_tris;
         const std::vector<uint32_t> order = kd_order(ctx, visit_tri, group_tris);
@@ -960,7 +954,7 @@ static void kev_mark(rtgl_context *ctx)
 // ---- bounce-wavefront pipeline: buffers + launches ------------------------------------------------
 // the scan launch policy (rt_scan_launch.hpp): what it needs to know of the device, the mesh and the options
 static_assert(rt_scan_launch::kQuadTris == (uint32_t)kMfQuadTris && rt_scan_launch::kQuadTiles == (uint32_t)kMfQuadTiles && rt_scan_launch::kRaysPerWave == SoloCfg::kRaysPerWave, "rt_scan_launch.hpp");
-static rt_scan_launch::Setup scan_setup(const rtgl_context *ctx) { return {(uint32_t)ctx->n_cus, rt_scan_launch::real_quads(ctx->n_mf_groups, ctx->mf_group_quads, ctx->n_tri_visits), (uint32_t)ctx->opt_mf_chunk_quads, ctx->opt_scan_waves, ctx->opt_scan_dynamic, ctx->opt_cull}; }
+static rt_scan_launch::Setup scan_setup(const rtgl_context *ctx) { return {(uint32_t)ctx->n_cus, rt_scan_launch::real_quads(ctx->n_mf_groups, ctx->mf_group_quads, ctx->n_tri_visits), (uint32_t)ctx->opt.mf_chunk_quads, ctx->opt.scan_waves, ctx->opt.scan_dynamic, ctx->opt.cull}; }
 
 static size_t counts_bytes(uint32_t capacity) { return (size_t)(capacity + 1u) * sizeof(uint32_t); }      // ray counts per bounce + the fullest candidate region
 
@@ -994,7 +988,7 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
         if (!ctx->counts_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->counts_ev, hipEventDisableTiming));
         ctx->counts_capacity = max_bounce + 2; ctx->counts_pending = ctx->counts_valid = false; ctx->est_counts.clear();
     }
-    if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
+    if (ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
         const rt_scan_launch::Capacity scan = rt_scan_launch::capacity(scan_setup(ctx));
         const uint32_t need_regions = scan.regions;
         // (a record = one (ray, 5-triangle mask); every queue entry of the scan makes four of them)
@@ -1008,7 +1002,7 @@ static int ensure_wave_buffers(rtgl_context *ctx, uint32_t n0, uint32_t max_boun
         RCCHK(buf_grow(ctx, ctx->d_keep, ctx->keep_capacity, need_keep, need_keep * sizeof(uint32_t)));
         RCCHK(buf_grow(ctx, ctx->d_sched, ctx->sched_capacity, need_sched, need_sched * sizeof(uint32_t)));
         ctx->wb.keep_words = scan.keep_words; ctx->wb.keep = ctx->d_keep; ctx->wb.sched_stride = scan.sched_stride; ctx->wb.sched = ctx->d_sched;
-        if (ctx->opt_cull == 3) {                            // ray binning: staging queue (64-byte records of a, b, c, rng, pixel 4 B), key + rank 8 B, source slot 4 B, and the bin counters
+        if (ctx->opt.cull == 3) {                            // ray binning: staging queue (64-byte records of a, b, c, rng, pixel 4 B), key + rank 8 B, source slot 4 B, and the bin counters
             RCCHK(buf_grow(ctx, ctx->d_stage, ctx->stage_capacity, n0, (size_t)n0 * 80 + 1024));
             uint8_t *p = (uint8_t *)ctx->d_stage;
             const size_t cap = ctx->stage_capacity;
@@ -1068,9 +1062,9 @@ static void launch_bounce(rtgl_context *ctx, const SceneView &sc, const FramePar
 {
     dim3 grid((n0 + 256u * R - 1) / (256u * R));
     if (aov) {
-        if (ctx->opt_counters) hipLaunchKernelGGL((bounce_kernel<R, MODE, true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
+        if (ctx->opt.counters) hipLaunchKernelGGL((bounce_kernel<R, MODE, true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
         else hipLaunchKernelGGL((bounce_kernel<R, MODE, false, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, *aov);
-    } else if (ctx->opt_counters)
+    } else if (ctx->opt.counters)
         hipLaunchKernelGGL((bounce_kernel<R, MODE, true, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
     else
         hipLaunchKernelGGL((bounce_kernel<R, MODE, false, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, AovView{});
@@ -1086,7 +1080,7 @@ static void launch_shade(rtgl_context *ctx, const rt_shade_launch::Launch &L, co
         {{shade_stride_kernel<false, kSort, false>, shade_stride_kernel<false, kSort, true>}, {shade_stride_kernel<true, kSort, false>, shade_stride_kernel<true, kSort, true>}},
         {{shade_kernel<false, kSort, false>, shade_kernel<false, kSort, true>}, {shade_kernel<true, kSort, false>, shade_kernel<true, kSort, true>}}};
     if (L.one_pass) ctx->shade_pass_launches++;
-    hipLaunchKernelGGL(kKernels[L.one_pass][ctx->opt_counters != 0][aov != nullptr], dim3(L.blocks), dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, aov ? *aov : AovView{});
+    hipLaunchKernelGGL(kKernels[L.one_pass][ctx->opt.counters != 0][aov != nullptr], dim3(L.blocks), dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, bounce, rng_out, ctx->d_counters, aov ? *aov : AovView{});
 }
 
 // shade_camera_kernel: bounce 0 of a lean frame, a block per 256 slots of queue 0 (the kernel makes one pass)
@@ -1094,7 +1088,7 @@ template <bool kSort>
 static void launch_shade_camera(rtgl_context *ctx, uint32_t n0, const SceneView &sc, const FrameParams &P, const ImageView &im, uint4 *rng_out)
 {
     const dim3 grid((n0 + 255u) / 256u);
-    if (ctx->opt_counters) hipLaunchKernelGGL((shade_camera_kernel<true, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
+    if (ctx->opt.counters) hipLaunchKernelGGL((shade_camera_kernel<true, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
     else hipLaunchKernelGGL((shade_camera_kernel<false, kSort>), grid, dim3(256), 0, ctx->stream, sc, P, im, ctx->wb, rng_out, ctx->d_counters);
 }
 
@@ -1112,14 +1106,14 @@ static uint32_t estimate_rays(const rtgl_context *ctx, uint32_t n0, uint32_t bou
 template <int R, int MODE>
 static void launch_intersect(rtgl_context *ctx, const SceneView &sc, uint32_t n0, uint32_t bounce)
 {
-    const uint32_t chunk = (uint32_t)ctx->opt_wf_chunk;
+    const uint32_t chunk = (uint32_t)ctx->opt.wf_chunk;
     const uint32_t est = estimate_rays(ctx, n0, bounce);
     dim3 grid((est + 256u * R - 1) / (256u * R), (sc.n_tri_visits + chunk - 1) / chunk);
-    const bool early = bounce < (uint32_t)ctx->opt_wf_early;     // wave-level edge short circuit on the coherent bounces
+    const bool early = bounce < (uint32_t)ctx->opt.wf_early;     // wave-level edge short circuit on the coherent bounces
 #define RTGL_LAUNCH_ISECT(E, P, C) hipLaunchKernelGGL((intersect_kernel<R, MODE, E, P, C>), grid, dim3(256), 0, ctx->stream, sc, ctx->wb, bounce, chunk, ctx->d_counters)
-    if (early) { if (ctx->opt_counters) RTGL_LAUNCH_ISECT(true, false, true); else RTGL_LAUNCH_ISECT(true, false, false); }
-    else if (ctx->opt_wf_packed) { if (ctx->opt_counters) RTGL_LAUNCH_ISECT(false, true, true); else RTGL_LAUNCH_ISECT(false, true, false); }
-    else { if (ctx->opt_counters) RTGL_LAUNCH_ISECT(false, false, true); else RTGL_LAUNCH_ISECT(false, false, false); }
+    if (early) { if (ctx->opt.counters) RTGL_LAUNCH_ISECT(true, false, true); else RTGL_LAUNCH_ISECT(true, false, false); }
+    else if (ctx->opt.wf_packed) { if (ctx->opt.counters) RTGL_LAUNCH_ISECT(false, true, true); else RTGL_LAUNCH_ISECT(false, true, false); }
+    else { if (ctx->opt.counters) RTGL_LAUNCH_ISECT(false, false, true); else RTGL_LAUNCH_ISECT(false, false, false); }
 #undef RTGL_LAUNCH_ISECT
 }
 
@@ -1207,7 +1201,7 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
         // moves its rays out of the staging queue)
         if (!have_bits) {
             hipLaunchKernelGGL(packet_cull_kernel, dim3(L.cull_blocks), dim3(256), 0, ctx->stream, ctx->wb, ctx->d_mf_cull, setup.real_quads * (uint32_t)kMfQuadTiles, bounce, ro_add, sigma_add,
-                               ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt_sort_move == 1));
+                               ctx->d_mf_cull_node, ctx->d_mf_cull_node ? ctx->cull_node_shift : 0u, (uint32_t)(binned && ctx->opt.sort_move == 1));
             if (cached) {
                 // the camera's bits are in the stream: from here on they serve the frames of this camera, image and scene (a frame that
                 // fails drops them again: render_batch)
@@ -1216,12 +1210,12 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
             }
         }
         if (L.dist == 2) {
-            hipLaunchKernelGGL(ctx->opt_counters ? scan_plan_kernel<true> : scan_plan_kernel<false>, dim3(L.chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
+            hipLaunchKernelGGL(ctx->opt.counters ? scan_plan_kernel<true> : scan_plan_kernel<false>, dim3(L.chunks), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
             hipLaunchKernelGGL(scan_plan_base_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->wb, L.chunks);
         }
         if (L.dist == 1) {
             HIPCHK(ctx, hipMemsetAsync(ctx->wb.item_counts, 0, (size_t)L.chunks * sizeof(uint32_t), ctx->stream));
-            hipLaunchKernelGGL(ctx->opt_counters ? cull_items_kernel<true> : cull_items_kernel<false>, dim3(L.items_grid_x, L.items_grid_y), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
+            hipLaunchKernelGGL(ctx->opt.counters ? cull_items_kernel<true> : cull_items_kernel<false>, dim3(L.items_grid_x, L.items_grid_y), dim3(256), 0, ctx->stream, ctx->wb, bounce, L.chunk_quads, setup.real_quads, ctx->d_counters);
         }
     }
     // (testing the survivors of small launches in place instead of launching the narrow phase was measured: never faster --
@@ -1233,9 +1227,9 @@ static int launch_intersect_solo(rtgl_context *ctx, const SceneView &sc, uint32_
 #ifdef RT_SOLO_STAMPS
     const int fused = 0;
 #else
-    const int fused = ctx->opt_narrow_fused;
+    const int fused = ctx->opt.narrow_fused;
 #endif
-    hipLaunchKernelGGL(kScanKernels[ctx->opt_counters != 0][L.W - 1][L.dist], dim3(L.blocks), dim3(256 * L.W), L.lds, ctx->stream, sc, ctx->wb, mf, bounce, L.chunk_quads, L.chunks, ctx->d_counters, ctx->opt_debug_skip_exact, L.cull, fused);
+    hipLaunchKernelGGL(kScanKernels[ctx->opt.counters != 0][L.W - 1][L.dist], dim3(L.blocks), dim3(256 * L.W), L.lds, ctx->stream, sc, ctx->wb, mf, bounce, L.chunk_quads, L.chunks, ctx->d_counters, ctx->opt.debug_skip_exact, L.cull, fused);
     HIPCHK(ctx, hipGetLastError());
     if (!fused) hipLaunchKernelGGL(narrow_phase_kernel, dim3(L.blocks * L.waves, kNarrowSplit), dim3(256), 0, ctx->stream, sc, ctx->wb, mf, bounce, L.blocks * L.waves);
     return RTGL_OK;
@@ -1263,31 +1257,31 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
     // the camera-ray bounce: from kept bits?  And then in its lean form (option "camera_lean"): a single frame of one sample, no first-hit planes
     CameraKeep ck{};
     const FrameParams *const cam = (B == 1 && P.samples == 1u && !masked) ? &P : nullptr;
-    if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && sc.n_tri_visits > 0 && P.max_bounce > 0) RCCHK(camera_keep_decide(ctx, n0, cam, &ck));
-    const bool lean = rt_camera_keep::lean(ck, ctx->opt_camera_lean, aov != nullptr);
+    if (ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && sc.n_tri_visits > 0 && P.max_bounce > 0) RCCHK(camera_keep_decide(ctx, n0, cam, &ck));
+    const bool lean = rt_camera_keep::lean(ck, ctx->opt.camera_lean, aov != nullptr);
     if (lean) ctx->camera_lean_frames++;
     for (uint32_t s = 0; s < P.samples; ++s) {
         const uint32_t n_counts = ctx->counts_capacity + 1u <= 256u ? ctx->counts_capacity + 1u : 0u;      // cleared by generate_rays_kernel's first block
         if (!n_counts) HIPCHK(ctx, hipMemsetAsync(ctx->d_counts, 0, counts_bytes(ctx->counts_capacity), ctx->stream));
         // the scan launches' work counters (rt_scan.hpp): cleared by the first threads of generate_rays_kernel where there are enough of them
         uint32_t n_sched = 0u;
-        if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->d_sched && rt_scan_launch::uses_claim_counters(rt_scan_launch::mesh_dist(scan_setup(ctx)))) {      // (the mesh-level choice, not a launch's dist)
+        if (ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->d_sched && rt_scan_launch::uses_claim_counters(rt_scan_launch::mesh_dist(scan_setup(ctx)))) {      // (the mesh-level choice, not a launch's dist)
             const size_t words = (size_t)(P.max_bounce + 2) * ctx->wb.sched_stride;
             if (words <= (size_t)gen_grid.x * 256u && !getenv("RTGL_AMD_SCHED_FILL")) n_sched = (uint32_t)words;      // (the variable: measurement of the fill launch this replaces)
             else HIPCHK(ctx, hipMemsetAsync(ctx->d_sched, 0, words * sizeof(uint32_t), ctx->stream));
         }
         if (masked)
-            hipLaunchKernelGGL(generate_rays_masked_kernel, gen_grid, dim3(256), 0, ctx->stream, P, im, ctx->wb, masked, n0_frame, ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, n_counts, n_sched);
+            hipLaunchKernelGGL(generate_rays_masked_kernel, gen_grid, dim3(256), 0, ctx->stream, P, im, ctx->wb, masked, n0_frame, ctx->opt.counters ? ctx->d_counters : (Counters *)nullptr, n_counts, n_sched);
         else for (uint32_t f = 0; f < B; ++f)
             hipLaunchKernelGGL(generate_rays_kernel, gen_grid, dim3(256), 0, ctx->stream, frames[f], im, ctx->wb, s, n0_frame,
-                               ctx->opt_counters ? ctx->d_counters : (Counters *)nullptr, f == 0 ? n_counts : 0u, f * n0_frame, B > 1 ? f << 28 : 0u, f == 0 ? n0 : 0u, f == 0 ? n_sched : 0u,
+                               ctx->opt.counters ? ctx->d_counters : (Counters *)nullptr, f == 0 ? n_counts : 0u, f * n0_frame, B > 1 ? f << 28 : 0u, f == 0 ? n0 : 0u, f == 0 ? n_sched : 0u,
                                lean ? 1u : 0u);
         bool binned = false;                                 // the queue of the bounce about to be launched was binned
         for (uint32_t b = 0; b < P.max_bounce; ++b) {
-            const int key = ctx->opt_wf_mode * 10 + ctx->opt_wf_rays;
+            const int key = ctx->opt.wf_mode * 10 + ctx->opt.wf_rays;
             const AovView *aov_b = (s == 0u && b == 0u) ? aov : nullptr;      // the first-hit planes: the camera rays of sample 0
-            if (ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_SPLIT || ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
-                if (sc.n_tri_visits > 0 && ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
+            if (ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_SPLIT || ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
+                if (sc.n_tri_visits > 0 && ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO) {
                     kev_mark(ctx);
                     { const int rc = launch_intersect_solo(ctx, sc, n0, b, binned, b == 0u ? &ck : nullptr, cam); if (rc) return rc; }
                     kev_mark(ctx);
@@ -1309,9 +1303,9 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                 // ray binning: the queue of the next bounce in (direction bin, origin cell) order, where it is long enough to pay for
                 // the three small launches and the extra pass over its rays
                 const uint32_t est_next = estimate_rays(ctx, n0, b + 1u);
-                const bool bin_next = ctx->opt_kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->opt_cull == 3 && sc.n_tri_visits > 0 && b + 1u < P.max_bounce
-                                      && est_next >= (uint32_t)ctx->opt_sort_min_rays;
-                const rt_shade_launch::Launch shade = rt_shade_launch::launch(ctx->opt_shade_pass, n0, estimate_rays(ctx, n0, b), bin_next);
+                const bool bin_next = ctx->opt.kernel == RTGL_KERNEL_WAVEFRONT_MFMA_SOLO && ctx->opt.cull == 3 && sc.n_tri_visits > 0 && b + 1u < P.max_bounce
+                                      && est_next >= (uint32_t)ctx->opt.sort_min_rays;
+                const rt_shade_launch::Launch shade = rt_shade_launch::launch(ctx->opt.shade_pass, n0, estimate_rays(ctx, n0, b), bin_next);
                 if (bin_next) {
                     // two sets of bin counters take turns: the move (sort_place_kernel or sort_scatter_kernel) zeroes the one the next binned bounce will count in
                     const rt_bin_plan::Plan plan = {ctx->wb.sort_ob, ctx->wb.sort_cells.db, ctx->wb.sort_bits, ctx->wb.sort_cells.T, false};
@@ -1329,7 +1323,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     hipLaunchKernelGGL(sort_sums_kernel, dim3(rt_bin_plan::sums_grid(plan)), dim3(256), 0, ctx->stream, ctx->wb);
                     hipLaunchKernelGGL(sort_prefix_kernel, dim3(rt_bin_plan::sums_grid(plan)), dim3(256), 0, ctx->stream, ctx->wb);
                     // (the move: the rays' staging slots in key order, gathered by the next bounce's packet_cull_kernel; or, option 0, the rays themselves)
-                    if (ctx->opt_sort_move == 1) hipLaunchKernelGGL(sort_place_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
+                    if (ctx->opt.sort_move == 1) hipLaunchKernelGGL(sort_place_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     else hipLaunchKernelGGL(sort_scatter_kernel, dim3(std::max(1u, std::min((est_next + 255u) / 256u, 16384u))), dim3(256), 0, ctx->stream, ctx->wb, b + 1u);
                     HIPCHK(ctx, hipGetLastError());
                     ctx->sort_set ^= 1; ctx->sort_sets_clean = true;
@@ -1420,12 +1414,12 @@ extern "C" int rtgl_render_frame(rtgl_context *ctx)
     ctx->ad.active = false;                              // (adaptive sampling: an ordinary frame ends the session; one refused above does not)
     // frame batching: hold the frame back until the batch is full.  Only what the batched pipeline covers: one sample per frame, the
     // per-bounce pipeline (a scene with triangles), no per-frame read-outs (counters, RNG states)
-    const bool batchable = ctx->opt_frame_batch > 1 && ctx->params.samples == 1 && ctx->params.max_bounce > 0 && !ctx->opt_counters && !ctx->opt_rng_state
-                           && !ctx->opt_kernel_timing && !ctx->opt_aov && (ctx->n_tri_visits > 0 || ctx->tris_dirty || ctx->kernel_explicit) && ctx->opt_kernel != RTGL_KERNEL_MEGA;
+    const bool batchable = ctx->opt.frame_batch > 1 && ctx->params.samples == 1 && ctx->params.max_bounce > 0 && !ctx->opt.counters && !ctx->opt.rng_state
+                           && !ctx->opt.kernel_timing && !ctx->opt.aov && (ctx->n_tri_visits > 0 || ctx->tris_dirty || ctx->kernel_explicit) && ctx->opt.kernel != RTGL_KERNEL_MEGA;
     if (!ctx->pending.empty() && (!batchable || !batch_compatible(ctx->pending.front(), ctx->params))) { const int rc = flush_pending(ctx); if (rc) return rc; }
     if (batchable) {
         ctx->pending.push_back(ctx->params);
-        return (int)ctx->pending.size() >= ctx->opt_frame_batch ? flush_pending(ctx) : RTGL_OK;
+        return (int)ctx->pending.size() >= ctx->opt.frame_batch ? flush_pending(ctx) : RTGL_OK;
     }
     return render_batch(ctx, std::vector<FrameParams>(1, ctx->params));
 }
@@ -1452,8 +1446,8 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     }
     if (ctx->visits_dirty) { int rc = rebuild_sphere_visits(ctx); if (rc) return rc; }
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
-    if (ctx->opt_rng_state) RCCHK(buf_ensure(ctx, ctx->d_rng, local_px(ctx) * sizeof(uint4)));
-    if ((ctx->opt_aov & RTGL_AOV_IDS) && ctx->visit_ids_dirty) {
+    if (ctx->opt.rng_state) RCCHK(buf_ensure(ctx, ctx->d_rng, local_px(ctx) * sizeof(uint4)));
+    if ((ctx->opt.aov & RTGL_AOV_IDS) && ctx->visit_ids_dirty) {
         const size_t bytes = ctx->h_visit_tri.size() * sizeof(uint32_t);
         int rc = realloc_upload(ctx, ctx->d_visit_mesh, ctx->h_visit_mesh.data(), bytes);
         if (!rc) rc = realloc_upload(ctx, ctx->d_visit_tri, ctx->h_visit_tri.data(), bytes);
@@ -1470,17 +1464,17 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     im.disp_w = ctx->width / 8 * 8; im.disp_h = ctx->height / 8 * 8;
     im.local_rows = ctx->local_rows; im.rank = ctx->rank; im.world = ctx->world; im.strip_rows = ctx->strip_rows;
 
-    if (ctx->opt_counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
+    if (ctx->opt.counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
     // rows of the dispatch footprint held locally: a prefix of the local rows (strips are 8-row aligned)
     int local_disp_rows = 0;
     for (int lr = 0; lr < ctx->local_rows; ++lr) if (rtgl_local_row_to_global(ctx, lr) < im.disp_h) local_disp_rows = lr + 1;
     const uint32_t n0_frame = (uint32_t)im.disp_w * (uint32_t)local_disp_rows;
     if ((uint64_t)n0_frame * B > 0xFFFFFFF0ull || local_px(ctx) > (size_t)kBatchPixelMask) return fail(ctx, RTGL_ERR_INVALID, "frame_batch: the batch does not fit 32-bit ray slots");
     const uint32_t n0 = n0_frame * B;            // rays entering bounce 0: all frames of the batch
-    uint4 *rng_out = ctx->opt_rng_state ? ctx->d_rng : nullptr;
+    uint4 *rng_out = ctx->opt.rng_state ? ctx->d_rng : nullptr;
     // first-hit planes: frames are rendered one by one while they are on (B == 1); the running mean restarts with a reset frame
     AovView aov{};
-    if (ctx->opt_aov) {
+    if (ctx->opt.aov) {
         ctx->aov_n = (P.reset_flag || ctx->aov_restart) ? 1u : ctx->aov_n + 1u;
         ctx->aov_restart = false;
         aov.albedo = ctx->d_aov[0]; aov.normal = ctx->d_aov[1]; aov.position = ctx->d_aov[2]; aov.ids = ctx->d_aov_ids;
@@ -1488,7 +1482,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     }
     // a scene without triangles has no scan to split off: one megakernel launch per frame beats the per-bounce pipeline
     // (C1, 256x256 spheres: 1460 vs 1025 Mpaths/s) unless the caller asked for a specific variant
-    const int kernel = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt_kernel;
+    const int kernel = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt.kernel;
     const bool use_wavefront = kernel != RTGL_KERNEL_MEGA && P.max_bounce > 0;
     ctx->kernel_in_use = use_wavefront ? kernel : (int)RTGL_KERNEL_MEGA;
     if (B > 1 && !(use_wavefront && n0 > 0)) {          // (nothing to batch: a scene that lost its triangles meanwhile, an empty tile) one frame at a time
@@ -1505,7 +1499,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     ctx->last_batch_frames = B;
     HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     // option kernel_timing = N: every N-th frame since the last reset carries the event pairs (each pair costs ~3 us of gap)
-    ctx->timing_this_frame = ctx->opt_kernel_timing > 0 && (ctx->timing_frame_counter++ % (uint32_t)ctx->opt_kernel_timing) == 0u;
+    ctx->timing_this_frame = ctx->opt.kernel_timing > 0 && (ctx->timing_frame_counter++ % (uint32_t)ctx->opt.kernel_timing) == 0u;
     if (ctx->timing_this_frame) {
         if (ctx->kev_frame_start.size() >= 4096) { ctx->kev_used = 0; ctx->kev_frame_start.clear(); }   // bounded history
         ctx->kev_frame_start.push_back(ctx->kev_used);
@@ -1514,17 +1508,17 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if (n0 > 0 && !use_wavefront) {
         dim3 grid((im.disp_w + 31) / 32, (local_disp_rows + 7) / 8);
         kev_mark(ctx);
-        if (ctx->opt_aov) {
-            if (ctx->opt_counters) hipLaunchKernelGGL((pathtrace_mega_kernel<true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, aov);
+        if (ctx->opt.aov) {
+            if (ctx->opt.counters) hipLaunchKernelGGL((pathtrace_mega_kernel<true, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, aov);
             else hipLaunchKernelGGL((pathtrace_mega_kernel<false, true>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, aov);
-        } else if (ctx->opt_counters)
+        } else if (ctx->opt.counters)
             hipLaunchKernelGGL((pathtrace_mega_kernel<true, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, AovView{});
         else
             hipLaunchKernelGGL((pathtrace_mega_kernel<false, false>), grid, dim3(256), 0, ctx->stream, sc, P, im, rng_out, ctx->d_counters, AovView{});
         kev_mark(ctx);
         HIPCHK(ctx, hipGetLastError());
     } else if (n0 > 0) {
-        int rc = launch_wavefront(ctx, sc, frames, im, n0_frame, rng_out, ctx->opt_aov ? &aov : nullptr);
+        int rc = launch_wavefront(ctx, sc, frames, im, n0_frame, rng_out, ctx->opt.aov ? &aov : nullptr);
         if (rc) { ctx->keep0_valid = false; return rc; }      // (a frame that failed half way vouches for nothing it left behind)
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -1581,7 +1575,7 @@ extern "C" int rtgl_last_frame_timing(rtgl_context *ctx, rtgl_frame_timing *out)
     ENTER(ctx);
     if (!ctx->parts.empty()) { const int rc = rtgl_last_frame_timing(ctx->parts[0], out); return rc ? fail(ctx, rc, ctx->parts[0]->error) : RTGL_OK; }   // device 0's share
     if (!out || !ctx->timed) return fail(ctx, RTGL_ERR_STATE, "no frame has been rendered");
-    if (!ctx->opt_kernel_timing || ctx->kev_frame_start.empty()) return fail(ctx, RTGL_ERR_STATE, "option kernel_timing was not enabled before rendering");
+    if (!ctx->opt.kernel_timing || ctx->kev_frame_start.empty()) return fail(ctx, RTGL_ERR_STATE, "option kernel_timing was not enabled before rendering");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return sum_timing(ctx, ctx->kev_frame_start.size() - 1, ctx->kev_frame_start.size(), out);
 }
@@ -1591,7 +1585,7 @@ extern "C" int rtgl_accumulated_timing(rtgl_context *ctx, rtgl_frame_timing *out
     ENTER(ctx);
     if (!ctx->parts.empty()) { const int rc = rtgl_accumulated_timing(ctx->parts[0], out, frames_out); return rc ? fail(ctx, rc, ctx->parts[0]->error) : RTGL_OK; }
     if (!out) return fail(ctx, RTGL_ERR_INVALID, "out is NULL");
-    if (!ctx->opt_kernel_timing) return fail(ctx, RTGL_ERR_STATE, "option kernel_timing is not enabled");
+    if (!ctx->opt.kernel_timing) return fail(ctx, RTGL_ERR_STATE, "option kernel_timing is not enabled");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (frames_out) *frames_out = (uint32_t)ctx->kev_frame_start.size();
     return sum_timing(ctx, 0, ctx->kev_frame_start.size(), out);
@@ -1744,7 +1738,7 @@ extern "C" int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw)
         }
         return RTGL_OK;
     }
-    if (!ctx->opt_rng_state || !ctx->d_rng) return fail(ctx, RTGL_ERR_STATE, "option rng_state was not enabled before rendering");
+    if (!ctx->opt.rng_state || !ctx->d_rng) return fail(ctx, RTGL_ERR_STATE, "option rng_state was not enabled before rendering");
     return read_rows(ctx, xyzw, ctx->d_rng, 16);
 }
 
@@ -1771,7 +1765,7 @@ static int set_aov(rtgl_context *ctx, int mask)
         RCCHK(buf_release(ctx, ctx->d_visit_mesh, ctx->d_visit_tri));
         ctx->visit_ids_dirty = true;
     }
-    ctx->opt_aov = 0;
+    ctx->opt.aov = 0;
     const size_t bytes = local_px(ctx) * 16;
     for (int k = 0; k < 4; ++k) {
         if (!(mask & (1 << k))) continue;
@@ -1779,7 +1773,7 @@ static int set_aov(rtgl_context *ctx, int mask)
         HIPCHK(ctx, hipMemsetAsync(aov_plane(ctx, k), 0, bytes, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->opt_aov = mask; ctx->aov_restart = true;
+    ctx->opt.aov = mask; ctx->aov_restart = true;
     return RTGL_OK;
 }
 
@@ -1829,7 +1823,7 @@ extern "C" int rtgl_denoise_defaults(rtgl_denoise_params *out)
 // rtgl_temporal_accumulate; NULL: there is none yet
 static const float4 *denoise_input(const rtgl_context *ctx)
 {
-    if (ctx->opt_denoise_source == 0) return ctx->d_image;
+    if (ctx->opt.denoise_source == 0) return ctx->d_image;
     return ctx->has_temporal ? ctx->d_tm_hist[ctx->tm_cur] : nullptr;
 }
 
@@ -1859,7 +1853,7 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
                                          "render on a single-device context, or filter the gathered image yourself");
     const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_c = P.sigma_color > 0.0f, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
     const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
+    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: this context holds no pixels");
     const float4 *input = denoise_input(ctx);
@@ -1967,14 +1961,14 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
                                          "render on a single-device context, or filter the gathered image yourself");
     const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
     const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
+    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
     const float4 *input = denoise_input(ctx);
     if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
-    const bool tvar = ctx->opt_denoise_variance == 1;
+    const bool tvar = ctx->opt.denoise_variance == 1;
     if (tvar) {
-        if (ctx->opt_denoise_source != 1) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and \"denoise_source\" is not: the temporal variance is that of the history");
+        if (ctx->opt.denoise_source != 1) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and \"denoise_source\" is not: the temporal variance is that of the history");
         if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the latest rtgl_temporal_accumulate stored no moments (option \"temporal_moments\")");
         if (ctx->tm_moments != (demod ? 2 : 1))
             return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the stored moments are of the other kind: RTGL_DENOISE_DEMODULATE needs \"temporal_moments\" = 2, a call without it 1");
@@ -2085,13 +2079,13 @@ extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_p
         return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a tiled or multi-device context holds strips; a reprojected pixel may come from another strip, which is out of scope: "
                                          "render on a single-device context");
     const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const int moments = ctx->opt_temporal_moments;
+    const int moments = ctx->opt.temporal_moments;
     const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0) | (moments == 2 ? RTGL_AOV_ALBEDO : 0);
-    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0, albedo for \"temporal_moments\" = 2)");
+    if (need & ~ctx->opt.aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0, albedo for \"temporal_moments\" = 2)");
     if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: no frame has been rendered since the first-hit planes last restarted");
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: this context holds no pixels");
-    const bool with_normal = (ctx->opt_aov & RTGL_AOV_NORMAL) != 0;      // the normal plane is copied whenever it is on, tested or not
+    const bool with_normal = (ctx->opt.aov & RTGL_AOV_NORMAL) != 0;      // the normal plane is copied whenever it is on, tested or not
     for (int k = 0; k < 2; ++k) {
         RCCHK(buf_ensure(ctx, ctx->d_tm_hist[k], n * 16));
         RCCHK(buf_ensure(ctx, ctx->d_tm_position[k], n * 16));
@@ -2198,7 +2192,7 @@ extern "C" int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_pa
     if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no rtgl_temporal_accumulate call has succeeded on this context");
     const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
     const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0);
-    if (need & ~ctx->opt_aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a first-hit plane this call needs is not enabled (option \"aov\": position always, for the kind test; normal for sigma_normal > 0)");
+    if (need & ~ctx->opt.aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a first-hit plane this call needs is not enabled (option \"aov\": position always, for the kind test; normal for sigma_normal > 0)");
     if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no frame has been rendered since the first-hit planes last restarted");
     const size_t n = (size_t)ctx->local_rows * ctx->width;
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: this context holds no pixels");
@@ -2546,7 +2540,7 @@ static int masked_frame_refused(rtgl_context *ctx, const TileSession &s, const c
 {
     if (!s.active) return fail(ctx, RTGL_ERR_STATE, std::string(who) + no_session);
     if (!ctx->have_params) return fail(ctx, RTGL_ERR_STATE, no_params);
-    if (ctx->opt_aov || ctx->opt_rng_state) return fail(ctx, RTGL_ERR_STATE, std::string(who) + ": a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
+    if (ctx->opt.aov || ctx->opt.rng_state) return fail(ctx, RTGL_ERR_STATE, std::string(who) + ": a masked frame writes neither first-hit planes nor RNG states: options \"aov\" and \"rng_state\" must be 0");
     if (ctx->params.samples != 1u) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": a masked frame is one sample per pixel: samples must be 1");
     if (ctx->params.max_bounce == 0u) return fail(ctx, RTGL_ERR_INVALID, std::string(who) + ": max_bounce must be > 0");
     return RTGL_OK;
@@ -2591,12 +2585,12 @@ static int masked_frame(rtgl_context *ctx, float4 *samples, const uint32_t *list
     im.pixels = samples; im.width = ctx->width; im.height = ctx->height;
     im.disp_w = sh.fw; im.disp_h = sh.fh;
     im.local_rows = ctx->local_rows; im.rank = ctx->rank; im.world = ctx->world; im.strip_rows = ctx->strip_rows;
-    if (ctx->opt_counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
+    if (ctx->opt.counters) HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
     // the per-bounce pipeline whatever the scene: where an ordinary frame would take the megakernel, RTGL_KERNEL_WAVEFRONT
-    const int effective = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt_kernel;
-    const int saved_kernel = ctx->opt_kernel;
-    ctx->opt_kernel = effective == RTGL_KERNEL_MEGA ? (int)RTGL_KERNEL_WAVEFRONT : effective;
-    ctx->kernel_in_use = ctx->opt_kernel;
+    const int effective = (ctx->n_tri_visits == 0 && !ctx->kernel_explicit) ? (int)RTGL_KERNEL_MEGA : ctx->opt.kernel;
+    const int saved_kernel = ctx->opt.kernel;
+    ctx->opt.kernel = effective == RTGL_KERNEL_MEGA ? (int)RTGL_KERNEL_WAVEFRONT : effective;
+    ctx->kernel_in_use = ctx->opt.kernel;
     int rc = ensure_wave_buffers(ctx, n0, P.max_bounce, false);
     if (!rc) {
         ctx->wb.batch_rad = nullptr; ctx->wb.batch_px = 0;
@@ -2608,7 +2602,7 @@ static int masked_frame(rtgl_context *ctx, float4 *samples, const uint32_t *list
         rc = launch_wavefront(ctx, sc, frames, im, n0, nullptr, nullptr, list);
         if (rc) ctx->keep0_valid = false;                 // (as in render_batch: a frame that failed half way vouches for nothing it left behind)
     }
-    ctx->opt_kernel = saved_kernel;
+    ctx->opt.kernel = saved_kernel;
     return rc;
 }
 
@@ -3068,7 +3062,7 @@ extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_
         return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_denoise: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
                                          "render on a single-device context");
     if (const char *why = rt_bucket_guide_plan::refused(ctx->rb_active, ctx->rb_N, ctx->rb_K)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_denoise: ") + why);
-    if (const char *why = rt_bucket_guide_plan::planes_refused(rt_bucket_guide_plan::planes_needed(P), (uint32_t)ctx->opt_aov, ctx->aov_restart, ctx->aov_n))
+    if (const char *why = rt_bucket_guide_plan::planes_refused(rt_bucket_guide_plan::planes_needed(P), (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n))
         return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_denoise: ") + why);
     const size_t n = rt_bucket_guide_plan::pixels(ctx->local_rows, ctx->width);
     if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_denoise: this context holds no pixels");
@@ -3105,86 +3099,24 @@ extern "C" int rtgl_robust_denoise(rtgl_context *ctx, const rtgl_robust_denoise_
     return launch_guided_passes(ctx, a, P.passes, demod);
 }
 
+// Keys, ranges and messages: the table of rt_options.hpp.  Here: what an option means to the rest of the context
 extern "C" int rtgl_set_option(rtgl_context *ctx, const char *key, int value)
 {
+    using rt_options::Options;
     ENTER(ctx);
     FANOUT(ctx, rtgl_set_option(part, key, value));
     if (!key) return fail(ctx, RTGL_ERR_INVALID, "key is NULL");
-    if (!strcmp(key, "kernel")) {
-        if (value == RTGL_KERNEL_REMOVED_3)
-            return fail(ctx, RTGL_ERR_INVALID, "kernel variant 3 (three waves per SIMD) was removed: it was not deterministic (DESIGN.md section 5); use 4");
-        if (value < RTGL_KERNEL_MEGA || value > RTGL_KERNEL_WAVEFRONT_MFMA_SOLO)
-            return fail(ctx, RTGL_ERR_INVALID, "unknown kernel variant");
-        ctx->opt_kernel = value; ctx->kernel_explicit = true;
-    } else if (!strcmp(key, "wf_rays")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8) return fail(ctx, RTGL_ERR_INVALID, "wf_rays must be 1, 2, 4 or 8");
-        ctx->opt_wf_rays = value;
-    } else if (!strcmp(key, "wf_chunk")) {
-        if (value < kBoundGroup || value % kBoundGroup || (uint32_t)value > kMaxChunk) return fail(ctx, RTGL_ERR_INVALID, "wf_chunk must be a multiple of 64 in [64, 4096]");
-        ctx->opt_wf_chunk = value;
-    } else if (!strcmp(key, "debug_skip_exact")) {      // timing diagnostics only: the image is wrong
-        if (value < 0 || value > 3) return fail(ctx, RTGL_ERR_INVALID, "debug_skip_exact must be 0, 1, 2 or 3");
-        ctx->opt_debug_skip_exact = value;               // 1: survivors are dropped instead of tested; 2: broad phase rejects everything; 3: every segment through the list loop (image right)
-    } else if (!strcmp(key, "mf_chunk_quads")) {
-        if (value < 1 || (uint32_t)value > kMfMaxChunkQuads) return fail(ctx, RTGL_ERR_INVALID, "mf_chunk_quads must be in [1, 32]");
-        ctx->opt_mf_chunk_quads = value;
-    } else if (!strcmp(key, "scan_waves")) {
-        if (value < 0 || value > 2) return fail(ctx, RTGL_ERR_INVALID, "scan_waves (waves per SIMD of the kernel-4 scan) must be 0 (default: two), 1 or 2");
-        ctx->opt_scan_waves = value;
-    } else if (!strcmp(key, "scan_dynamic")) {
-        if (value < 0 || value > 4) return fail(ctx, RTGL_ERR_INVALID, "scan_dynamic must be 0 (chosen by the mesh), 1 (static turns), 2 (dynamic claims), 3 (planned: equal-cost intervals) or 4 (hybrid: turns + a claimed tail)");
-        ctx->opt_scan_dynamic = value;
-    } else if (!strcmp(key, "narrow_fused")) {
-        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "narrow_fused must be 0 (narrow_phase_kernel tests the scan's survivors) or 1 (every scan wave tests its own at its end)");
-        ctx->opt_narrow_fused = value;
-    } else if (!strcmp(key, "camera_lean")) {
-        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "camera_lean must be 0 (camera rays travel through queue 0 in full) or 1 (shade rebuilds them while the camera's keep bits are reused)");
-        ctx->opt_camera_lean = value;
-    } else if (!strcmp(key, "shade_pass")) {
-        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "shade_pass must be 0 (every shade launch in grid-stride passes) or 1 (one pass, a block per 256 slots of queue 0, unless the queue is expected to be all but empty)");
-        ctx->opt_shade_pass = value;
-    } else if (!strcmp(key, "frame_batch")) {
-        if (value < 1 || value > (int)kBatchMax) return fail(ctx, RTGL_ERR_INVALID, "frame_batch (consecutive frames traced in one set of launches) must be 1..16");
-        ctx->opt_frame_batch = value;
-    } else if (!strcmp(key, "cull")) {
-        if (value < 0 || value > 3) return fail(ctx, RTGL_ERR_INVALID, "cull must be 0 (off), 1 (camera rays), 2 (every bounce, queues as they come) or 3 (camera rays + binned bounces)");
-        ctx->opt_cull = value;
-    } else if (!strcmp(key, "sort_min_rays")) {
-        if (value < 0) return fail(ctx, RTGL_ERR_INVALID, "sort_min_rays (a bounce's queue is binned when at least this many rays are expected) must be >= 0");
-        ctx->opt_sort_min_rays = value;
-    } else if (!strcmp(key, "mf_group_quads")) {
-        if (value < 1 || value > (int)kMfMaxGroupQuads || (value & (value - 1))) return fail(ctx, RTGL_ERR_INVALID, "mf_group_quads must be a power of two in [1, 64]");
-        if (value != (int)ctx->mf_group_quads) ctx->tris_dirty = true;                         // local origins and A tiles are per group
-        ctx->opt_mf_group_quads = value; ctx->group_explicit = true;
-    } else if (!strcmp(key, "wf_packed")) {
-        ctx->opt_wf_packed = value != 0;
-    } else if (!strcmp(key, "wf_early")) {
-        if (value < 0) return fail(ctx, RTGL_ERR_INVALID, "wf_early is the number of leading bounces with the wave-level edge short circuit (>= 0)");
-        ctx->opt_wf_early = value;
-    } else if (!strcmp(key, "wf_mode")) {
-        if (value != kScalar && value != kLds) return fail(ctx, RTGL_ERR_INVALID, "wf_mode must be 0 (scalar) or 1 (lds)");
-        ctx->opt_wf_mode = value;
-    } else if (!strcmp(key, "aov")) {
-        if (value < 0 || value > RTGL_AOV_ALL) return fail(ctx, RTGL_ERR_INVALID, "aov must be a mask of RTGL_AOV_ALBEDO | RTGL_AOV_NORMAL | RTGL_AOV_POSITION | RTGL_AOV_IDS (0: off)");
-        const int rc = set_aov(ctx, value);
-        if (rc) return rc;
-    } else if (!strcmp(key, "denoise_source")) {
-        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "denoise_source must be 0 (the accumulation image) or 1 (the latest history buffer of rtgl_temporal_accumulate)");
-        ctx->opt_denoise_source = value;
-    } else if (!strcmp(key, "temporal_moments")) {
-        if (value < 0 || value > 2) return fail(ctx, RTGL_ERR_INVALID, "temporal_moments must be 0 (off), 1 (luminance moments of the radiance) or 2 (of the radiance divided by the albedo)");
-        if (value != ctx->opt_temporal_moments) ctx->tm_valid = false;       // moments and colour history always have the same age
-        ctx->opt_temporal_moments = value;
-    } else if (!strcmp(key, "denoise_variance")) {
-        if (value != 0 && value != 1) return fail(ctx, RTGL_ERR_INVALID, "denoise_variance must be 0 (the spatial estimate) or 1 (the temporal moments where the history is long enough)");
-        ctx->opt_denoise_variance = value;
-    } else if (!strcmp(key, "rng_state")) ctx->opt_rng_state = value != 0;
-    else if (!strcmp(key, "counters")) ctx->opt_counters = value != 0;
-    else if (!strcmp(key, "kernel_timing")) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (value < 0) return fail(ctx, RTGL_ERR_INVALID, "kernel_timing must be 0 (off) or the sampling period in frames");
-        ctx->opt_kernel_timing = value; ctx->kev_used = 0; ctx->kev_frame_start.clear(); ctx->timing_frame_counter = 0; ctx->timing_this_frame = false;
-    } else return fail(ctx, RTGL_ERR_INVALID, std::string("unknown option ") + key);
+    const rt_options::Row *row = rt_options::find(key);
+    if (!row || !(row->flags & rt_options::kSet)) return fail(ctx, RTGL_ERR_INVALID, std::string("unknown option ") + key);
+    if (row->field == &Options::kernel_timing) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (before the value is judged)
+    const int before = ctx->opt.*row->field;
+    const char *refused = row->field == &Options::aov ? rt_options::refusal(*row, value) : rt_options::set(ctx->opt, *row, value);
+    if (refused) return fail(ctx, RTGL_ERR_INVALID, refused);
+    if (row->field == &Options::aov) return set_aov(ctx, value);      // stores the mask itself, once the planes are there
+    if (row->field == &Options::kernel) ctx->kernel_explicit = true;
+    else if (row->field == &Options::mf_group_quads) { ctx->group_explicit = true; if (value != (int)ctx->mf_group_quads) ctx->tris_dirty = true; }      // local origins and A tiles are per group
+    else if (row->field == &Options::temporal_moments && value != before) ctx->tm_valid = false;       // moments and colour history always have the same age
+    else if (row->field == &Options::kernel_timing) { ctx->kev_used = 0; ctx->kev_frame_start.clear(); ctx->timing_frame_counter = 0; ctx->timing_this_frame = false; }
     return RTGL_OK;
 }
 
@@ -3193,35 +3125,19 @@ extern "C" int rtgl_get_option(rtgl_context *ctx, const char *key, int *value)
     ENTER(ctx);
     if (!key || !value) return fail(ctx, RTGL_ERR_INVALID, "NULL argument");
     if (!ctx->parts.empty()) { const int rc = rtgl_get_option(ctx->parts[0], key, value); return rc ? fail(ctx, rc, ctx->parts[0]->error) : RTGL_OK; }
-    if (!strcmp(key, "kernel")) *value = ctx->opt_kernel;
-    else if (!strcmp(key, "kernel_in_use")) *value = ctx->kernel_in_use;
-    else if (!strcmp(key, "wf_rays")) *value = ctx->opt_wf_rays;
-    else if (!strcmp(key, "wf_mode")) *value = ctx->opt_wf_mode;
-    else if (!strcmp(key, "wf_chunk")) *value = ctx->opt_wf_chunk;
-    else if (!strcmp(key, "wf_early")) *value = ctx->opt_wf_early;
-    else if (!strcmp(key, "wf_packed")) *value = ctx->opt_wf_packed;
-    else if (!strcmp(key, "mf_sets")) *value = kSoloSets;
-    else if (!strcmp(key, "mf_chunk_quads")) *value = ctx->opt_mf_chunk_quads;
-    else if (!strcmp(key, "mf_group_quads")) *value = (int)ctx->mf_group_quads;
-    else if (!strcmp(key, "cull")) *value = ctx->opt_cull;
-    else if (!strcmp(key, "sort_min_rays")) *value = ctx->opt_sort_min_rays;
-    else if (!strcmp(key, "scan_waves")) *value = ctx->opt_scan_waves;
-    else if (!strcmp(key, "scan_dynamic")) *value = ctx->opt_scan_dynamic;
-    else if (!strcmp(key, "narrow_fused")) *value = ctx->opt_narrow_fused;
-    else if (!strcmp(key, "frame_batch")) *value = ctx->opt_frame_batch;
-    else if (!strcmp(key, "camera_lean")) *value = ctx->opt_camera_lean;
-    else if (!strcmp(key, "camera_lean_frames")) *value = (int)ctx->camera_lean_frames;      // read-only: frames of this context that took the lean camera bounce
-    else if (!strcmp(key, "shade_pass")) *value = ctx->opt_shade_pass;
-    else if (!strcmp(key, "shade_pass_launches")) *value = (int)ctx->shade_pass_launches;      // read-only: launches of this context that took the one-pass shade_kernel
-    else if (!strcmp(key, "rng_state")) *value = ctx->opt_rng_state;
-    else if (!strcmp(key, "aov")) *value = ctx->opt_aov;
-    else if (!strcmp(key, "denoise_source")) *value = ctx->opt_denoise_source;
-    else if (!strcmp(key, "temporal_moments")) *value = ctx->opt_temporal_moments;
-    else if (!strcmp(key, "denoise_variance")) *value = ctx->opt_denoise_variance;
-    else if (!strcmp(key, "counters")) *value = ctx->opt_counters;
-    else if (!strcmp(key, "kernel_timing")) *value = ctx->opt_kernel_timing;
-    else if (!strcmp(key, "cand_region_pairs")) *value = (int)ctx->cand_region_pairs;      // kernel 4: current capacity of one wave's candidate region
-    else if (!strcmp(key, "device_mbytes")) *value = (int)((ctx->buffers.total_bytes() + (1u << 20) - 1) >> 20);      // device memory held by this context: the ledger's sum (MiB, rounded up)
-    else return fail(ctx, RTGL_ERR_INVALID, std::string("unknown option ") + key);
+    // read-only keys: what the context did or holds, not what it was asked for
+    const struct { const char *key; int value; } derived[] = {
+        {"kernel_in_use", ctx->kernel_in_use},                                  // the variant the last frame ran
+        {"mf_sets", kSoloSets},
+        {"mf_group_quads", (int)ctx->mf_group_quads},                           // the value in use, not the option
+        {"camera_lean_frames", (int)ctx->camera_lean_frames},                   // frames of this context that took the lean camera bounce
+        {"shade_pass_launches", (int)ctx->shade_pass_launches},                 // launches of this context that took the one-pass shade_kernel
+        {"cand_region_pairs", (int)ctx->cand_region_pairs},                     // kernel 4: current capacity of one wave's candidate region
+        {"device_mbytes", (int)((ctx->buffers.total_bytes() + (1u << 20) - 1) >> 20)},      // device memory held by this context: the ledger's sum (MiB, rounded up)
+    };
+    for (const auto &d : derived) if (!strcmp(d.key, key)) { *value = d.value; return RTGL_OK; }
+    const rt_options::Row *row = rt_options::find(key);
+    if (!row || !(row->flags & rt_options::kGet)) return fail(ctx, RTGL_ERR_INVALID, std::string("unknown option ") + key);
+    *value = ctx->opt.*row->field;
     return RTGL_OK;
 }

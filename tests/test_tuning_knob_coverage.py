@@ -1,6 +1,7 @@
 """Every environment variable the library reads is accounted for: a tuning variable must be named by tests/test_gpu_tuning_knobs.py, a
 switch that another module covers is listed here with that module, and so is the environment's spelling of an option that the suite sets
-through rtgl_set_option.  A new getenv("RTGL_AMD_...") in rtgl_amd.hip fails this test until it is put in one of the lists -- or tested."""
+through rtgl_set_option.  A new getenv("RTGL_AMD_...") in rtgl_amd.hip, or a new environment name in the option table (rt_options.hpp),
+fails this test until it is put in one of the lists -- or tested."""
 import os
 import re
 
@@ -41,8 +42,13 @@ def test_every_variable_the_library_reads_is_tested_or_listed():
     for name in os.listdir(os.path.join(ROOT, "raytracer.glsl_amd", "csrc")):
         if name.endswith(".hpp"):
             assert "getenv(" not in read(os.path.join(ROOT, "raytracer.glsl_amd", "csrc", name)), f"{name} reads the environment"
+    # ... so the spellings of the options are names in the option table (rt_options.hpp), which rtgl_amd.hip reads through its own getter
+    spellings = set(re.findall(r'"(RTGL_[A-Z_]+)"', read(os.path.join(ROOT, "raytracer.glsl_amd", "csrc", "rt_options.hpp"))))
+    assert spellings == set(OPTION_SPELLINGS) | {"RTGL_AMD_SORT_MOVE", "RTGL_AMD_FRAME_BATCH"} and "rt_options::read_environment(ctx->opt," in code
     names = set(re.findall(r'getenv\("(RTGL_[A-Z_]+)"\)', code))
-    assert len(names) >= 20
+    assert not names & spellings
+    names |= spellings
+    assert len(names) == 24      # what the getenv calls of rtgl_amd.hip alone named before the table
     knobs = read(os.path.join(TESTS, "test_gpu_tuning_knobs.py"))
     listed = set(COVERED_ELSEWHERE) | set(OPTION_SPELLINGS) | NOT_A_KERNEL_PATH | set(DEBUG)
     missing = sorted(n for n in names - listed if n not in knobs)
