@@ -35,7 +35,8 @@ typedef enum rtgl_status {
 } rtgl_status;
 /* Order of the checks: a call that is wrong in its arguments AND in the state of the context reports the arguments (RTGL_ERR_INVALID): every
  * entry point checks its parameters before it looks at the context.  Two checks need the context and come after its state: n < 1 of
- * rtgl_error_estimate (F_n is known only once a frame has been rendered) and samples / max_bounce of rtgl_adaptive_frame.  A post-process
+ * rtgl_error_estimate (F_n is known only once a frame has been rendered) and samples / max_bounce of rtgl_adaptive_frame and of
+ * rtgl_robust_adaptive_frame (a masked frame of either kind without a session or with "aov" on is RTGL_ERR_STATE whatever `samples` is).  A post-process
  * call (rtgl_denoise and everything below it in this header) that is refused changes nothing: no buffer, no option, no session, no snapshot. */
 
 /* The 17 uniforms of reference shaders/raytracer.glsl:62-81, set per frame by

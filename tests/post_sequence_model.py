@@ -3,9 +3,10 @@ tests/post_sequence_inputs.py.  A helper, not a test; numpy, no device.
 
 PostModel(h, w) composes the mirrors the suite already has -- denoise_mirror, denoise_guided_mirror, temporal_mirror,
 temporal_moments_mirror, temporal_clip_mirror, tonemap_mirror.Tonemapper, error_mirror.Estimator, adaptive_mirror.Session,
-robust_mirror.Session, robust_error_mirror.estimate, robust_denoise_mirror.robust_denoise -- and adds no arithmetic of its own: what it
-adds is WHICH buffer a call reads, which state a call drops, and when a call is refused, each taken from a sentence of the header (quoted
-where it is used).  It never reads rtgl_amd.hip and is never fed anything the context under test produced.
+robust_mirror.Session, robust_error_mirror.estimate, robust_denoise_mirror.robust_denoise, robust_adaptive_mirror.Session -- and adds no
+arithmetic of its own: what it adds is WHICH buffer a call reads, which state a call drops, and when a call is refused, each taken from
+a sentence of the header (quoted where it is used).  It never reads rtgl_amd.hip and is never fed anything the context under test
+produced.
 
   status_of(step)          the status the header gives the step in the current state: 0, -1 (RTGL_ERR_INVALID) or -4 (RTGL_ERR_STATE).
                            A bad argument is reported before the state (header, "rtgl_status").
@@ -13,10 +14,15 @@ where it is used).  It never reads rtgl_amd.hip and is never fed anything the co
                            a frame step is rtgl_set_frame_params, which succeeds, and then the frame call, so the CURRENT camera of
                            rtgl_temporal_accumulate is that of the latest frame step, refused or not.
                            traced: for an accepted "render" dict(image=the image after the frame, planes={bit: plane after the frame});
-                           for an accepted "adaptive_frame" dict(sample=the full one-frame image of the frame's uniforms).
+                           for an accepted "adaptive_frame" or "robust_adaptive_frame" dict(sample=the full one-frame image of the
+                           frame's uniforms).
   readouts()               every read-out of the header, by name: the expected contents, or REFUSED where the header says the read-out
                            returns RTGL_ERR_STATE.  Arrays are never modified in place once handed out.
   image                    the accumulation image as it must be now: what a plain twin has to hold before it traces the next frame.
+
+PostModel(h, w, defect=name) is the model with ONE rule of the host state got wrong, a name of DEFECTS: the mistakes a host body shared by
+the adaptive and the robust adaptive session makes plausible.  tests/test_post_sequence_inputs.py walks each over the default sequences:
+where the walk differs from the true model's, a library with that mistake would differ from the model on the device.
 """
 import numpy as np
 
@@ -24,6 +30,7 @@ import adaptive_mirror as am
 import denoise_guided_mirror as dgm
 import denoise_mirror as dm
 import error_mirror as em
+import robust_adaptive_mirror as ram
 import robust_denoise_mirror as rdm
 import robust_error_mirror as rem
 import robust_mirror as rm
@@ -38,7 +45,20 @@ REFUSED = "refused"
 A, N, P, IDS = 1, 2, 4, 8
 BITS = (A, N, P, IDS)
 READOUTS = ("image", "planes", "denoised", "variance", "history", "moments", "display", "exposure", "histogram", "error_summary", "error_tiles", "adaptive_tiles",
-            "adaptive_mask", "robust_buckets", "robust_output", "robust_frames", "robust_error_summary", "robust_error_tiles")
+            "adaptive_mask", "robust_buckets", "robust_output", "robust_frames", "robust_error_summary", "robust_error_tiles", "robust_adaptive_buckets",
+            "robust_adaptive_output", "robust_adaptive_tiles", "robust_adaptive_mask")
+FRAMES = ("render", "adaptive_frame", "robust_adaptive_frame")         # the steps that begin with rtgl_set_frame_params
+UPDATES = ("adaptive_update", "robust_adaptive_update")                # the steps that return a summary
+# one wrong rule each (see the module's text); every name is looked up where the rule it breaks is written
+DEFECTS = ("render ends the robust adaptive session", "a replaced image ends the robust adaptive session", "adaptive_begin ends the robust adaptive session",
+           "adaptive_set_mask also sets the robust adaptive mask", "adaptive_update also sets the robust adaptive mask",
+           "robust_adaptive_set_mask also sets the adaptive mask", "robust_adaptive_update also sets the adaptive mask",
+           "robust_adaptive_frame merges into the image", "robust_adaptive_frame drops the error snapshot",
+           "robust_adaptive_begin clears the image and restarts the planes", "the resolve into the image leaves the adaptive session open",
+           "the resolve into the image keeps the error snapshot", "robust_adaptive_accumulate folds the sample buffer", "a second begin keeps n",
+           "a second begin keeps the mask", "a second begin leaves the output readable", "robust_adaptive_frame is accepted with aov on",
+           "robust_denoise serves a robust adaptive session", "robust_error_estimate serves a robust adaptive session",
+           "robust_adaptive_end ends the robust session")
 
 
 def _finite(*values):
@@ -46,10 +66,11 @@ def _finite(*values):
 
 
 class PostModel:
-    def __init__(self, h, w, tiled=False):
+    def __init__(self, h, w, tiled=False, defect=None):
         """tiled: a context of rtgl_create_tiled with more than one rank, holding h x w LOCAL rows: every post-process call but the
-        robust session's begin, accumulate, resolve and end is RTGL_ERR_STATE there"""
-        self.h, self.w, self.tiled = h, w, tiled
+        robust session's begin, accumulate, resolve and end is RTGL_ERR_STATE there.  defect: None, or the one rule of DEFECTS to get wrong"""
+        assert defect is None or defect in DEFECTS, defect
+        self.h, self.w, self.tiled, self.defect = h, w, tiled, defect
         self.image = np.zeros((h, w, 4), f32)                          # "zero-initialised"
         self.aov, self.planes = 0, {}
         self.restarted = True                                          # no frame since the planes last restarted (none yet)
@@ -62,7 +83,9 @@ class PostModel:
         self.est, self.error = em.Estimator(), None
         self.session, self.ad_records = None, None                     # an open adaptive session; the records of the latest one
         self.robust, self.robust_output, self.robust_error = None, None, None
-        self.summary = None                                            # what the latest accepted adaptive_update returned
+        self.ra, self.ra_output = None, None                           # an open robust adaptive session; its output plane once resolved into
+        self.ra_sample = None                                          # (the session's sample buffer: only a defect reads it)
+        self.summary = None                                            # what the latest accepted adaptive_update or robust_adaptive_update returned
 
     # -------------------------------------------------------------------------------------------- refusals
     def _planes_state(self, need, always=False):
@@ -148,7 +171,9 @@ class PostModel:
     def _status_adaptive_frame(self, a):
         if self.tiled or self.session is None or self.aov:            # "no session"; "option "aov" ... non-zero"
             return STATE
-        return OK
+        # "at rtgl_adaptive_frame: samples != 1 ... in the frame parameters"; "Two checks need the context and come after its state: ...
+        # samples / max_bounce of rtgl_adaptive_frame and of rtgl_robust_adaptive_frame"
+        return INVALID if a.get("samples", 1) != 1 else OK
 
     def _status_adaptive_update(self, a):
         return STATE if self.tiled or self.session is None else OK
@@ -172,27 +197,60 @@ class PostModel:
     def _status_robust_error_estimate(self, a):
         if not rem.valid_params(a["threshold"], a["floor"], a["gain"], 950):
             return INVALID
+        if self._served_by_defect("robust_error_estimate serves a robust adaptive session"):
+            return OK
+        # "rtgl_robust_denoise and rtgl_robust_error_estimate serve the plain robust session only"
         if self.tiled or rem.refused(self.robust is not None, self.robust.N if self.robust else 0, self.robust.K if self.robust else 0):
             return STATE
         return OK
+
+    def _served_by_defect(self, name):
+        """(a defect) no plain session, and a robust adaptive one in which some tile holds K samples"""
+        return self.defect == name and not self.tiled and self.robust is None and self.ra is not None and int(self.ra.n.max()) >= self.ra.K
 
     def _status_robust_denoise(self, a):
         # "RTGL_ERR_INVALID: ... passes > 8, a non-finite sigma, sigma_lum <= 0, gain NaN, negative or infinite"
         if not rdm.valid_params(a["passes"], a["sigma_lum"], a["sigma_normal"], a["sigma_position"], a["gain"]):
             return INVALID
         # "RTGL_ERR_STATE: no session; N < K (an empty bucket has no luminance); a tiled or multi-device context; ..."
-        if self.tiled or self.robust is None or self.robust.N < self.robust.K:
+        if self.tiled or ((self.robust is None or self.robust.N < self.robust.K) and not self._served_by_defect("robust_denoise serves a robust adaptive session")):
             return STATE
         # "... a plane the parameters need is not enabled; a plane is needed and no frame has been rendered since the planes last
         # restarted (the conditions of rtgl_denoise_guided)": with no plane needed the restart does not refuse
         return self._planes_state(self._denoiser_planes(a))
+
+    def _status_robust_adaptive_begin(self, a):
+        # "RTGL_ERR_INVALID: ... buckets not 4, 8 or 16; threshold or floor not finite or not > 0; gain NaN, negative or infinite;
+        # min_samples < K; max_samples < min_samples or > 16777216"
+        if not ram.valid_params(a["buckets"], a["threshold"], a["floor"], a["gain"], a["min_samples"], a["max_samples"]):
+            return INVALID
+        return STATE if self.tiled else OK                             # "a tiled or multi-device context"
+
+    def _status_robust_adaptive_frame(self, a):
+        # "RTGL_ERR_STATE: no session (every call but begin and defaults); a tiled or multi-device context; ... rtgl_robust_adaptive_frame
+        # ... with option "aov" ... non-zero"
+        if self.tiled or self.ra is None or (self.aov and self.defect != "robust_adaptive_frame is accepted with aov on"):
+            return STATE
+        return INVALID if a.get("samples", 1) != 1 else OK             # "at rtgl_robust_adaptive_frame: samples != 1": after the state, see above
+
+    def _status_robust_adaptive_update(self, a):
+        return STATE if self.tiled or self.ra is None else OK
+
+    _status_robust_adaptive_accumulate = _status_robust_adaptive_set_mask = _status_robust_adaptive_end = _status_robust_adaptive_update
+
+    def _status_robust_adaptive_resolve(self, a):
+        if not rm.valid_resolve_params(a["gain"], a["dest"]):          # "dest > 1", and the gain of rtgl_robust_resolve_params
+            return INVALID
+        return STATE if self.tiled or self.ra is None else OK
 
     # -------------------------------------------------------------------------------------------- events several calls share
     def _image_replaced(self):
         """what rtgl_write_image_f32 does on the host, and with it rtgl_clear_image, rtgl_bind_device_image and rtgl_robust_resolve into
         the image: "an adaptive session ends, the snapshot of rtgl_error_estimate is dropped" """
         self.est.drop()
-        self.session = None
+        self.session = None                                            # "The events that end an adaptive session do not end this one"
+        if self.defect == "a replaced image ends the robust adaptive session":
+            self._do_robust_adaptive_end(None, None)                   # (a defect)
 
     def _source(self):
         """what the denoisers filter: "0 (default) ... the image; 1 they take the latest history buffer wherever they take the image" """
@@ -205,7 +263,7 @@ class PostModel:
     def step(self, step, traced=None, params=None):
         """params: the uniforms of a frame step (rtgl_set_frame_params, which comes first and succeeds whatever becomes of the frame)"""
         a = step.args
-        if step.kind in ("render", "adaptive_frame"):
+        if step.kind in FRAMES:
             self.params = params
         status = self.status_of(step)
         if status == OK:
@@ -214,6 +272,8 @@ class PostModel:
 
     def _do_render(self, a, traced):
         self.session = None                                            # "rtgl_render_frame ... END the session"
+        if self.defect == "render ends the robust adaptive session":
+            self._do_robust_adaptive_end(a, traced)
         self.est.frame(a["frames"], a["reset_flag"])                   # "any rendered frame with reset_flag != 0" drops the snapshot; F_n
         self.image = traced["image"]
         self.planes = {bit: traced["planes"][bit] for bit in BITS if self.aov & bit}
@@ -295,6 +355,8 @@ class PostModel:
         self._do_clear_image(a, traced)
         self.session = am.Session(self.h, self.w, threshold=a["threshold"], min_samples=a["min_samples"], max_samples=a["max_samples"])
         self.ad_records = self.session.records
+        if self.defect == "adaptive_begin ends the robust adaptive session":
+            self._do_robust_adaptive_end(a, traced)
 
     def _do_adaptive_frame(self, a, traced):
         self.est.drop()                                                # "A masked frame drops the snapshot of rtgl_error_estimate"
@@ -306,9 +368,13 @@ class PostModel:
         self.session.image = self.image
         self.summary = self.session.update()
         self.ad_records = self.session.records
+        if self.defect == "adaptive_update also sets the robust adaptive mask" and self.ra is not None:
+            self.ra.mask = self.session.mask
 
     def _do_adaptive_set_mask(self, a, traced):
         self.session.set_mask(a["tiles"])
+        if self.defect == "adaptive_set_mask also sets the robust adaptive mask" and self.ra is not None:
+            self.ra.set_mask(a["tiles"])
 
     def _do_robust_begin(self, a, traced):
         self.robust, self.robust_output, self.robust_error = rm.Session(self.h, self.w, a["buckets"]), None, None
@@ -325,10 +391,78 @@ class PostModel:
         else:
             self.robust_output = out
 
+    # a robust adaptive session.  "The session is independent of an adaptive session and of a robust session: either may be open beside
+    # it, and neither is read or written.  The events that end an adaptive session do not end this one: only rtgl_robust_adaptive_end does."
+    def _do_robust_adaptive_begin(self, a, traced):
+        # "a second begin restarts the session ..., zeroes the buckets, n, m and the records and sets active every tile that holds a
+        # footprint pixel.  It does not touch the image."
+        old, output = self.ra, self.ra_output
+        self.ra = ram.Session(self.h, self.w, **a)
+        self.ra_output, self.ra_sample = None, np.zeros((self.h, self.w, 4), f32)      # "before a resolve with dest BUFFER": since this begin
+        if old is not None:
+            if self.defect == "a second begin keeps n":
+                self.ra.n = old.n
+            if self.defect == "a second begin keeps the mask":
+                self.ra.mask = old.mask
+            if self.defect == "a second begin leaves the output readable":
+                self.ra_output = output
+        if self.defect == "robust_adaptive_begin clears the image and restarts the planes":
+            self._do_clear_image(a, traced)
+
+    def _do_robust_adaptive_frame(self, a, traced):
+        # "into the session's sample buffer, and then runs the FOLD with that buffer as the source.  It writes neither the image nor
+        # anything of rtgl_error_estimate."
+        on = am.active_pixels(self.h, self.w, self.ra.mask)[..., None]
+        self.ra_sample = np.where(on, traced["sample"], self.ra_sample)
+        if self.defect == "robust_adaptive_frame merges into the image":
+            self.image = am.merge(self.image, traced["sample"], self.ra.n, self.ra.mask)[0]
+        if self.defect == "robust_adaptive_frame drops the error snapshot":
+            self.est.drop()
+        self.ra.fold(traced["sample"])
+
+    def _do_robust_adaptive_accumulate(self, a, traced):
+        # "runs the fold with the accumulation image AS IT STANDS as the source"
+        self.ra.fold(self.ra_sample if self.defect == "robust_adaptive_accumulate folds the sample buffer" else self.image)
+
+    def _do_robust_adaptive_update(self, a, traced):
+        self.summary = self.ra.update()
+        if self.defect == "robust_adaptive_update also sets the adaptive mask" and self.session is not None:
+            self.session.mask = self.ra.mask
+
+    def _do_robust_adaptive_set_mask(self, a, traced):
+        self.ra.set_mask(a["tiles"])
+        if self.defect == "robust_adaptive_set_mask also sets the adaptive mask" and self.session is not None:
+            self.session.set_mask(a["tiles"])
+
+    def _do_robust_adaptive_resolve(self, a, traced):
+        out = self.ra.resolve(a["gain"], a["dest"])
+        if a["dest"] == ram.DEST_BUFFER:                               # "in the session's output plane ...; nothing else changes"
+            self.ra_output = out
+            return
+        # "stores all four components in the accumulation image and does on the host exactly what rtgl_robust_resolve with dest IMAGE
+        # does: an adaptive session ends, the snapshot of rtgl_error_estimate is dropped.  The session goes on after either."
+        self.image = out
+        session = self.session
+        keep = self.defect == "the resolve into the image keeps the error snapshot"
+        if keep:
+            saved = dict(vars(self.est))
+        self._image_replaced()
+        if keep:
+            vars(self.est).update(saved)
+        if self.defect == "the resolve into the image leaves the adaptive session open":
+            self.session = session
+
+    def _do_robust_adaptive_end(self, a, traced):
+        self.ra = self.ra_output = self.ra_sample = None
+        if self.defect == "robust_adaptive_end ends the robust session":
+            self.robust = self.robust_output = self.robust_error = None
+
     def _do_robust_end(self, a, traced):
         self.robust = self.robust_output = self.robust_error = None
 
     def _do_robust_error_estimate(self, a, traced):
+        if self.defect == "robust_error_estimate serves a robust adaptive session" and self.robust is None:
+            return                                                     # (a defect: accepted, and no plain session whose read-outs could show it)
         self.robust_error = rem.estimate(self.robust.planes, self.robust.N, threshold=a["threshold"], floor=a["floor"], gain=a["gain"])
 
     def _do_robust_denoise(self, a, traced):
@@ -336,7 +470,10 @@ class PostModel:
         # the session's error records are only read or not touched, and so are the image, the first-hit planes, the snapshot of
         # rtgl_error_estimate and an adaptive session.  The session goes on."  It filters the buckets, never the image or the history:
         # "denoise_source" and "denoise_variance" do not enter
-        self.denoised, self.variance = rdm.robust_denoise(self.robust.planes, self.robust.N, self._plane(A), self._plane(N), self._plane(P), passes=a["passes"],
+        planes, n = self.robust.planes if self.robust is not None else None, self.robust.N if self.robust is not None else 0
+        if self._served_by_defect("robust_denoise serves a robust adaptive session"):
+            planes, n = self.ra.planes, int(self.ra.n.max())           # (a defect: the other session's buckets)
+        self.denoised, self.variance = rdm.robust_denoise(planes, n, self._plane(A), self._plane(N), self._plane(P), passes=a["passes"],
                                                           sigma_lum=a["sigma_lum"], sigma_normal=a["sigma_normal"], sigma_position=a["sigma_position"],
                                                           gain=a["gain"], demodulate=a["demodulate"])
 
@@ -355,6 +492,9 @@ class PostModel:
         rb = self.robust
         out.update(robust_buckets=REFUSED if rb is None else rb.planes, robust_output=REFUSED if rb is None else r(self.robust_output),
                    robust_frames=REFUSED if rb is None else (rb.N, rb.K))
+        ra = None if self.tiled else self.ra                           # "RTGL_ERR_STATE: no session ...; a tiled or multi-device context; rtgl_read_robust_adaptive_f32 before a resolve with dest BUFFER"
+        out.update(robust_adaptive_buckets=REFUSED if ra is None else ra.planes, robust_adaptive_output=REFUSED if ra is None else r(self.ra_output),
+                   robust_adaptive_tiles=REFUSED if ra is None else ra.records, robust_adaptive_mask=REFUSED if ra is None else ra.mask)
         if not self.tiled:
             out.update(robust_error_summary=REFUSED if rb is None else r(self.robust_error),
                        robust_error_tiles=REFUSED if rb is None or self.robust_error is None else self.robust_error["tiles"])
@@ -362,13 +502,14 @@ class PostModel:
 
 
 def walk(model, steps, tracer, params_of=None):
-    """the model through `steps`: [(status, read-outs after the step, the summary an accepted adaptive_update returned or None)].
+    """the model through `steps`: [(status, read-outs after the step, the summary an accepted adaptive_update or robust_adaptive_update
+    returned or None)].
     tracer(step, params, model) is called before every step the model accepts and returns what step() wants as `traced` (None where the
     step traces nothing); it is where a plain twin follows the writers of the image.  params_of(step): the uniforms of a frame step."""
     out = []
     for s in steps:
-        params = params_of(s) if params_of and s.kind in ("render", "adaptive_frame") else None
+        params = params_of(s) if params_of and s.kind in FRAMES else None
         traced = tracer(s, params, model) if model.status_of(s) == OK else None
         status = model.step(s, traced, params)
-        out.append((status, model.readouts(), model.summary if status == OK and s.kind == "adaptive_update" else None))
+        out.append((status, model.readouts(), model.summary if status == OK and s.kind in UPDATES else None))
     return out

@@ -4,11 +4,11 @@ tests/post_sequence_model.py, the host state of a context restated from include/
 Nothing the model is fed comes from the context under test.  A PLAIN TWIN, a second host.Context that only ever traces frames and has its
 image written, cleared and its planes set, supplies the image and the planes after every frame; where the model's image has moved on without
 a frame (a masked frame's merge, a resolve into the image) the twin is handed the MODEL's image before it traces the next one.  Every run
-of ordinary frames of the twin is held to the CPU oracle, and every one-frame sample of a masked frame likewise (the merge is
-adaptive_mirror's).  Every comparison is of bits, a NaN counting as one word; there is no tolerance anywhere.  One printed line per
-differing step.
+of ordinary frames of the twin is held to the CPU oracle, and every one-frame sample of a masked frame of either kind likewise (the merge is
+adaptive_mirror's, the fold robust_adaptive_mirror's).  Every comparison is of bits, a NaN counting as one word; there is no tolerance
+anywhere.  One printed line per differing step.
 
-POST_SEQ_CASES (default 15: five per size) and POST_SEQ_SEED (default 0) choose the sequences, as FUZZ_CASES and FUZZ_SEED do elsewhere.
+POST_SEQ_CASES (default 24: eight per size) and POST_SEQ_SEED (default 0) choose the sequences, as FUZZ_CASES and FUZZ_SEED do elsewhere.
 Twin, oracle and model run once per seed and are shared by the tests."""
 import os
 import re
@@ -96,29 +96,43 @@ def read_all(ctx):
                robust_error_tiles=read(ctx.read_robust_error_tiles))
     frames = out["robust_frames"]
     out["robust_buckets"] = REFUSED if frames == REFUSED else np.stack([ctx.read_robust_bucket(j) for j in range(frames[1])])
+    out.update(robust_adaptive_output=read(ctx.read_robust_adaptive), robust_adaptive_tiles=read(ctx.read_robust_adaptive_tiles),
+               robust_adaptive_mask=read(ctx.robust_adaptive_get_mask), robust_adaptive_buckets=REFUSED)
+    planes = []                                                        # no call tells K: the planes there are, up to the first "bucket >= K"
+    for j in range(max(ps.BUCKETS) + 1):
+        status, plane = status_of(lambda: ctx.read_robust_adaptive_bucket(j))
+        allowed = (0, pm.STATE) if j == 0 else (0,) if j < min(ps.BUCKETS) else (0, pm.INVALID)
+        assert status in allowed, f"rtgl_read_robust_adaptive_bucket_f32({j}) returned {status}"
+        if status:
+            break
+        planes.append(plane)
+    assert len(planes) in (0,) + tuple(ps.BUCKETS), len(planes)
+    if planes:
+        out["robust_adaptive_buckets"] = np.stack(planes)
     return out
 
 
 def normalise(want):
-    """the model's read-outs as the binding returns them: the adaptive records contiguous"""
+    """the model's read-outs as the binding returns them: the records of both kinds of masked-tile session contiguous"""
     out = dict(want)
-    if out["adaptive_tiles"] is not REFUSED:
-        out["adaptive_tiles"] = np.ascontiguousarray(out["adaptive_tiles"])
+    for name in ("adaptive_tiles", "robust_adaptive_tiles"):
+        if out[name] is not REFUSED:
+            out[name] = np.ascontiguousarray(out[name])
     return out
 
 
 def apply(ctx, seq, step, rows=None, bound=0, sync=None):
-    """one step on the context: (status, what an adaptive_update returned)"""
+    """one step on the context: (status, what an adaptive_update or robust_adaptive_update returned)"""
     k, a = step.kind, step.args
     lib, h = ctx.lib, ctx.h
-    if k in ("render", "adaptive_frame"):
+    if k in pm.FRAMES:
         ctx.set_params(ps.frame_params(seq.base, a))
-        rc = lib.rtgl_render_frame(h) if k == "render" else lib.rtgl_adaptive_frame(h)
+        rc = {"render": lib.rtgl_render_frame, "adaptive_frame": lib.rtgl_adaptive_frame, "robust_adaptive_frame": lib.rtgl_robust_adaptive_frame}[k](h)
         if rc == 0 and (a["sync"] if sync is None else sync):
             ctx.synchronize()
         return rc, None
-    if k == "adaptive_update":
-        return status_of(ctx.adaptive_update)
+    if k in pm.UPDATES:
+        return status_of(ctx.adaptive_update if k == "adaptive_update" else ctx.robust_adaptive_update)
     call = {
         "write_image": lambda: ctx.write_image(a["pixels"] if rows is None else a["pixels"][rows]),
         "clear_image": ctx.clear_image, "bind_image": lambda: ctx.bind_device_image(bound),
@@ -130,6 +144,9 @@ def apply(ctx, seq, step, rows=None, bound=0, sync=None):
         "adaptive_begin": lambda: ctx.adaptive_begin(**a), "adaptive_set_mask": lambda: ctx.adaptive_set_mask(a["tiles"]),
         "robust_begin": lambda: ctx.robust_begin(a["buckets"]), "robust_accumulate": ctx.robust_accumulate, "robust_resolve": lambda: ctx.robust_resolve(**a),
         "robust_end": ctx.robust_end, "robust_error_estimate": lambda: ctx.robust_error_estimate(**a), "robust_denoise": lambda: ctx.robust_denoise(**a),
+        "robust_adaptive_begin": lambda: ctx.robust_adaptive_begin(**a), "robust_adaptive_accumulate": ctx.robust_adaptive_accumulate,
+        "robust_adaptive_set_mask": lambda: ctx.robust_adaptive_set_mask(a["tiles"]), "robust_adaptive_resolve": lambda: ctx.robust_adaptive_resolve(**a),
+        "robust_adaptive_end": ctx.robust_adaptive_end,
     }[k]
     return status_of(call)[0], None
 
@@ -140,7 +157,7 @@ def names_the_entry_point(ctx, step):
         return step.args["key"].encode() in text
     if step.kind == "render":
         return b"u_samples" in text
-    return b"rtgl_" + step.kind.encode() + b":" in text
+    return b"rtgl_" + step.kind.encode() + b":" in text          # (robust_adaptive_* included: no name of a call is the head of another's)
 
 
 # ---------------------------------------------------------------------------------------------- the plain twin and the model, once per seed
@@ -197,10 +214,11 @@ class Twin:
             self.run.append(params)
             self.frames += 1
             return dict(image=self.local(self.known), planes={bit: self.local(ctx.read_aov(bit)) for bit in pm.BITS if model.aov & bit})
-        elif k == "adaptive_frame":
+        elif k in ps.MASKED_FRAMES:                                    # the full one-frame sample: the model takes the active tiles from it
             self.end_run()
             p = params.replace(frames=0, reset_flag=1)
-            ctx.render(p)
+            ctx.clear_image()                                          # (a frame traces the footprint only: outside it the sample is +0, not what the twin held;
+            ctx.render(p)                                              #  "aov" is 0 here, so the clear restarts nothing)
             self.known = ctx.read_image()
             want = np.zeros_like(self.known)
             self.oracle.render(self.seq.scene, p, want, threads=16)
@@ -261,7 +279,7 @@ def run_checked(rt, seq, steps, walk, who, rows=None, bound=0, before=None, **ti
         if rc != 0:
             d += [f"{name} changed by a refused call" for name in differing(got, prev)]
         if summary is not None and (got_summary is None or am.same_summary(got_summary, summary)):
-            d.append(f"the summary of adaptive_update: {got_summary}, the model says {summary}")
+            d.append(f"the summary of {s.kind}: {got_summary}, the model says {summary}")
         if d:
             lines.append(f"{who} step {i} {s.kind} {({k: v for k, v in s.args.items() if not isinstance(v, np.ndarray)})}: " + "; ".join(d) + f" | {seq.W} x {seq.H} {seq.units}")
             print(lines[-1], flush=True)
@@ -281,7 +299,7 @@ def run_blind(rt, seq, steps, walk, who, options=()):
         if rc != status:
             lines.append(f"{who} step {i} {s.kind}: status {rc}, the model says {status}")
         if summary is not None and (got_summary is None or am.same_summary(got_summary, summary)):
-            lines.append(f"{who} step {i}: the summary of adaptive_update: {got_summary}, the model says {summary}")
+            lines.append(f"{who} step {i}: the summary of {s.kind}: {got_summary}, the model says {summary}")
     d = differing(read_all(ctx), walk[-1][1])
     if d:
         lines.append(f"{who} at its end: " + "; ".join(d) + f" | {seq.W} x {seq.H} {seq.units}")
@@ -295,6 +313,8 @@ def test_every_step_matches_the_model(rt, oracle):
     t0, bad, steps_run, refused = time.perf_counter(), 0, 0, 0
     rd = {K: 0 for K in ps.BUCKETS}
     rd.update({pm.INVALID: 0, pm.STATE: 0})                            # robust_denoise: accepted per K of the session, and the two refusals
+    ra = {K: 0 for K in ps.BUCKETS}                                    # the robust adaptive session: accepted updates per K, resolves per destination, the refusals
+    ra.update({"buffer": 0, "image": 0, pm.INVALID: 0, pm.STATE: 0})
     for seed in seeds():
         seq, steps, walk, _ = expected(rt, oracle, seed)
         t1 = time.perf_counter()
@@ -306,13 +326,22 @@ def test_every_step_matches_the_model(rt, oracle):
         for s, (st, out, _) in zip(steps, walk):
             if s.kind == "robust_denoise":
                 rd[st if st else out["robust_frames"][1]] += 1
+            if s.kind.startswith("robust_adaptive") and st:
+                ra[st] += 1
+            elif s.kind == "robust_adaptive_update":
+                ra[out["robust_adaptive_buckets"].shape[0]] += 1
+            elif s.kind == "robust_adaptive_resolve":
+                ra["image" if s.args["dest"] else "buffer"] += 1
         print(f"sequence {seed} {seq.W} x {seq.H}: {len(steps)} steps, device part {time.perf_counter() - t1:.2f} s", flush=True)
     print(f"sequences {len(seeds())} steps {steps_run} refused {refused} | differing steps: {bad} | {time.perf_counter() - t0:.2f} s with twin, oracle and model", flush=True)
     print("robust_denoise: accepted " + ", ".join(f"{rd[K]} at K = {K}" for K in ps.BUCKETS) + f"; {rd[pm.INVALID]} times -1, {rd[pm.STATE]} times -4", flush=True)
+    print("robust_adaptive: accepted updates " + ", ".join(f"{ra[K]} at K = {K}" for K in ps.BUCKETS) + f"; resolves {ra['buffer']} into the buffer, {ra['image']} into the image; "
+          f"{ra[pm.INVALID]} times -1, {ra[pm.STATE]} times -4", flush=True)
     assert bad == 0, f"{bad} steps of {len(seeds())} sequences differ from the model (see the lines printed above)"
     assert refused * 10 >= steps_run, "hardly a step was refused"
     if len(seeds()) >= len(ps.ROWS):                                   # every row is among them
         assert all(rd[k] >= 1 for k in rd), rd
+        assert all(ra[k] >= 1 for k in ra), ra
 
 
 def test_the_same_sequence_without_intermediate_read_outs_ends_on_the_same_bits(rt, oracle):
@@ -347,9 +376,10 @@ def test_bound_image_on_a_torch_stream_changes_nothing(rt, oracle):
     dev = torch.device("cuda", 0)
     for seed in seeds():
         seq, steps, walk, _ = expected(rt, oracle, seed)
-        key = (seq.W, seq.H, any(s.kind == "robust_denoise" and st == 0 for s, (st, _, _) in zip(steps, walk)))
-        if key in done:                                                # per size: the first sequence, and the first in which rtgl_robust_denoise is accepted
-            continue
+        accepts = lambda kind: any(s.kind == kind and st == 0 for s, (st, _, _) in zip(steps, walk))
+        key = (seq.W, seq.H, accepts("robust_denoise"), accepts("robust_adaptive_update"))
+        if key in done:                                                # per size: the first sequence, and the first in which rtgl_robust_denoise, the first in which
+            continue                                                   # rtgl_robust_adaptive_update is accepted
         done.add(key)
         tensor = torch.zeros((seq.H, seq.W, 4), dtype=torch.float32, device=dev)
         side = torch.cuda.Stream(device=dev)
@@ -369,13 +399,14 @@ def test_bound_image_on_a_torch_stream_changes_nothing(rt, oracle):
     print(f"bound image: {len(done)} sequences, {time.perf_counter() - t0:.2f} s", flush=True)
     assert bad == 0 and len({k[:2] for k in done}) == min(len(ps.SIZES), len(seeds())), f"{bad} differing steps (see the lines printed above)"
     if len(seeds()) >= len(ps.ROWS):
-        assert sum(k[2] for k in done) == len(ps.SIZES), "rtgl_robust_denoise on a torch stream at every size"
+        assert {k[:2] for k in done if k[2]} == set(ps.SIZES), "rtgl_robust_denoise on a torch stream at every size"
+        assert {k[:2] for k in done if k[3]} == set(ps.SIZES), "rtgl_robust_adaptive_update on a torch stream at every size"
 
 
 def test_a_tiled_context_refuses_or_works_as_the_header_says(rt, oracle):
     """rank 1 of 2, strips of 8 rows, 48 x 40: the robust session works on the local rows; every other post-process call that looks at
-    the picture is RTGL_ERR_STATE and leaves the context as it was"""
-    t0, bad, n, robust_ok, refused = time.perf_counter(), 0, 0, 0, 0
+    the picture, every call of a robust adaptive session among them, is RTGL_ERR_STATE and leaves the context as it was"""
+    t0, bad, n, robust_ok, refused, ra_refused = time.perf_counter(), 0, 0, 0, 0, 0
     tiling = dict(rank=1, world=2, strip_rows=8)
     for seed in seeds():
         if ps.size_of(seed) != (48, 40) or n == ps.DEFAULT_SEQUENCES // len(ps.SIZES):
@@ -384,13 +415,16 @@ def test_a_tiled_context_refuses_or_works_as_the_header_says(rt, oracle):
         seq, steps, walk, rows = expected(rt, oracle, seed, tiling)
         assert len(rows) == 16 and (rows == np.r_[8:16, 24:32]).all()
         for s, (st, out, _) in zip(steps, walk):
-            if s.kind in ("denoise", "denoise_guided", "temporal_accumulate", "temporal_clip", "tonemap", "error_estimate", "robust_error_estimate", "robust_denoise") or s.kind.startswith("adaptive"):
+            if s.kind in ("denoise", "denoise_guided", "temporal_accumulate", "temporal_clip", "tonemap", "error_estimate", "robust_error_estimate", "robust_denoise") or s.kind.startswith(("adaptive", "robust_adaptive")):
                 assert st in (pm.STATE, pm.INVALID), (s.kind, st)
                 refused += st == pm.STATE
+                ra_refused += s.kind.startswith("robust_adaptive")
             robust_ok += st == 0 and s.kind in ("robust_accumulate", "robust_resolve")
         ctx, lines = run_checked(rt, seq, steps, walk, f"sequence {seed}, rank 1 of 2", rows=rows, **tiling)
         ctx.close()
         bad += len(lines)
-    print(f"tiled: {n} sequences, {robust_ok} robust folds and resolves, {refused} refusals, {time.perf_counter() - t0:.2f} s", flush=True)
+    print(f"tiled: {n} sequences, {robust_ok} robust folds and resolves, {refused} refusals, {ra_refused} robust_adaptive steps all refused, {time.perf_counter() - t0:.2f} s", flush=True)
     assert bad == 0, f"{bad} differing steps (see the lines printed above)"
     assert n >= 1 and robust_ok >= 2 and refused >= 10
+    if len(seeds()) >= len(ps.ROWS):                                   # the three robust adaptive rows of 48 x 40 are among them
+        assert n == ps.DEFAULT_SEQUENCES // len(ps.SIZES) and refused >= 120 and ra_refused >= 60, (n, refused, ra_refused)

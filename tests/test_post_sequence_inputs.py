@@ -13,6 +13,7 @@ import error_inputs as ei
 import error_mirror as em
 import post_sequence_inputs as ps
 import post_sequence_model as pm
+import robust_adaptive_mirror as ram
 import robust_denoise_inputs as rdi
 import robust_denoise_mirror as rdm
 import robust_error_mirror as rem
@@ -52,12 +53,12 @@ class Synthetic:
         self.seq, self.k = seq, 0
 
     def __call__(self, step, params, model):
-        if step.kind not in ("render", "adaptive_frame"):
+        if step.kind not in pm.FRAMES:
             return None
         self.k += 1
         rng = np.random.default_rng([self.seq.seed, self.k])
         image, normal, position = ti.view(ps.CAMERAS[step.args["camera"]], self.seq.W, self.seq.H, ti.STEP, rng)
-        if step.kind == "adaptive_frame":
+        if step.kind in ps.MASKED_FRAMES:
             return dict(sample=image)
         planes = {pm.A: mi.albedo_plane(self.seq.H, self.seq.W, self.k), pm.N: normal, pm.P: position, pm.IDS: np.zeros(image.shape, np.int32)}
         return dict(image=image, planes=planes)
@@ -95,9 +96,11 @@ def test_every_alphabet_entry_and_every_hazard_twice(start):
 
 
 def test_five_default_sequences_per_size():
+    """eight since the robust adaptive session's nine rows joined: five per size as before among the first fifteen, three among the new"""
     sizes = [(q.W, q.H) for q in (ps.sequence(s) for s in ps.default_seeds())]
-    assert sorted(set(sizes)) == sorted(ps.SIZES) and all(sizes.count(s) == 5 for s in ps.SIZES)
-    assert ps.DEFAULT_SEQUENCES == len(ps.ROWS) == 5 * len(ps.SIZES)
+    assert sorted(set(sizes)) == sorted(ps.SIZES) and all(sizes.count(s) == 8 for s in ps.SIZES)
+    assert all(sizes[:15].count(s) == 5 for s in ps.SIZES)
+    assert ps.DEFAULT_SEQUENCES == len(ps.ROWS) == 8 * len(ps.SIZES)
 
 
 def test_the_robust_denoise_hazards_read_the_context_as_the_model_does():
@@ -114,6 +117,122 @@ def test_the_robust_denoise_hazards_read_the_context_as_the_model_does():
     # six of the hazards ask for a refusal (three restarts, N < K, after robust_end, a second begin), each in two sequences; every one of
     # the nineteen asks for an accepted call, some share one
     assert n - accepted >= 12 and accepted >= 24, (n, accepted)
+
+
+def test_the_robust_adaptive_hazards_read_the_context_as_the_model_does():
+    """post_sequence_inputs._ra_trace works out from the steps the status of every step of RA_JUDGED, and the predicates of RA_HAZARDS
+    go by it; the model says the same of every one, and of which sessions are open, K and whether the output is readable"""
+    seen = {k: set() for k in ps.RA_JUDGED}
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        for t in ps._ra_trace(seq.steps):
+            if t.status is not None:
+                assert walk[t.i][0] == t.status, (seed, t.i, t.step.kind, walk[t.i][0], t.status)
+                seen[t.step.kind].add(t.status)
+            before = walk[t.i - 1][1] if t.i else None
+            if before is not None and t.ra:
+                assert not isinstance(before["robust_adaptive_mask"], str), (seed, t.i)
+                assert isinstance(before["robust_adaptive_output"], str) != t.buffer, (seed, t.i)
+                assert before["robust_adaptive_buckets"].shape[0] == t.K, (seed, t.i)
+            elif before is not None:
+                assert before["robust_adaptive_mask"] == pm.REFUSED, (seed, t.i)
+            if before is not None:
+                assert isinstance(before["adaptive_mask"], str) != t.ad, (seed, t.i)
+    assert all({0, pm.STATE} <= v for k, v in seen.items() if k != "robust_adaptive_begin"), seen      # (the begin is refused for the state on a tiled context only)
+    assert all(pm.INVALID in seen[k] for k in ("robust_adaptive_begin", "robust_adaptive_resolve") + ps.MASKED_FRAMES), seen
+
+
+def test_the_counts_of_the_trace_are_the_models():
+    """the per-class counts of post_sequence_inputs._ra_trace against the n of the model's session, read off the records after an
+    accepted update: every known count is the count of the tiles of that class"""
+    checked = 0
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        trace = ps._ra_trace(seq.steps)
+        for t in trace[:-1]:
+            if t.step.kind == "robust_adaptive_update" and t.status == 0:
+                records = walk[t.i][1]["robust_adaptive_tiles"]
+                for c, n in t.n.items():
+                    tiles = (ps.mask_tiles("checker", seq.H, seq.W) == c[0]) & (ps.mask_tiles("left", seq.H, seq.W) == c[1]) & (am.tile_pixels(seq.H, seq.W) > 0)
+                    if n is not None and tiles.any():
+                        assert (records["samples"][tiles] == n).all(), (seed, t.i, c, n)
+                        checked += 1
+    assert checked >= 40, checked
+
+
+def test_every_K_has_an_accepted_robust_adaptive_update_with_a_record_that_is_not_zero():
+    """a fill that folded one source K times would give mse = 0 in every tile and a rule with nothing to go by; the updates of a row
+    both stop tiles and keep tiles going, in five of the nine rows, and three updates do both at once.  Not in all nine, and which five
+    depends on the seed: between min_samples = K and max_samples = K + 2 the threshold decides, and it comes in turn from the seed.
+    With 0.05 the synthetic frames meet it at n = K, so every tile of rows 16 and 22 stops at the first update and folds from then on
+    only under explicit masks; with 0.002 no tile meets it, and rows 21 and 23 end their session before any tile reaches K + 2 (their
+    units fold at most once more).  Only the two ends of the rule are free of the data -- below K a tile goes on, at K + 2 it stops --
+    and "ra_resolves" (rows 15 and 17) is the unit that puts both into one update; a second fold in the others does not fit 40 steps"""
+    spread = {K: 0 for K in ps.BUCKETS}
+    mixed, rows = 0, 0
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        stops = keeps = False
+        for s, (status, out, summary) in zip(seq.steps, walk):
+            if s.kind == "robust_adaptive_update" and status == 0:
+                spread[out["robust_adaptive_buckets"].shape[0]] += bool((out["robust_adaptive_tiles"]["mse"] != 0).any())
+                mixed += 0 < summary["tiles_active"] < summary["tiles_total"]
+                stops |= summary["tiles_active"] < summary["tiles_total"]
+                keeps |= summary["tiles_active"] > 0
+        rows += stops and keeps
+    assert all(spread[K] >= 2 for K in ps.BUCKETS), spread
+    assert mixed >= 3 and rows >= 5, (mixed, rows)
+
+
+@pytest.mark.parametrize("defect", pm.DEFECTS)
+def test_every_seeded_defect_is_told_apart(defect):
+    """for every name of post_sequence_model.DEFECTS the model with that one rule wrong, walked over the default sequences on the same
+    synthetic frames, differs from the model in a status, a read-out or an update's summary, in at least two sequences: the device test
+    compares exactly these, so a library with that mistake would fail it.  (No defective library is built.)"""
+    def differs(a, b):
+        for (sa, oa, ma), (sb, ob, mb) in zip(a, b):
+            if sa != sb or (ma is None) != (mb is None) or (ma is not None and am.same_summary(ma, mb)):
+                return True
+            for name in pm.READOUTS:
+                x, y = oa[name], ob[name]
+                if name == "planes":
+                    if any(not same_readout(x[bit], y[bit]) for bit in pm.BITS):
+                        return True
+                elif not same_readout(x, y):
+                    return True
+        return False
+
+    told = []
+    for seed in ps.default_seeds():
+        seq, walk = synthetic_walk(seed)
+        if not any(s.kind.startswith("robust_adaptive") for s in seq.steps):
+            continue                                                   # (every defect is a rule of the robust adaptive session: the model is the model without one)
+        steps = [ps.resolved(seq, s) for s in seq.steps]
+        other = pm.walk(pm.PostModel(seq.H, seq.W, defect=defect), steps, Synthetic(seq), lambda s: ps.frame_params(seq.base, s.args))
+        if differs(walk, other):
+            told.append(seed)
+    assert len(told) >= 2, f"told apart in fewer than two sequences: {told}"
+
+
+def test_the_seeded_defects_are_named_once_each():
+    assert len(pm.DEFECTS) >= 15 and len(set(pm.DEFECTS)) == len(pm.DEFECTS)
+    with pytest.raises(AssertionError):
+        pm.PostModel(16, 16, defect="no such rule")
+
+
+def same_readout(x, y):
+    if x is y:
+        return True
+    if isinstance(x, str) or isinstance(y, str):
+        return isinstance(x, str) and isinstance(y, str) and x == y
+    if isinstance(x, dict):
+        return isinstance(y, dict) and x.keys() == y.keys() and all(same_readout(x[k], y[k]) for k in x)
+    if isinstance(x, tuple):
+        return isinstance(y, tuple) and len(x) == len(y) and all(same_readout(p, q) for p, q in zip(x, y))
+    x, y = np.asarray(x), np.asarray(y)
+    if x.dtype.names:
+        return x.shape == y.shape and np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes()
+    return same(x, y) if x.dtype == f32 and y.dtype == f32 else x.shape == y.shape and bool((x == y).all())
 
 
 def test_the_buckets_of_an_accepted_robust_denoise_differ_for_every_K():
@@ -144,7 +263,9 @@ def test_both_refusal_classes_are_predicted_for_every_feature():
 
 
 def test_a_refused_step_changes_no_read_out():
-    for seed in ps.default_seeds()[:3]:
+    """rows 0 to 2, and two of the robust adaptive session's: a refused begin, a masked frame with samples = 2, a resolve with dest = 2 and
+    the calls after the end leave the session's four read-outs the very arrays they were"""
+    for seed in ps.default_seeds()[:3] + [16, 23]:
         seq, walk = synthetic_walk(seed)
         for k in range(1, len(walk)):
             if walk[k][0] != 0:
@@ -158,7 +279,7 @@ def test_the_nan_share_of_the_expected_outputs_stays_under_the_cap():
     total = nans = 0
     for seed in ps.default_seeds():
         for _, out, _ in synthetic_walk(seed)[1]:
-            for name in ("image", "denoised", "variance", "history", "moments", "robust_buckets", "robust_output"):
+            for name in ("image", "denoised", "variance", "history", "moments", "robust_buckets", "robust_output", "robust_adaptive_buckets", "robust_adaptive_output"):
                 if not isinstance(out[name], str):
                     total += out[name].size
                     nans += int(np.isnan(out[name]).sum())
@@ -302,6 +423,98 @@ def test_the_robust_session_alone(K):
         assert same(a["robust_output"], alone.resolve(gain)) and same(c["image"], alone.resolve(gain, rm.DEST_IMAGE))
         assert em.same_result(b["robust_error_summary"], rem.estimate(alone.planes, alone.N, gain=gain)) == []
         assert c["robust_frames"] == (alone.N, K)
+
+
+@pytest.mark.parametrize("K", ram.BUCKETS)
+def test_the_robust_adaptive_session_alone(K):
+    """begin, folds of both kinds, masks, updates and both resolves: what a bare robust_adaptive_mirror.Session gives, fed the same
+    samples; every RTGL_ERR_INVALID and RTGL_ERR_STATE of the header's block; a tiled context"""
+    samples = ri.noisy(np.random.default_rng(7 + K), H, W, K + 3, firefly=0.0)
+    params = dict(buckets=K, threshold=0.05, floor=0.01, gain=1.0, min_samples=K, max_samples=K + 2)
+    begin = lambda **over: S("robust_adaptive_begin", **dict(params, **over))
+    frame = lambda **over: S("robust_adaptive_frame", camera=None, **over)
+    kinds = ("frame", "accumulate", "update", "set_mask", "resolve", "end")
+    call = {"frame": frame(), "accumulate": S("robust_adaptive_accumulate"), "update": S("robust_adaptive_update"), "end": S("robust_adaptive_end"),
+            "set_mask": S("robust_adaptive_set_mask", tiles=ps.mask_tiles("checker", H, W)), "resolve": S("robust_adaptive_resolve", gain=1.0, dest=0)}
+    written = ps.written_image(H, W, 3)
+    # without a session: -4 of every call but begin, and the four read-outs refused; the bad arguments of begin and resolve come first
+    steps = [call[k] for k in kinds] + [begin(min_samples=K - 1), begin(buckets=5), begin(threshold=0.0), begin(floor=float("nan")), begin(gain=-1.0),
+                                       begin(max_samples=K - 1, min_samples=K), begin(max_samples=(1 << 24) + 1), S("robust_adaptive_resolve", gain=1.0, dest=2),
+                                       S("write_image", pixels=written), begin()]
+    want = [pm.STATE] * 6 + [pm.INVALID] * 8 + [None, None]
+    alone, checks = ram.Session(H, W, **params), {}
+
+    def then(step, check=None, status=None):
+        steps.append(step)
+        want.append(status)
+        if check is not None:
+            checks[len(steps) - 1] = check
+
+    state = lambda: (alone.planes.copy(), alone.records.copy(), alone.mask.copy())
+    then(S("robust_adaptive_resolve", gain=1.0, dest=0), ("output", alone.resolve(1.0)))           # N = 0 everywhere: zeros
+    fed = []
+    for k, smp in enumerate(samples):
+        if k == 2:
+            tiles = ps.mask_tiles("checker", H, W)
+            alone.set_mask(tiles)
+            then(S("robust_adaptive_set_mask", tiles=tiles), ("state", state()))
+        if k % 2:
+            alone.fold(smp)
+            fed.append(smp)
+            then(frame(), ("state", state()))
+        else:                                                          # the image as it stands: a written one
+            alone.fold(written)
+            then(S("robust_adaptive_accumulate"), ("state", state()))
+        if k >= K - 2:
+            summary = alone.update()
+            then(S("robust_adaptive_update"), ("update", summary, state()))
+    then(frame(samples=2), status=pm.INVALID)                          # in an open session with "aov" 0
+    then(S("set_aov", mask=4))
+    then(frame(), status=pm.STATE)
+    then(frame(samples=2), status=pm.STATE)                            # the state comes first
+    then(S("set_aov", mask=0))
+    for gain in (1.0, 0.0, 2.5):
+        then(S("robust_adaptive_resolve", gain=gain, dest=0), ("output", alone.resolve(gain)))
+        then(S("robust_adaptive_resolve", gain=gain, dest=1), ("image", alone.resolve(gain, ram.DEST_IMAGE)))
+    then(S("robust_adaptive_resolve", gain=-1.0, dest=0), status=pm.INVALID)
+    then(begin(min_samples=K - 1), ("state", state()), status=pm.INVALID)       # a refused begin leaves the session as it is
+    alone = ram.Session(H, W, **params)
+    then(begin(), ("restarted", state()))                              # a second begin: zeroed, every tile active, the output refused, the image kept
+    then(S("robust_adaptive_end"))
+    then(S("robust_adaptive_end"), status=pm.STATE)
+    it = iter(fed)
+    model = pm.PostModel(H, W)
+    walk = pm.walk(model, steps, lambda s, p, m: dict(sample=next(it)) if s.kind == "robust_adaptive_frame" else None)
+    assert len(walk) == len(want) == len(steps)
+    updates = 0
+    for k, ((status, out, summary), w) in enumerate(zip(walk, want)):
+        assert status == (0 if w is None else w), (k, steps[k].kind, status, w)
+        c = checks.get(k)
+        if c is None:
+            continue
+        if c[0] == "output":
+            assert same(out["robust_adaptive_output"], c[1]), k
+        elif c[0] == "image":
+            assert same(out["image"], c[1]), k
+        else:
+            planes, records, mask = c[-1]
+            assert same(out["robust_adaptive_buckets"], planes) and out["robust_adaptive_tiles"].tobytes() == records.tobytes() and (out["robust_adaptive_mask"] == mask).all(), k
+        if c[0] == "update":
+            assert am.same_summary(summary, c[1]) == [], k
+            updates += 1
+        if c[0] == "restarted":
+            assert out["robust_adaptive_output"] == pm.REFUSED and not out["robust_adaptive_buckets"].any() and same(out["image"], walk[k - 1][1]["image"]), k
+    assert updates == 5 and (walk[len(steps) - 4][1]["robust_adaptive_tiles"]["mse"] != 0).any()
+    names = ("robust_adaptive_buckets", "robust_adaptive_output", "robust_adaptive_tiles", "robust_adaptive_mask")
+    assert all(walk[k][1][n] == pm.REFUSED for k in (0, 13, len(steps) - 1) for n in names)           # no session: all four read-outs
+    assert walk[15][1]["robust_adaptive_output"] == pm.REFUSED and not isinstance(walk[15][1]["robust_adaptive_mask"], str)       # begun, not resolved
+    assert same(walk[15][1]["image"], written), "the begin does not touch the image"
+    it = iter(fed)
+    tiled = pm.walk(pm.PostModel(H, W, tiled=True), steps, lambda s, p, m: dict(sample=next(it)) if s.kind == "robust_adaptive_frame" else None)
+    for s, (status, out, _), w in zip(steps, tiled, want):
+        if s.kind.startswith("robust_adaptive"):
+            assert status == (pm.INVALID if w == pm.INVALID and s.kind != "robust_adaptive_frame" else pm.STATE), (s.kind, status)
+            assert all(out[n] == pm.REFUSED for n in names)
 
 
 @pytest.mark.parametrize("K", rm.BUCKETS)
