@@ -21,10 +21,14 @@
 #include "rt_mfma.hpp"
 #include "rt_scan.hpp"
 #include "rt_denoise.hpp"
+#include "rt_denoise_plan.hpp"
 #include "rt_temporal.hpp"
 #include "rt_temporal_clip.hpp"
+#include "rt_temporal_plan.hpp"
 #include "rt_tonemap.hpp"
+#include "rt_tonemap_plan.hpp"
 #include "rt_error.hpp"
+#include "rt_error_plan.hpp"
 #include "rt_adaptive.hpp"
 #include "rt_adaptive_plan.hpp"
 #include "rt_robust.hpp"
@@ -317,16 +321,15 @@ struct rtgl_context {
     // first call that needs them; tm_moments: the mode (1, 2) whose records the latest successful call stored in set tm_cur, 0: none
     float4 *d_tm_moments[2] = {nullptr, nullptr}; int tm_moments = 0;
     // rtgl_tonemap: the RGBA8 display buffer and the state the kernels share (two histogram sets that take turns and the exposure,
-    // rt_tonemap.hpp), allocated by the first call.  has_display: a call has succeeded; tone_set: the set the next auto call counts in;
-    // tone_hist_set: the set the latest auto call counted in (-1: none yet); tone_prev: the state holds an exposure stored since the last
-    // rtgl_tonemap_reset; tone_auto: the latest call solved its exposure on the device, otherwise it used tone_exposure
+    // rt_tonemap.hpp), allocated by the first call.  has_display: a call has succeeded; tone: the turn of the two sets
+    // (rt_tonemap_plan.hpp); tone_auto: the latest call solved its exposure on the device, otherwise it used tone_exposure
     uchar4 *d_display = nullptr; uint32_t *d_tone_state = nullptr;
-    bool has_display = false, tone_prev = false, tone_auto = false; int tone_set = 0, tone_hist_set = -1; float tone_exposure = 1.0f;
-    // rtgl_error_estimate (rt_error.hpp): the luminance snapshot, the tile records and the summary, allocated by the first call.  The
-    // snapshot is usable while err_snap_epoch == err_epoch: every event that drops it (header, "error estimate") advances err_epoch.
-    // err_fm, err_first: the snapshot's `frames` and first_frames; err_rendered, err_fn: a frame has been rendered, and its `frames`
+    bool has_display = false, tone_auto = false; rt_tonemap_plan::Sets tone; float tone_exposure = 1.0f;
+    // rtgl_error_estimate (rt_error.hpp): the luminance snapshot, the tile records and the summary, allocated by the first call.  err:
+    // what the host knows of the accumulation and of the snapshot (rt_error_plan.hpp); every event that drops the snapshot (header,
+    // "error estimate") goes through rt_error_plan::drop
     float *d_err_snapshot = nullptr; uint4 *d_err_tiles = nullptr; uint32_t *d_err_summary = nullptr;
-    uint64_t err_epoch = 1, err_snap_epoch = 0; int32_t err_fm = 0, err_first = 0, err_fn = 0; bool err_rendered = false, has_error = false;
+    rt_error_plan::Snapshot err; bool has_error = false;
     // adaptive sampling (rt_adaptive.hpp, rt_adaptive_plan.hpp), all allocated by the first rtgl_adaptive_begin: the session's masked tiles
     // and the snapshot plane.  has_adaptive: a begin has succeeded, so the tile records can be read
     TileSession ad; float *d_ad_snapshot = nullptr;
@@ -380,6 +383,20 @@ static int read_rows(rtgl_context *ctx, void *dst, const void *src, size_t px_by
     HIPCHK(ctx, hipMemcpyAsync(dst, src, (size_t)ctx->local_rows * ctx->width * px_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return RTGL_OK;
+}
+
+// The two getters of a plane that one call writes.  `ready`: that call has succeeded; otherwise the message is `who` + `why`.  `what`: the
+// whole message for a NULL `dst` (some entry points say it with their name, some without)
+static int read_plane(rtgl_context *ctx, void *dst, const char *what, bool ready, const void *src, size_t px_bytes, const char *who, const char *why)
+{
+    if (!dst) return fail(ctx, RTGL_ERR_INVALID, what);
+    if (!ready) return fail(ctx, RTGL_ERR_STATE, std::string(who) + why);
+    return read_rows(ctx, dst, src, px_bytes);
+}
+static void *device_plane(rtgl_context *ctx, bool ready, const void *ptr, const char *who, const char *why)
+{
+    if (!ready) { ctx->error = std::string(who) + why; return nullptr; }
+    return (void *)ptr;
 }
 
 template <typename T>
@@ -1441,8 +1458,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
 {
     const uint32_t B = (uint32_t)batch.size();
     for (const FrameParams &f : batch) {                 // rtgl_error_estimate: a reset frame starts a new accumulation; the latest frame's `frames`
-        if (f.reset_flag) ++ctx->err_epoch;
-        ctx->err_fn = f.frames; ctx->err_rendered = true;
+        rt_error_plan::rendered_frame(ctx->err, f.frames, f.reset_flag != 0);
     }
     if (ctx->visits_dirty) { int rc = rebuild_sphere_visits(ctx); if (rc) return rc; }
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
@@ -1612,7 +1628,7 @@ extern "C" int rtgl_write_image_f32(rtgl_context *ctx, const float *rgba)
 {
     ENTER(ctx);
     if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
-    ++ctx->err_epoch;                                   // (rtgl_error_estimate: another image, the snapshot is dropped)
+    rt_error_plan::drop(ctx->err);                      // (rtgl_error_estimate: another image, the snapshot is dropped)
     ctx->ad.active = false;                             // (adaptive sampling: ... and the session ends)
     if (!ctx->parts.empty()) {                          // scatter the rows to their owners
         ctx->gathered = false;
@@ -1637,7 +1653,7 @@ extern "C" int rtgl_clear_image(rtgl_context *ctx)
     FANOUT(ctx, rtgl_clear_image(part));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;                              // the first-hit planes' mean restarts with the next frame (their contents stay)
-    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the snapshot is dropped)
+    rt_error_plan::drop(ctx->err);                        // (rtgl_error_estimate: the snapshot is dropped)
     ctx->ad.active = false;                               // (adaptive sampling: the session ends)
     return RTGL_OK;
 }
@@ -1681,7 +1697,7 @@ extern "C" int rtgl_bind_device_image(rtgl_context *ctx, void *dptr)
     ENTER(ctx);
     if (!ctx->parts.empty()) return fail(ctx, RTGL_ERR_STATE, "a multi-device context renders into its own per-device tile buffers");
     ctx->d_image = dptr ? (float4 *)dptr : ctx->d_image_own;
-    ++ctx->err_epoch;                                     // (rtgl_error_estimate: another image, the snapshot is dropped)
+    rt_error_plan::drop(ctx->err);                        // (rtgl_error_estimate: another image, the snapshot is dropped)
     ctx->ad.active = false;                               // (adaptive sampling: ... and the session ends)
     return RTGL_OK;
 }
@@ -1811,11 +1827,17 @@ extern "C" void *rtgl_device_aov(rtgl_context *ctx, int plane)
 }
 
 // ---- rtgl_denoise: edge-avoiding a-trous filter guided by the first-hit planes (rt_denoise.hpp) --------
+static_assert(sizeof(rtgl_denoise_params) == sizeof(rt_denoise_plan::Params) && offsetof(rtgl_denoise_params, flags) == offsetof(rt_denoise_plan::Params, flags)
+              && sizeof(rtgl_denoise_guided_params) == sizeof(rt_denoise_plan::GuidedParams) && offsetof(rtgl_denoise_guided_params, flags) == offsetof(rt_denoise_plan::GuidedParams, flags)
+              && rt_denoise_plan::kFlagDemodulate == (uint32_t)RTGL_DENOISE_DEMODULATE && rt_denoise_plan::kPlaneAlbedo == (uint32_t)RTGL_AOV_ALBEDO
+              && rt_denoise_plan::kPlaneNormal == (uint32_t)RTGL_AOV_NORMAL && rt_denoise_plan::kPlanePosition == (uint32_t)RTGL_AOV_POSITION
+              && rt_denoise_plan::kPrepLdsBytes == kPrepLdsBytes, "the layouts of the header and of the kernels");
+
 extern "C" int rtgl_denoise_defaults(rtgl_denoise_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->passes = 5; out->sigma_color = 16.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f; out->flags = RTGL_DENOISE_DEMODULATE;
+    const rt_denoise_plan::Params p = rt_denoise_plan::default_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
@@ -1831,36 +1853,31 @@ static const float4 *denoise_input(const rtgl_context *ctx)
 template <bool kDemod, bool kRemod>
 static void launch_atrous(rtgl_context *ctx, const AtrousArgs &a)
 {
-    const int s = a.step, wt = 64 + 4 * s;
-    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)(((a.height + 4 * s - 1) / (4 * s)) * s));
-    const size_t lds = (size_t)2 * 9 * wt * sizeof(float);
-    if (wt > 256) hipLaunchKernelGGL((atrous_kernel<kDemod, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
+    const rt_denoise_plan::Pass g = rt_denoise_plan::pass((uint32_t)a.step_log2, a.width, a.height);
+    const dim3 grid(g.grid_x, g.grid_y);
+    const size_t lds = rt_denoise_plan::lds_bytes(g, rt_denoise_plan::kAtrousArrays);
+    if (g.wide) hipLaunchKernelGGL((atrous_kernel<kDemod, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL((atrous_kernel<kDemod, kRemod, false>), grid, dim3(256), lds, ctx->stream, a);
 }
 
 extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params)
 {
     ENTER(ctx);
-    rtgl_denoise_params P;
-    rtgl_denoise_defaults(&P);
-    if (params) P = *params;
-    if (P.passes > 8u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: passes must be 0..8");
-    if (!std::isfinite(P.sigma_color) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: the sigmas must be finite (<= 0 switches a term off)");
-    if (P.flags & ~(uint32_t)RTGL_DENOISE_DEMODULATE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: unknown flag bits");
-    if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise: reserved fields must be 0");
+    rt_denoise_plan::Params P = rt_denoise_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_denoise_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_denoise: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
                                          "render on a single-device context, or filter the gathered image yourself");
-    const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_c = P.sigma_color > 0.0f, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
-    const size_t n = (size_t)ctx->local_rows * ctx->width;
-    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: this context holds no pixels");
+    if (const char *why = rt_bucket_guide_plan::planes_refused(rt_denoise_plan::planes_needed(P), (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
+    const size_t n = rt_denoise_plan::pixels(ctx->local_rows, ctx->width);
+    if (const char *why = rt_denoise_plan::input_refused(n, ctx->opt.denoise_source, ctx->has_temporal)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise: ") + why);
     const float4 *input = denoise_input(ctx);
-    if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
+    const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_c = P.sigma_color > 0.0f, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
     // pass k of K reads the image (k = 0) or the buffer pass k - 1 wrote, and writes the denoised buffer (k = K - 1) or scratch k & 1
-    RCCHK(buf_ensure(ctx, ctx->d_denoised, n * 16));
-    for (uint32_t k = 0; k < 2u && k + 1u < P.passes; ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_denoised, rt_denoise_plan::record_bytes(n)));
+    for (uint32_t k = 0; k < rt_denoise_plan::scratch_buffers(P.passes); ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], rt_denoise_plan::record_bytes(n)));
     AtrousArgs a{};
     a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
     a.width = ctx->width; a.height = ctx->local_rows;
@@ -1869,7 +1886,7 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
     a.use_color = use_c; a.use_normal = use_n; a.use_position = use_p;
     if (P.passes == 0u) {
         a.src = input; a.dst = ctx->d_denoised;
-        const dim3 grid((unsigned)((n + 255) / 256));
+        const dim3 grid(rt_denoise_plan::identity_blocks(n));
         if (demod) hipLaunchKernelGGL(atrous_identity_kernel<true>, grid, dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(atrous_identity_kernel<false>, grid, dim3(256), 0, ctx->stream, a);
     }
@@ -1891,27 +1908,25 @@ extern "C" int rtgl_denoise(rtgl_context *ctx, const rtgl_denoise_params *params
     return RTGL_OK;
 }
 
+static const char *const kNoDenoise = ": no rtgl_denoise call has succeeded on this context";
+
 extern "C" int rtgl_read_denoised_f32(rtgl_context *ctx, float *rgba)
 {
     ENTER(ctx);
-    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
-    if (!ctx->has_denoised) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoised_f32: no rtgl_denoise call has succeeded on this context");
-    return read_rows(ctx, rgba, ctx->d_denoised, 16);
+    return read_plane(ctx, rgba, "rgba is NULL", ctx->has_denoised, ctx->d_denoised, 16, "rtgl_read_denoised_f32", kNoDenoise);
 }
 
 extern "C" void *rtgl_device_denoised(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_denoised) { ctx->error = "rtgl_device_denoised: no rtgl_denoise call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_denoised;
+    return ctx ? device_plane(ctx, ctx->has_denoised, ctx->d_denoised, "rtgl_device_denoised", kNoDenoise) : nullptr;
 }
 
 // ---- rtgl_denoise_guided: variance-guided a-trous filter with a firefly clamp (rt_denoise.hpp, guided_*) --------
 extern "C" int rtgl_denoise_guided_defaults(rtgl_denoise_guided_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->passes = 5; out->sigma_lum = 4.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f; out->firefly_ratio = 1.0f; out->flags = RTGL_DENOISE_DEMODULATE;
+    const rt_denoise_plan::GuidedParams p = rt_denoise_plan::default_guided_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
@@ -1919,10 +1934,10 @@ extern "C" int rtgl_denoise_guided_defaults(rtgl_denoise_guided_params *out)
 template <bool kLast, bool kRemod>
 static void launch_guided(rtgl_context *ctx, const GuidedArgs &a)
 {
-    const int s = a.step, wt = 64 + 4 * s;
-    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)(((a.height + 4 * s - 1) / (4 * s)) * s));
-    const size_t lds = (size_t)2 * 10 * wt * sizeof(float);
-    if (wt > 256) hipLaunchKernelGGL((guided_kernel<kLast, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
+    const rt_denoise_plan::Pass g = rt_denoise_plan::pass((uint32_t)a.step_log2, a.width, a.height);
+    const dim3 grid(g.grid_x, g.grid_y);
+    const size_t lds = rt_denoise_plan::lds_bytes(g, rt_denoise_plan::kGuidedArrays);
+    if (g.wide) hipLaunchKernelGGL((guided_kernel<kLast, kRemod, true>), grid, dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL((guided_kernel<kLast, kRemod, false>), grid, dim3(256), lds, ctx->stream, a);
 }
 
@@ -1947,38 +1962,27 @@ static int launch_guided_passes(rtgl_context *ctx, GuidedArgs a, uint32_t passes
 extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_params *params)
 {
     ENTER(ctx);
-    rtgl_denoise_guided_params P;
-    rtgl_denoise_guided_defaults(&P);
-    if (params) P = *params;
-    if (P.passes > 8u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: passes must be 0..8");
-    if (!std::isfinite(P.sigma_lum) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position) || !std::isfinite(P.firefly_ratio))
-        return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: the sigmas and the firefly ratio must be finite (<= 0 switches the normal term, the position term or the clamp off)");
-    if (!(P.sigma_lum > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: sigma_lum must be > 0");
-    if (P.flags & ~(uint32_t)RTGL_DENOISE_DEMODULATE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: unknown flag bits");
-    if (P.reserved[0] || P.reserved[1]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_denoise_guided: reserved fields must be 0");
+    rt_denoise_plan::GuidedParams P = rt_denoise_plan::default_guided_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_denoise_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_denoise_guided: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: a tiled or multi-device context holds strips that lack their neighbours' rows; filtering a gathered image is out of scope: "
                                          "render on a single-device context, or filter the gathered image yourself");
+    if (const char *why = rt_bucket_guide_plan::planes_refused(rt_denoise_plan::planes_needed(P), (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
+    const size_t n = rt_denoise_plan::pixels(ctx->local_rows, ctx->width);
+    if (const char *why = rt_denoise_plan::input_refused(n, ctx->opt.denoise_source, ctx->has_temporal)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
     const bool demod = (P.flags & RTGL_DENOISE_DEMODULATE) != 0, use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const uint32_t need = (demod ? RTGL_AOV_ALBEDO : 0) | (use_n ? RTGL_AOV_NORMAL : 0) | (use_p ? RTGL_AOV_POSITION : 0);
-    if (const char *why = rt_bucket_guide_plan::planes_refused(need, (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
-    const size_t n = (size_t)ctx->local_rows * ctx->width;
-    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: this context holds no pixels");
+    if (const char *why = rt_denoise_plan::guided_variance_refused(ctx->opt.denoise_variance, ctx->opt.denoise_source, ctx->tm_moments, demod))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_denoise_guided: ") + why);
     const float4 *input = denoise_input(ctx);
-    if (!input) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_source\" is 1 and no rtgl_temporal_accumulate call has succeeded on this context");
     const bool tvar = ctx->opt.denoise_variance == 1;
-    if (tvar) {
-        if (ctx->opt.denoise_source != 1) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and \"denoise_source\" is not: the temporal variance is that of the history");
-        if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the latest rtgl_temporal_accumulate stored no moments (option \"temporal_moments\")");
-        if (ctx->tm_moments != (demod ? 2 : 1))
-            return fail(ctx, RTGL_ERR_STATE, "rtgl_denoise_guided: \"denoise_variance\" is 1 and the stored moments are of the other kind: RTGL_DENOISE_DEMODULATE needs \"temporal_moments\" = 2, a call without it 1");
-    }
     // the prepare kernel writes scratch 0 (passes = 0: the denoised buffer); pass k of K reads scratch k & 1 and writes scratch (k + 1) & 1
     // or, as the last, the denoised buffer
-    RCCHK(buf_ensure(ctx, ctx->d_denoised, n * 16));
-    RCCHK(buf_ensure(ctx, ctx->d_dn_variance, n * 16));
-    RCCHK(buf_ensure(ctx, ctx->d_dn_near, n * 4));
-    for (uint32_t k = 0; k < 2u && k < P.passes; ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], n * 16));
+    RCCHK(buf_ensure(ctx, ctx->d_denoised, rt_denoise_plan::record_bytes(n)));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_variance, rt_denoise_plan::record_bytes(n)));
+    RCCHK(buf_ensure(ctx, ctx->d_dn_near, rt_denoise_plan::near_bytes(n)));
+    for (uint32_t k = 0; k < rt_denoise_plan::guided_scratch_buffers(P.passes); ++k) RCCHK(buf_ensure(ctx, ctx->d_dn_scratch[k], rt_denoise_plan::record_bytes(n)));
     GuidedArgs a{};
     a.image = input; a.variance = ctx->d_dn_variance; a.near = ctx->d_dn_near;
     a.albedo = demod ? ctx->d_aov[0] : nullptr; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = use_p ? ctx->d_aov[2] : nullptr;
@@ -1990,7 +1994,7 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     a.use_clamp = P.firefly_ratio > 0.0f; a.use_normal = use_n; a.use_position = use_p;
     a.demodulate = demod; a.final_image = P.passes == 0u;
     a.dst = P.passes == 0u ? ctx->d_denoised : ctx->d_dn_scratch[0];
-    const dim3 prep_grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
+    const dim3 prep_grid(rt_denoise_plan::prepare_grid_x(a.width), rt_denoise_plan::prepare_grid_y(a.height));
     if (tvar) {
         GuidedTvarArgs t{};
         t.g = a; t.moments = ctx->d_tm_moments[ctx->tm_cur];
@@ -1999,27 +2003,30 @@ extern "C" int rtgl_denoise_guided(rtgl_context *ctx, const rtgl_denoise_guided_
     return launch_guided_passes(ctx, a, P.passes, demod);
 }
 
+static const char *const kNoDenoiseGuided = ": no rtgl_denoise_guided call has succeeded on this context";
+
 extern "C" int rtgl_read_denoise_variance_f32(rtgl_context *ctx, float *rgba)
 {
     ENTER(ctx);
-    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
-    if (!ctx->has_dn_variance) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_denoise_variance_f32: no rtgl_denoise_guided call has succeeded on this context");
-    return read_rows(ctx, rgba, ctx->d_dn_variance, 16);
+    return read_plane(ctx, rgba, "rgba is NULL", ctx->has_dn_variance, ctx->d_dn_variance, 16, "rtgl_read_denoise_variance_f32", kNoDenoiseGuided);
 }
 
 extern "C" void *rtgl_device_denoise_variance(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_dn_variance) { ctx->error = "rtgl_device_denoise_variance: no rtgl_denoise_guided call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_dn_variance;
+    return ctx ? device_plane(ctx, ctx->has_dn_variance, ctx->d_dn_variance, "rtgl_device_denoise_variance", kNoDenoiseGuided) : nullptr;
 }
 
 // ---- rtgl_temporal_accumulate: reprojected history across camera moves (rt_temporal.hpp) --------
+static_assert(sizeof(rtgl_temporal_params) == sizeof(rt_temporal_plan::Params) && offsetof(rtgl_temporal_params, flags) == offsetof(rt_temporal_plan::Params, flags)
+              && sizeof(rtgl_temporal_clip_params) == sizeof(rt_temporal_plan::ClipParams) && offsetof(rtgl_temporal_clip_params, flags) == offsetof(rt_temporal_plan::ClipParams, flags)
+              && rt_temporal_plan::kPlaneAlbedo == (uint32_t)RTGL_AOV_ALBEDO && rt_temporal_plan::kPlaneNormal == (uint32_t)RTGL_AOV_NORMAL
+              && rt_temporal_plan::kPlanePosition == (uint32_t)RTGL_AOV_POSITION, "the layouts of the header");
+
 extern "C" int rtgl_temporal_defaults(rtgl_temporal_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->max_history = 32.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f;
+    const rt_temporal_plan::Params p = rt_temporal_plan::default_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
@@ -2050,7 +2057,7 @@ template <int kMom, bool kHistory, bool kStatic>
 static void launch_temporal(rtgl_context *ctx, const typename TemporalArgsOf<kMom>::type &a, bool use_n, bool use_p)
 {
     const TemporalArgs &t = temporal_base(a);
-    const dim3 grid((unsigned)((t.width + 63) / 64), (unsigned)((t.height + 3) / 4));
+    const dim3 grid(rt_temporal_plan::grid_x(t.width), rt_temporal_plan::grid_y(t.height));
     if (!kHistory) hipLaunchKernelGGL((temporal_kernel<false, false, false, false, kMom>), grid, dim3(256), 0, ctx->stream, a);
     else if (use_n && use_p) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, true, kMom>), grid, dim3(256), 0, ctx->stream, a);
     else if (use_n) hipLaunchKernelGGL((temporal_kernel<true, kStatic, true, false, kMom>), grid, dim3(256), 0, ctx->stream, a);
@@ -2068,33 +2075,28 @@ static void launch_temporal(rtgl_context *ctx, const typename TemporalArgsOf<kMo
 extern "C" int rtgl_temporal_accumulate(rtgl_context *ctx, const rtgl_temporal_params *params)
 {
     ENTER(ctx);
-    rtgl_temporal_params P;
-    rtgl_temporal_defaults(&P);
-    if (params) P = *params;
-    if (!std::isfinite(P.max_history) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: max_history and the sigmas must be finite (a sigma <= 0 switches its test off)");
-    if (!(P.max_history >= 1.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: max_history must be >= 1");
-    if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: no flag bits are defined");
-    if (P.reserved[0] || P.reserved[1] || P.reserved[2] || P.reserved[3]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_accumulate: reserved fields must be 0");
+    rt_temporal_plan::Params P = rt_temporal_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_temporal_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_temporal_accumulate: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a tiled or multi-device context holds strips; a reprojected pixel may come from another strip, which is out of scope: "
                                          "render on a single-device context");
     const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
     const int moments = ctx->opt.temporal_moments;
-    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0) | (moments == 2 ? RTGL_AOV_ALBEDO : 0);
-    if (need & ~ctx->opt.aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: a first-hit plane this call needs is not enabled (option \"aov\": position always, normal for sigma_normal > 0, albedo for \"temporal_moments\" = 2)");
-    if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: no frame has been rendered since the first-hit planes last restarted");
-    const size_t n = (size_t)ctx->local_rows * ctx->width;
-    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_accumulate: this context holds no pixels");
+    if (const char *why = rt_temporal_plan::planes_refused(rt_temporal_plan::planes_needed(P, moments), (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n, false))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_temporal_accumulate: ") + why);
+    const size_t n = rt_temporal_plan::pixels(ctx->local_rows, ctx->width);
+    if (const char *why = rt_temporal_plan::pixels_refused(n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_temporal_accumulate: ") + why);
     const bool with_normal = (ctx->opt.aov & RTGL_AOV_NORMAL) != 0;      // the normal plane is copied whenever it is on, tested or not
     for (int k = 0; k < 2; ++k) {
-        RCCHK(buf_ensure(ctx, ctx->d_tm_hist[k], n * 16));
-        RCCHK(buf_ensure(ctx, ctx->d_tm_position[k], n * 16));
-        if (with_normal) RCCHK(buf_ensure(ctx, ctx->d_tm_normal[k], n * 16));
-        if (moments) RCCHK(buf_ensure(ctx, ctx->d_tm_moments[k], n * 16));
+        RCCHK(buf_ensure(ctx, ctx->d_tm_hist[k], rt_temporal_plan::record_bytes(n)));
+        RCCHK(buf_ensure(ctx, ctx->d_tm_position[k], rt_temporal_plan::record_bytes(n)));
+        if (with_normal) RCCHK(buf_ensure(ctx, ctx->d_tm_normal[k], rt_temporal_plan::record_bytes(n)));
+        if (moments) RCCHK(buf_ensure(ctx, ctx->d_tm_moments[k], rt_temporal_plan::record_bytes(n)));
     }
     const TemporalCamera cam = temporal_camera(ctx->params, ctx->width, ctx->height);
-    const bool history = ctx->tm_valid && !(use_n && !ctx->tm_has_normal);
-    const int from = ctx->tm_cur, to = ctx->has_temporal ? from ^ 1 : from;             // the two sets take turns
+    const bool history = rt_temporal_plan::history_usable(ctx->tm_valid, use_n, ctx->tm_has_normal);
+    const int from = ctx->tm_cur, to = rt_temporal_plan::turn(ctx->has_temporal, from);             // the two sets take turns
     TemporalArgs a{};
     a.image = ctx->d_image; a.position = ctx->d_aov[2]; a.normal = with_normal ? ctx->d_aov[1] : nullptr;
     a.hist_prev = ctx->d_tm_hist[from]; a.position_prev = ctx->d_tm_position[from]; a.normal_prev = ctx->d_tm_normal[from];
@@ -2127,49 +2129,44 @@ extern "C" int rtgl_temporal_reset(rtgl_context *ctx)
     return RTGL_OK;
 }
 
+static const char *const kNoTemporal = ": no rtgl_temporal_accumulate call has succeeded on this context";
+static const char *const kNoTemporalMoments = ": the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")";
+
 extern "C" int rtgl_read_temporal_f32(rtgl_context *ctx, float *rgba)
 {
     ENTER(ctx);
-    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
-    if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_f32: no rtgl_temporal_accumulate call has succeeded on this context");
-    return read_rows(ctx, rgba, ctx->d_tm_hist[ctx->tm_cur], 16);
+    return read_plane(ctx, rgba, "rgba is NULL", ctx->has_temporal, ctx->d_tm_hist[ctx->tm_cur], 16, "rtgl_read_temporal_f32", kNoTemporal);
 }
 
 extern "C" void *rtgl_device_temporal(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_temporal) { ctx->error = "rtgl_device_temporal: no rtgl_temporal_accumulate call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_tm_hist[ctx->tm_cur];
+    return ctx ? device_plane(ctx, ctx->has_temporal, ctx->d_tm_hist[ctx->tm_cur], "rtgl_device_temporal", kNoTemporal) : nullptr;
 }
 
 extern "C" int rtgl_read_temporal_moments_f32(rtgl_context *ctx, float *rgba)
 {
     ENTER(ctx);
-    if (!rgba) return fail(ctx, RTGL_ERR_INVALID, "rgba is NULL");
-    if (!ctx->tm_moments) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_temporal_moments_f32: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")");
-    return read_rows(ctx, rgba, ctx->d_tm_moments[ctx->tm_cur], 16);
+    return read_plane(ctx, rgba, "rgba is NULL", ctx->tm_moments != 0, ctx->d_tm_moments[ctx->tm_cur], 16, "rtgl_read_temporal_moments_f32", kNoTemporalMoments);
 }
 
 extern "C" void *rtgl_device_temporal_moments(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->tm_moments) { ctx->error = "rtgl_device_temporal_moments: the latest successful rtgl_temporal_accumulate on this context stored no moments (option \"temporal_moments\")"; return nullptr; }
-    return (void *)ctx->d_tm_moments[ctx->tm_cur];
+    return ctx ? device_plane(ctx, ctx->tm_moments != 0, ctx->d_tm_moments[ctx->tm_cur], "rtgl_device_temporal_moments", kNoTemporalMoments) : nullptr;
 }
 
 // ---- rtgl_temporal_clip: the latest history clamped into the current frame's neighbourhood colour box (rt_temporal_clip.hpp) --------
 extern "C" int rtgl_temporal_clip_defaults(rtgl_temporal_clip_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->sigma_scale = 2.0f; out->clip_history = 3.0f; out->sigma_normal = 0.3f; out->sigma_position = 0.05f;
+    const rt_temporal_plan::ClipParams p = rt_temporal_plan::default_clip_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
 template <bool kNormal, bool kPosition>
 static void launch_temporal_clip(rtgl_context *ctx, const TemporalClipArgs &a, bool moments)
 {
-    const dim3 grid((unsigned)((a.width + 63) / 64), (unsigned)((a.height + 3) / 4));
+    const dim3 grid(rt_temporal_plan::grid_x(a.width), rt_temporal_plan::grid_y(a.height));
     if (moments) hipLaunchKernelGGL((temporal_clip_kernel<kNormal, kPosition, true>), grid, dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((temporal_clip_kernel<kNormal, kPosition, false>), grid, dim3(256), 0, ctx->stream, a);
 }
@@ -2177,25 +2174,17 @@ static void launch_temporal_clip(rtgl_context *ctx, const TemporalClipArgs &a, b
 extern "C" int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_params *params)
 {
     ENTER(ctx);
-    rtgl_temporal_clip_params P;
-    rtgl_temporal_clip_defaults(&P);
-    if (params) P = *params;
-    if (!std::isfinite(P.sigma_scale) || !std::isfinite(P.clip_history) || !std::isfinite(P.sigma_normal) || !std::isfinite(P.sigma_position))
-        return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: sigma_scale, clip_history and the sigmas must be finite (a sigma <= 0 switches its term off)");
-    if (!(P.sigma_scale > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: sigma_scale must be > 0");
-    if (!(P.clip_history >= 1.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: clip_history must be >= 1");
-    if (P.flags) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: no flag bits are defined");
-    if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(ctx, RTGL_ERR_INVALID, "rtgl_temporal_clip: reserved fields must be 0");
+    rt_temporal_plan::ClipParams P = rt_temporal_plan::default_clip_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_temporal_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_temporal_clip: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a tiled or multi-device context holds strips that lack their neighbours' rows, and has no history (rtgl_temporal_accumulate is out of scope there): "
                                          "render on a single-device context");
-    if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no rtgl_temporal_accumulate call has succeeded on this context");
+    if (const char *why = rt_temporal_plan::clip_refused(ctx->has_temporal)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_temporal_clip: ") + why);
+    if (const char *why = rt_temporal_plan::planes_refused(rt_temporal_plan::planes_needed(P), (uint32_t)ctx->opt.aov, ctx->aov_restart, ctx->aov_n, true))
+        return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_temporal_clip: ") + why);
+    if (const char *why = rt_temporal_plan::pixels_refused(rt_temporal_plan::pixels(ctx->local_rows, ctx->width))) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_temporal_clip: ") + why);
     const bool use_n = P.sigma_normal > 0.0f, use_p = P.sigma_position > 0.0f;
-    const int need = RTGL_AOV_POSITION | (use_n ? RTGL_AOV_NORMAL : 0);
-    if (need & ~ctx->opt.aov) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: a first-hit plane this call needs is not enabled (option \"aov\": position always, for the kind test; normal for sigma_normal > 0)");
-    if (ctx->aov_restart || ctx->aov_n == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: no frame has been rendered since the first-hit planes last restarted");
-    const size_t n = (size_t)ctx->local_rows * ctx->width;
-    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_temporal_clip: this context holds no pixels");
     TemporalClipArgs a{};
     a.image = ctx->d_image; a.normal = use_n ? ctx->d_aov[1] : nullptr; a.position = ctx->d_aov[2];
     a.hist = ctx->d_tm_hist[ctx->tm_cur];
@@ -2214,62 +2203,52 @@ extern "C" int rtgl_temporal_clip(rtgl_context *ctx, const rtgl_temporal_clip_pa
 }
 
 // ---- rtgl_tonemap: the display transform, float buffer -> RGBA8 (rt_tonemap.hpp) ----------------------------------------------------
+static_assert(sizeof(rtgl_tonemap_params) == sizeof(rt_tonemap_plan::Params) && offsetof(rtgl_tonemap_params, adapt) == offsetof(rt_tonemap_plan::Params, adapt)
+              && offsetof(rtgl_tonemap_params, low_permille) == offsetof(rt_tonemap_plan::Params, low_permille)
+              && rt_tonemap_plan::kSourceImage == (uint32_t)RTGL_TONEMAP_SOURCE_IMAGE && rt_tonemap_plan::kSourceDenoised == (uint32_t)RTGL_TONEMAP_SOURCE_DENOISED
+              && rt_tonemap_plan::kSourceTemporal == (uint32_t)RTGL_TONEMAP_SOURCE_TEMPORAL && rt_tonemap_plan::kOpLinear == (uint32_t)RTGL_TONEMAP_LINEAR
+              && rt_tonemap_plan::kOpReinhard == (uint32_t)RTGL_TONEMAP_REINHARD && rt_tonemap_plan::kOpAces == (uint32_t)RTGL_TONEMAP_ACES
+              && rt_tonemap_plan::kFlagAuto == (uint32_t)RTGL_TONEMAP_AUTO_EXPOSURE && rt_tonemap_plan::kBins == kToneBins && rt_tonemap_plan::kSetWords == kToneWords
+              && rt_tonemap_plan::kExposureWord == kToneExposureWord && rt_tonemap_plan::kStateWords == kToneStateWords, "the layouts of the header and of the kernels");
+
 extern "C" int rtgl_tonemap_defaults(rtgl_tonemap_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->source = RTGL_TONEMAP_SOURCE_IMAGE; out->op = RTGL_TONEMAP_REINHARD; out->flags = RTGL_TONEMAP_AUTO_EXPOSURE;
-    out->exposure = 1.0f; out->key = 0.18f; out->white = 4.0f; out->adapt = 1.0f;
-    out->exposure_min = 0x1p-16f; out->exposure_max = 0x1p16f;
-    out->low_permille = 100u; out->high_permille = 20u;
+    const rt_tonemap_plan::Params p = rt_tonemap_plan::default_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
 extern "C" int rtgl_tonemap(rtgl_context *ctx, const rtgl_tonemap_params *params)
 {
     ENTER(ctx);
-    rtgl_tonemap_params P;
-    rtgl_tonemap_defaults(&P);
-    if (params) P = *params;
-    if (P.source > RTGL_TONEMAP_SOURCE_TEMPORAL) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: source must be 0 (image), 1 (denoised) or 2 (temporal history)");
-    if (P.op > RTGL_TONEMAP_ACES) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: op must be 0 (linear), 1 (Reinhard with white point) or 2 (ACES fit)");
-    if (P.flags & ~(uint32_t)RTGL_TONEMAP_AUTO_EXPOSURE) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: only flag bit 0 (auto exposure) is defined");
-    for (float v : { P.exposure, P.key, P.white, P.adapt, P.exposure_min, P.exposure_max })
-        if (!std::isfinite(v) || !(v > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: exposure, key, white, adapt, exposure_min and exposure_max must be finite and > 0");
-    if (P.adapt > 1.0f) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: adapt must be in (0, 1]");
-    if (P.exposure_min > P.exposure_max) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: exposure_min must not exceed exposure_max");
-    if ((uint64_t)P.low_permille + (uint64_t)P.high_permille >= 1000u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: low_permille + high_permille must be < 1000");
-    for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_tonemap: reserved fields must be 0");
+    rt_tonemap_plan::Params P = rt_tonemap_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_tonemap_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_tonemap: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: a tiled or multi-device context holds strips, and the exposure is a property of the whole picture: render on a single-device context");
-    const float4 *src = ctx->d_image;
-    if (P.source == RTGL_TONEMAP_SOURCE_DENOISED) {
-        if (!ctx->has_denoised) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: source 1, and no rtgl_denoise or rtgl_denoise_guided call has succeeded on this context");
-        src = ctx->d_denoised;
-    } else if (P.source == RTGL_TONEMAP_SOURCE_TEMPORAL) {
-        if (!ctx->has_temporal) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: source 2, and no rtgl_temporal_accumulate call has succeeded on this context");
-        src = ctx->d_tm_hist[ctx->tm_cur];
-    }
+    if (const char *why = rt_tonemap_plan::source_refused(P.source, ctx->has_denoised, ctx->has_temporal)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_tonemap: ") + why);
+    const float4 *src = P.source == RTGL_TONEMAP_SOURCE_DENOISED ? ctx->d_denoised : P.source == RTGL_TONEMAP_SOURCE_TEMPORAL ? ctx->d_tm_hist[ctx->tm_cur] : ctx->d_image;
     const size_t n = (size_t)ctx->local_rows * ctx->width;
-    if (n == 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_tonemap: this context holds no pixels");
-    RCCHK(buf_ensure(ctx, ctx->d_display, n * 4));
+    if (const char *why = rt_tonemap_plan::pixels_refused(n)) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_tonemap: ") + why);
+    RCCHK(buf_ensure(ctx, ctx->d_display, rt_tonemap_plan::display_bytes(n)));
     if (!ctx->d_tone_state) {
         RCCHK(buf_alloc(ctx, ctx->d_tone_state, kToneStateWords * 4));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_tone_state, 0, kToneStateWords * 4, ctx->stream));      // both sets start clean; from here on the solve keeps them so
     }
-    const bool automatic = (P.flags & RTGL_TONEMAP_AUTO_EXPOSURE) != 0;
-    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)ctx->n_cus * 8);
+    const bool automatic = rt_tonemap_plan::automatic(P);
+    const unsigned blocks = rt_tonemap_plan::blocks(n, ctx->n_cus);
     if (automatic) {
-        const int set = ctx->tone_set;
+        const int set = ctx->tone.set;
         hipLaunchKernelGGL(tonemap_histogram_kernel, dim3(blocks), dim3(256), 0, ctx->stream, src, n, ctx->d_tone_state + set * kToneWords);
         HIPCHK(ctx, hipGetLastError());
         TonemapSolveArgs s{};
-        s.state = ctx->d_tone_state; s.set = set; s.use_prev = ctx->tone_prev ? 1u : 0u;
+        s.state = ctx->d_tone_state; s.set = set; s.use_prev = ctx->tone.prev ? 1u : 0u;
         s.low_permille = P.low_permille; s.high_permille = P.high_permille;
         s.exposure = P.exposure; s.key = P.key; s.adapt = P.adapt; s.exposure_min = P.exposure_min; s.exposure_max = P.exposure_max;
         hipLaunchKernelGGL(tonemap_solve_kernel, dim3(1), dim3(64), 0, ctx->stream, s);
         HIPCHK(ctx, hipGetLastError());
-        ctx->tone_set = set ^ 1; ctx->tone_hist_set = set; ctx->tone_prev = true;
+        ctx->tone.after_auto_call();
     }
     TonemapMapArgs a{};
     a.src = src; a.display = reinterpret_cast<uint32_t *>(ctx->d_display); a.n = n;
@@ -2286,7 +2265,7 @@ extern "C" int rtgl_tonemap(rtgl_context *ctx, const rtgl_tonemap_params *params
 extern "C" int rtgl_tonemap_reset(rtgl_context *ctx)
 {
     ENTER(ctx);
-    ctx->tone_prev = false;                               // (the display buffer, the histogram and the exposure stay readable)
+    ctx->tone.prev = false;                             // (the display buffer, the histogram and the exposure stay readable)
     return RTGL_OK;
 }
 
@@ -2305,9 +2284,7 @@ extern "C" int rtgl_read_display_u8(rtgl_context *ctx, uint8_t *rgba, int flip)
 
 extern "C" void *rtgl_device_display(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_display) { ctx->error = "rtgl_device_display: no rtgl_tonemap call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_display;
+    return ctx ? device_plane(ctx, ctx->has_display, ctx->d_display, "rtgl_device_display", ": no rtgl_tonemap call has succeeded on this context") : nullptr;
 }
 
 extern "C" int rtgl_read_tonemap_exposure(rtgl_context *ctx, float *exposure)
@@ -2325,9 +2302,9 @@ extern "C" int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256]
 {
     ENTER(ctx);
     if (!hist) return fail(ctx, RTGL_ERR_INVALID, "hist is NULL");
-    if (ctx->tone_hist_set < 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_tonemap_histogram: no rtgl_tonemap call with auto exposure has succeeded on this context");
+    if (ctx->tone.hist_set < 0) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_tonemap_histogram: no rtgl_tonemap call with auto exposure has succeeded on this context");
     uint32_t words[kToneWords];
-    HIPCHK(ctx, hipMemcpyAsync(words, ctx->d_tone_state + ctx->tone_hist_set * kToneWords, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(words, ctx->d_tone_state + ctx->tone.hist_set * kToneWords, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(hist, words, kToneBins * 4);
     if (ignored) *ignored = words[kToneBins];
@@ -2335,62 +2312,51 @@ extern "C" int rtgl_read_tonemap_histogram(rtgl_context *ctx, uint32_t hist[256]
 }
 
 // ---- rtgl_error_estimate: the noise level of the accumulation image and the stop rule (rt_error.hpp) -----------------------------------
+static_assert(sizeof(rtgl_error_params) == sizeof(rt_error_plan::Params) && offsetof(rtgl_error_params, first_frames) == offsetof(rt_error_plan::Params, first_frames)
+              && offsetof(rtgl_error_params, flags) == offsetof(rt_error_plan::Params, flags) && rt_error_plan::kFlagKeep == (uint32_t)RTGL_ERROR_KEEP_SNAPSHOT
+              && rt_error_plan::kInvalid == RTGL_ERR_INVALID && rt_error_plan::kState == RTGL_ERR_STATE && rt_error_plan::kTile == (uint32_t)kErrTile
+              && rt_error_plan::kSummaryBytes == kErrSummaryWords * 4 && rt_error_plan::kRecordBytes == sizeof(uint4), "the layouts of the header and of the kernels");
+
 extern "C" int rtgl_error_defaults(rtgl_error_params *out)
 {
     if (!out) return RTGL_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->threshold = 0.05f; out->floor = 0.01f; out->quantile_permille = 950u; out->first_frames = 1;
+    const rt_error_plan::Params p = rt_error_plan::default_params();
+    memcpy(out, &p, sizeof p);
     return RTGL_OK;
 }
 
 extern "C" int rtgl_error_estimate(rtgl_context *ctx, const rtgl_error_params *params)
 {
     ENTER(ctx);
-    rtgl_error_params P;
-    rtgl_error_defaults(&P);
-    if (params) P = *params;
-    for (float v : { P.threshold, P.floor })
-        if (!std::isfinite(v) || !(v > 0.0f)) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: threshold and floor must be finite and > 0");
-    if (P.quantile_permille < 1u || P.quantile_permille > 1000u) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: quantile_permille must be in 1..1000");
-    if (P.first_frames < 0) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: first_frames must be >= 0");
-    if (P.flags & ~(uint32_t)RTGL_ERROR_KEEP_SNAPSHOT) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: only flag bit 0 (keep the snapshot) is defined");
-    for (uint32_t r : P.reserved) if (r) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: reserved fields must be 0");
+    rt_error_plan::Params P = rt_error_plan::default_params();
+    if (params) memcpy(&P, params, sizeof P);
+    if (const char *why = rt_error_plan::invalid(P)) return fail(ctx, RTGL_ERR_INVALID, std::string("rtgl_error_estimate: ") + why);
     if (!ctx->parts.empty() || ctx->world > 1)
         return fail(ctx, RTGL_ERR_STATE, "rtgl_error_estimate: a tiled or multi-device context holds strips, and the estimate is of the whole picture (out of scope): render on a single-device context");
-    if (!ctx->err_rendered) return fail(ctx, RTGL_ERR_STATE, "rtgl_error_estimate: no frame has been rendered on this context");
-    const int64_t fn = ctx->err_fn, n = fn + 1 - (int64_t)P.first_frames;
-    if (n < 1) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: the latest frame's `frames` is below first_frames: the image would hold no frame");
-    const int fw = ctx->width / 8 * 8, fh = ctx->height / 8 * 8;
-    if ((uint64_t)fw * (uint64_t)fh > 0xFFFFFFFFull) return fail(ctx, RTGL_ERR_INVALID, "rtgl_error_estimate: the footprint does not fit 32-bit counts");
-    const unsigned tx = (unsigned)((ctx->width + kErrTile - 1) / kErrTile), ty = (unsigned)((ctx->height + kErrTile - 1) / kErrTile);
-    RCCHK(buf_ensure(ctx, ctx->d_err_tiles, (size_t)tx * ty * sizeof(uint4)));
-    RCCHK(buf_ensure(ctx, ctx->d_err_summary, kErrSummaryWords * 4));
-    RCCHK(buf_ensure(ctx, ctx->d_err_snapshot, (size_t)ctx->height * ctx->width * sizeof(float)));
-    // a snapshot of an earlier moment of THIS accumulation, counted the same way
-    const bool usable = ctx->err_snap_epoch == ctx->err_epoch && fn > (int64_t)ctx->err_fm && P.first_frames == ctx->err_first;
-    const bool keep = usable && (P.flags & RTGL_ERROR_KEEP_SNAPSHOT);
+    const rt_error_plan::Refusal no = rt_error_plan::refused(ctx->err, P, ctx->width, ctx->height);
+    if (no.why) return fail(ctx, no.code, std::string("rtgl_error_estimate: ") + no.why);
+    const unsigned tx = rt_error_plan::tiles_along(ctx->width), ty = rt_error_plan::tiles_along(ctx->height);
+    RCCHK(buf_ensure(ctx, ctx->d_err_tiles, rt_error_plan::record_bytes(ctx->width, ctx->height)));
+    RCCHK(buf_ensure(ctx, ctx->d_err_summary, rt_error_plan::kSummaryBytes));
+    RCCHK(buf_ensure(ctx, ctx->d_err_snapshot, rt_error_plan::snapshot_bytes(ctx->width, ctx->height)));
+    const rt_error_plan::Plan q = rt_error_plan::plan(ctx->err, P);
     ErrorTilesArgs a{};
     a.image = ctx->d_image; a.snapshot = ctx->d_err_snapshot; a.tiles = ctx->d_err_tiles;
-    a.width = ctx->width; a.fw = fw; a.fh = fh;
+    a.width = ctx->width; a.fw = (int)rt_error_plan::footprint_side(ctx->width); a.fh = (int)rt_error_plan::footprint_side(ctx->height);
     a.floor_ = P.floor; a.threshold = P.threshold;
+    a.g_n = q.g_n; a.g_m = q.g_m; a.c = q.c;
     ErrorSolveArgs s{};
-    s.tiles = ctx->d_err_tiles; s.summary = ctx->d_err_summary; s.n_tiles = tx * ty; s.valid = usable ? 1u : 0u;
-    s.footprint = (uint32_t)((uint64_t)fw * (uint64_t)fh); s.quantile_permille = P.quantile_permille;
-    if (usable) {
-        const int64_t m = (int64_t)ctx->err_fm + 1 - (int64_t)P.first_frames;      // (>= 1: the call that took the snapshot checked it)
-        a.g_n = (float)((double)(fn + 1) / (double)n);
-        a.g_m = (float)((double)((int64_t)ctx->err_fm + 1) / (double)m);
-        a.c = (float)((double)m / (double)(n - m));
-        s.c = a.c; s.frames_now = (int32_t)fn; s.frames_snapshot = ctx->err_fm;
-    }
+    s.tiles = ctx->d_err_tiles; s.summary = ctx->d_err_summary; s.n_tiles = tx * ty; s.valid = q.usable ? 1u : 0u;
+    s.footprint = (uint32_t)rt_error_plan::footprint(ctx->width, ctx->height); s.quantile_permille = P.quantile_permille;
+    s.c = q.c; s.frames_now = q.frames_now; s.frames_snapshot = q.frames_snapshot;
     const dim3 grid(tx, ty);
-    if (!usable) hipLaunchKernelGGL((error_tiles_kernel<false, false>), grid, dim3(256), 0, ctx->stream, a);
-    else if (keep) hipLaunchKernelGGL((error_tiles_kernel<true, true>), grid, dim3(256), 0, ctx->stream, a);
+    if (!q.usable) hipLaunchKernelGGL((error_tiles_kernel<false, false>), grid, dim3(256), 0, ctx->stream, a);
+    else if (q.keep) hipLaunchKernelGGL((error_tiles_kernel<true, true>), grid, dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((error_tiles_kernel<true, false>), grid, dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(error_solve_kernel, dim3(1), dim3(256), 0, ctx->stream, s);
     HIPCHK(ctx, hipGetLastError());
-    if (!keep) { ctx->err_snap_epoch = ctx->err_epoch; ctx->err_fm = (int32_t)fn; ctx->err_first = P.first_frames; }
+    rt_error_plan::taken(ctx->err, P, q.keep);
     ctx->has_error = true;
     return RTGL_OK;
 }
@@ -2398,7 +2364,7 @@ extern "C" int rtgl_error_estimate(rtgl_context *ctx, const rtgl_error_params *p
 extern "C" int rtgl_error_reset(rtgl_context *ctx)
 {
     ENTER(ctx);
-    ++ctx->err_epoch;                                     // (the summary and the tile records of the latest call stay readable)
+    rt_error_plan::drop(ctx->err);                        // (the summary and the tile records of the latest call stay readable)
     return RTGL_OK;
 }
 
@@ -2418,7 +2384,7 @@ extern "C" int rtgl_read_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, 
     ENTER(ctx);
     if (!tiles) return fail(ctx, RTGL_ERR_INVALID, "tiles is NULL");
     if (!ctx->has_error) return fail(ctx, RTGL_ERR_STATE, "rtgl_read_error_tiles: no rtgl_error_estimate call has succeeded on this context");
-    const uint32_t nx = (uint32_t)((ctx->width + kErrTile - 1) / kErrTile), ny = (uint32_t)((ctx->height + kErrTile - 1) / kErrTile);
+    const uint32_t nx = rt_error_plan::tiles_along(ctx->width), ny = rt_error_plan::tiles_along(ctx->height);
     HIPCHK(ctx, hipMemcpyAsync(tiles, ctx->d_err_tiles, (size_t)nx * ny * sizeof(rtgl_error_tile), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (tx) *tx = nx;
@@ -2428,9 +2394,7 @@ extern "C" int rtgl_read_error_tiles(rtgl_context *ctx, rtgl_error_tile *tiles, 
 
 extern "C" void *rtgl_device_error_tiles(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_error) { ctx->error = "rtgl_device_error_tiles: no rtgl_error_estimate call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->d_err_tiles;
+    return ctx ? device_plane(ctx, ctx->has_error, ctx->d_err_tiles, "rtgl_device_error_tiles", ": no rtgl_error_estimate call has succeeded on this context") : nullptr;
 }
 
 // ---- adaptive sampling: masked frames over the tiles that are still noisy (rt_adaptive.hpp, rt_adaptive_plan.hpp) -------------------------
@@ -2562,7 +2526,7 @@ extern "C" int rtgl_adaptive_begin(rtgl_context *ctx, const rtgl_adaptive_params
     // the image as rtgl_clear_image leaves it
     HIPCHK(ctx, hipMemsetAsync(ctx->d_image, 0, (size_t)ctx->local_rows * ctx->width * 16, ctx->stream));
     ctx->aov_restart = true;
-    ++ctx->err_epoch;
+    rt_error_plan::drop(ctx->err);
     ctx->ad_params = P; ctx->has_adaptive = true;
     return tile_session_open(ctx, ctx->ad);
 }
@@ -2610,7 +2574,7 @@ extern "C" int rtgl_adaptive_frame(rtgl_context *ctx)
 {
     ENTER(ctx);
     RCCHK(masked_frame_refused(ctx, ctx->ad, "rtgl_adaptive_frame", kNoAdaptiveSession, "rtgl_set_frame_params has not been called"));
-    ++ctx->err_epoch;                                     // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
+    rt_error_plan::drop(ctx->err);                        // (rtgl_error_estimate: the image is no longer one accumulation of counted frames)
     if (ctx->ad.blocks.empty()) return RTGL_OK;
     RCCHK(masked_frame(ctx, ctx->ad.d_samples, ctx->ad.d_lists, (uint32_t)ctx->ad.blocks.size() * 64u));
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
@@ -2663,9 +2627,7 @@ extern "C" int rtgl_read_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_tile *t
 
 extern "C" void *rtgl_device_adaptive_tiles(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->has_adaptive) { ctx->error = "rtgl_device_adaptive_tiles: no rtgl_adaptive_begin call has succeeded on this context"; return nullptr; }
-    return (void *)ctx->ad.d_records;
+    return ctx ? device_plane(ctx, ctx->has_adaptive, ctx->ad.d_records, "rtgl_device_adaptive_tiles", ": no rtgl_adaptive_begin call has succeeded on this context") : nullptr;
 }
 
 // ---- robust accumulation: K bucket means and a Gini-trimmed resolve (rt_robust.hpp, rt_robust_plan.hpp) -----------------------------------
@@ -2740,7 +2702,7 @@ extern "C" int rtgl_robust_resolve(rtgl_context *ctx, const rtgl_robust_resolve_
     if (ctx->rb_N == 0u) return fail(ctx, RTGL_ERR_STATE, "rtgl_robust_resolve: no frame has been accumulated since rtgl_robust_begin");
     const bool to_image = P.dest == rt_robust_plan::kDestImage;
     if (to_image) {                                       // on the host, what rtgl_write_image_f32 does
-        ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
+        rt_error_plan::drop(ctx->err);                    // (rtgl_error_estimate: another image, the snapshot is dropped)
         ctx->ad.active = false;                           // (adaptive sampling: ... and the session ends)
     }
     RobustResolveArgs a{};
@@ -2865,9 +2827,7 @@ extern "C" int rtgl_read_robust_error_tiles(rtgl_context *ctx, rtgl_error_tile *
 
 extern "C" void *rtgl_device_robust_error_tiles(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->rb_active || !ctx->has_rb_error) { ctx->error = std::string("rtgl_device_robust_error_tiles") + kNoRobustError; return nullptr; }
-    return (void *)ctx->d_rbe_tiles;
+    return ctx ? device_plane(ctx, ctx->rb_active && ctx->has_rb_error, ctx->d_rbe_tiles, "rtgl_device_robust_error_tiles", kNoRobustError) : nullptr;
 }
 
 // ---- a robust adaptive session: masked frames folded into per-tile bucket means (rt_robust_tiles.hpp, rt_robust_tiles_plan.hpp) ------------
@@ -2976,7 +2936,7 @@ extern "C" int rtgl_robust_adaptive_resolve(rtgl_context *ctx, const rtgl_robust
     if (!ctx->ra.active) return fail(ctx, RTGL_ERR_STATE, std::string("rtgl_robust_adaptive_resolve") + kNoRobustAdaptiveSession);
     const bool to_image = P.dest == rt_robust_plan::kDestImage;
     if (to_image) {                                       // on the host, what rtgl_robust_resolve with dest IMAGE does
-        ++ctx->err_epoch;                                 // (rtgl_error_estimate: another image, the snapshot is dropped)
+        rt_error_plan::drop(ctx->err);                    // (rtgl_error_estimate: another image, the snapshot is dropped)
         ctx->ad.active = false;                           // (adaptive sampling: ... and the session ends)
     }
     const rt_adaptive_plan::Shape sh = rt_adaptive_plan::shape(ctx->width, ctx->height);
@@ -3032,9 +2992,7 @@ extern "C" int rtgl_read_robust_adaptive_tiles(rtgl_context *ctx, rtgl_adaptive_
 
 extern "C" void *rtgl_device_robust_adaptive_tiles(rtgl_context *ctx)
 {
-    if (!ctx) return nullptr;
-    if (!ctx->ra.active) { ctx->error = std::string("rtgl_device_robust_adaptive_tiles") + kNoRobustAdaptiveSession; return nullptr; }
-    return (void *)ctx->ra.d_records;
+    return ctx ? device_plane(ctx, ctx->ra.active, ctx->ra.d_records, "rtgl_device_robust_adaptive_tiles", kNoRobustAdaptiveSession) : nullptr;
 }
 
 // ---- rtgl_robust_denoise: the session's resolve and the guided filter in one call (rt_bucket_guide.hpp, rt_bucket_guide_plan.hpp) -------------

@@ -63,6 +63,7 @@ def test_defaults_are_the_documented_ones_and_need_no_device(rt):
 
 
 def test_denoise_calls_reject_a_null_context(rt):
+    """a NULL context is refused before a single field of the record is read: the rules themselves are checked by tests/test_post_plans.py"""
     lib = rt.host.load_library()
     buf = np.zeros(64, np.float32)
     p = rt.host.CDenoiseParams()

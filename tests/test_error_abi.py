@@ -1,6 +1,6 @@
 """The error estimate (rtgl_error_estimate, include/rtgl_amd.h) at the ABI level, without a GPU: the header, the Python binding and the
 library agree on the entry points and on the three layouts; header, binding, facade, library and mirror state the same defaults; the calls
-reject a NULL context and invalid arguments before touching a device; a C99 program compiles against the header and the facade's methods
+reject a NULL context, whatever the record, before touching a device (the record's rules: tests/test_post_plans.py); a C99 program compiles against the header and the facade's methods
 with the host compilers; and the kernels spill nothing and hold the LDS they were designed for (compiler resource report)."""
 import ctypes as C
 import os
@@ -114,6 +114,7 @@ def invalid_blocks(rt):
 
 
 def test_calls_reject_a_null_context_and_null_outputs(rt):
+    """a NULL context is refused before a single field of the record is read: the rules themselves are checked by tests/test_post_plans.py"""
     lib = rt.host.load_library()
     p = rt.host.CErrorParams()
     lib.rtgl_error_defaults(C.byref(p))

@@ -73,6 +73,7 @@ def test_header_binding_facade_and_mirror_state_the_same_defaults(rt):
 
 
 def test_calls_reject_a_null_context(rt):
+    """a NULL context is refused before a single field of the record is read: the rules themselves are checked by tests/test_post_plans.py"""
     lib = rt.host.load_library()
     buf = np.zeros(64, np.float32)
     p = rt.host.CTemporalParams()

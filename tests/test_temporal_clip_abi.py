@@ -1,6 +1,6 @@
 """The temporal clip (rtgl_temporal_clip, include/rtgl_amd.h) at the ABI level, without a GPU: the header, the Python binding and the
 library agree on the entry points and on the parameter block; header, binding, facade and mirror state the same defaults; the calls reject
-a NULL context and invalid arguments before touching a device; a C program compiles against the header and the facade's method with the
+a NULL context, whatever the record, before touching a device (the record's rules: tests/test_post_plans.py); a C program compiles against the header and the facade's method with the
 host compiler; and the eight kernel instances spill nothing and hold the LDS they were designed for (compiler resource report; hipcc
 cross-compiles)."""
 import ctypes as C
@@ -74,6 +74,7 @@ def test_header_binding_facade_and_mirror_state_the_same_defaults(rt):
 
 
 def test_calls_reject_a_null_context(rt):
+    """a NULL context is refused before a single field of the record is read: the rules themselves are checked by tests/test_post_plans.py"""
     lib = rt.host.load_library()
     p = rt.host.CTemporalClipParams()
     lib.rtgl_temporal_clip_defaults(C.byref(p))

@@ -1,6 +1,6 @@
 """The display transform (rtgl_tonemap, include/rtgl_amd.h) at the ABI level, without a GPU: the header, the Python binding and the library
 agree on the entry points and on the parameter block; header, binding, facade and mirror state the same defaults; the calls reject a NULL
-context and invalid arguments before touching a device; a C program compiles against the header and the facade's methods with the host
+context, whatever the record, before touching a device (the record's rules: tests/test_post_plans.py); a C program compiles against the header and the facade's methods with the host
 compiler; and the kernels spill nothing and hold the LDS they were designed for (compiler resource report; hipcc cross-compiles)."""
 import ctypes as C
 import os
@@ -109,6 +109,7 @@ def invalid_blocks(rt):
 
 
 def test_calls_reject_a_null_context_and_null_outputs(rt):
+    """a NULL context is refused before a single field of the record is read: the rules themselves are checked by tests/test_post_plans.py"""
     lib = rt.host.load_library()
     p = rt.host.CTonemapParams()
     lib.rtgl_tonemap_defaults(C.byref(p))
