@@ -358,6 +358,17 @@ public:
         if (!m_ctx || img.size() != (size_t)m_width * rtgl_local_rows(m_ctx) * 4) return false;      // (read_aov has said why)
         return write_pfm(path, img);
     }
+    // ---- guide pass (rtgl_guides_frame, include/rtgl_amd.h; extension): the camera rays' first hits folded into the enabled planes and
+    // nothing else -- no image, no RNG state, no session ends.  guides_frame(): one pass with the uniforms of a frame (one rand(), like every
+    // frame; frames and reset_flag are ignored, the frame count is not advanced and a pending reset_buffer() stays pending).
+    // render_guides(n): n passes, returns how many the library took.  Prints and returns false / stops on failure.
+    bool guides_frame() { return masked_frame(rtgl_guides_frame); }
+    long render_guides(long n = 1)
+    {
+        long done = 0;
+        while (done < n && guides_frame()) ++done;
+        return done;
+    }
     // ---- denoiser (rtgl_denoise, include/rtgl_amd.h; extension): an edge-avoiding a-trous filter over the image as it stands, guided by the
     // first-hit planes -- set_aov(RTGL_AOV_ALBEDO | RTGL_AOV_NORMAL | RTGL_AOV_POSITION) before rendering.  nullptr: the documented defaults.
     // The result is a snapshot in a buffer of its own; the accumulation image is not touched.  Prints and returns false on failure.

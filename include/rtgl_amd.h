@@ -198,6 +198,30 @@ int rtgl_read_rng_state(rtgl_context *ctx, uint32_t *xyzw);    /* per local pixe
 int rtgl_read_aov(rtgl_context *ctx, int plane, void *out);
 void *rtgl_device_aov(rtgl_context *ctx, int plane);
 
+/* -- guide pass: the first-hit planes without a frame.  rtgl_guides_frame traces, for every pixel of the dispatch footprint, the camera ray
+ * of sample 0 that rtgl_render_frame would draw from the current frame parameters, and folds its first hit into the enabled planes.
+ *   The ray.  Camera, random, depth of field, background and environment come from rtgl_set_frame_params; frames, reset_flag, samples and
+ *   max_bounce are ignored, and the ray is traced even with max_bounce == 0 (where a frame contributes a miss with albedo 0).
+ *   The hit is chosen exactly as bounce 0 of shading chooses it (a mesh wins a tie with a sphere; among triangles the lowest visit index);
+ *   a miss records the background or the cube-map value.  The records are those of the planes above, bit for bit what a frame of the same
+ *   parameters writes, whatever option "kernel" says: a scene without triangles takes one launch, a scene with triangles the lean ray
+ *   generation, the intersect stage of bounce 0 (kernel 2's for "kernel" = 2, otherwise kernel 4's with fresh keep bits) and that launch.
+ *   The fold is the planes' own: n = 1 if a restart is pending (after rtgl_clear_image, after "aov" is set, after
+ *   rtgl_adaptive_begin), otherwise n + 1; v = (x + prev * (n - 1)) / n in float32, n == 1 stores x exactly; the ids plane
+ *   holds this pass's ids.  The pass clears the pending restart and counts as a frame since the planes restarted for every call that asks
+ *   for one (rtgl_denoise, rtgl_denoise_guided, rtgl_robust_denoise, rtgl_temporal_accumulate, rtgl_temporal_clip); a later rtgl_render_frame
+ *   without reset_flag continues the same n.
+ *   Nothing else is written: not the image, the sample and bucket buffers, the RNG states, the counters, the denoised, temporal and display
+ *   buffers, nor the snapshot of rtgl_error_estimate, and the pass ends no session -- adaptive, robust and robust adaptive sessions stay open,
+ *   so masked frames (which write no planes) and the denoisers can be combined, and the guides of a session can be averaged.  The ray counts
+ *   the frame path sizes its grids by stay as they are, and the kept camera bits are neither taken nor dropped: every later frame is
+ *   bit-identical to the frame of a context that never made the call.  rtgl_last_frame_ms covers the pass.
+ * Frames a batching context holds are submitted first; the call enqueues on the context's stream and returns.  A tiled context works on its
+ * own strips.  An empty footprint (an image below 8 x 8) enqueues nothing, returns RTGL_OK and counts as a pass, as a frame does.
+ * RTGL_ERR_INVALID: ctx is NULL.  RTGL_ERR_STATE, in this order: a multi-device handle; no frame parameters; option "aov" is 0.  A refused
+ * call moves neither the planes nor n. */
+int rtgl_guides_frame(rtgl_context *ctx);
+
 /* -- denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the accumulation image, guided by the first-hit planes,
  * with albedo demodulation and the compact polynomial (1 - x/4)^4 in place of exp(-x).  No reference counterpart.  What a caller of a
  * 1-spp progressive renderer needs for a usable picture after a handful of frames.  The filter uses only + - x / and compares, so it is

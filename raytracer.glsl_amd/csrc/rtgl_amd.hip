@@ -39,6 +39,8 @@
 #include "rt_robust_tiles_plan.hpp"
 #include "rt_bucket_guide.hpp"
 #include "rt_bucket_guide_plan.hpp"
+#include "rt_guides.hpp"
+#include "rt_guides_plan.hpp"
 #include "rt_node_walk.hpp"
 #include "rt_mesh_visits.hpp"
 #include "rt_buffers.hpp"
@@ -1134,6 +1136,23 @@ static void launch_intersect(rtgl_context *ctx, const SceneView &sc, uint32_t n0
 #undef RTGL_LAUNCH_ISECT
 }
 
+// kernel 2's intersect stage in the form options "wf_mode" and "wf_rays" name
+static int launch_intersect_split(rtgl_context *ctx, const SceneView &sc, uint32_t n0, uint32_t bounce)
+{
+    switch (ctx->opt.wf_mode * 10 + ctx->opt.wf_rays) {
+    case 1: launch_intersect<1, kScalar>(ctx, sc, n0, bounce); break;
+    case 2: launch_intersect<2, kScalar>(ctx, sc, n0, bounce); break;
+    case 4: launch_intersect<4, kScalar>(ctx, sc, n0, bounce); break;
+    case 8: launch_intersect<8, kScalar>(ctx, sc, n0, bounce); break;
+    case 11: launch_intersect<1, kLds>(ctx, sc, n0, bounce); break;
+    case 12: launch_intersect<2, kLds>(ctx, sc, n0, bounce); break;
+    case 14: launch_intersect<4, kLds>(ctx, sc, n0, bounce); break;
+    case 18: launch_intersect<8, kLds>(ctx, sc, n0, bounce); break;
+    default: return fail(ctx, RTGL_ERR_STATE, "unsupported wf_mode / wf_rays combination");
+    }
+    return RTGL_OK;
+}
+
 // The camera-ray bounce of one frame and the kept bits (rt_camera_keep.hpp: the rule; here: its inputs, and the buffer).  Decided once
 // per frame, before ray generation is enqueued (launch_wavefront): the scan's launch of bounce 0 and the lean camera bounce both go by
 // it.  cam = NULL: not a single frame of one sample.  A frame that is `cached` without `have_bits` rebuilds the bits (launch_intersect_solo).
@@ -1304,17 +1323,7 @@ static int launch_wavefront(rtgl_context *ctx, const SceneView &sc, const std::v
                     kev_mark(ctx);
                 } else if (sc.n_tri_visits > 0) {
                     kev_mark(ctx);
-                    switch (key) {
-                    case 1: launch_intersect<1, kScalar>(ctx, sc, n0, b); break;
-                    case 2: launch_intersect<2, kScalar>(ctx, sc, n0, b); break;
-                    case 4: launch_intersect<4, kScalar>(ctx, sc, n0, b); break;
-                    case 8: launch_intersect<8, kScalar>(ctx, sc, n0, b); break;
-                    case 11: launch_intersect<1, kLds>(ctx, sc, n0, b); break;
-                    case 12: launch_intersect<2, kLds>(ctx, sc, n0, b); break;
-                    case 14: launch_intersect<4, kLds>(ctx, sc, n0, b); break;
-                    case 18: launch_intersect<8, kLds>(ctx, sc, n0, b); break;
-                    default: return fail(ctx, RTGL_ERR_STATE, "unsupported wf_mode / wf_rays combination");
-                    }
+                    RCCHK(launch_intersect_split(ctx, sc, n0, b));
                     kev_mark(ctx);
                 }
                 // ray binning: the queue of the next bounce in (direction bin, origin cell) order, where it is long enough to pay for
@@ -1453,6 +1462,17 @@ static SceneView scene_view(const rtgl_context *ctx)
     return sc;
 }
 
+// the ids plane's mesh and triangle of every triangle visit, uploaded once per rebuild of the triangles and only while the plane is on
+static int upload_visit_ids(rtgl_context *ctx)
+{
+    if (!(ctx->opt.aov & RTGL_AOV_IDS) || !ctx->visit_ids_dirty) return RTGL_OK;
+    const size_t bytes = ctx->h_visit_tri.size() * sizeof(uint32_t);
+    RCCHK(realloc_upload(ctx, ctx->d_visit_mesh, ctx->h_visit_mesh.data(), bytes));
+    RCCHK(realloc_upload(ctx, ctx->d_visit_tri, ctx->h_visit_tri.data(), bytes));
+    ctx->visit_ids_dirty = false;
+    return RTGL_OK;
+}
+
 // one frame, or the frames of a batch in one set of launches
 static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch)
 {
@@ -1463,13 +1483,7 @@ static int render_batch(rtgl_context *ctx, const std::vector<FrameParams> &batch
     if (ctx->visits_dirty) { int rc = rebuild_sphere_visits(ctx); if (rc) return rc; }
     if (ctx->tris_dirty) { int rc = rebuild_triangles(ctx); if (rc) return rc; }
     if (ctx->opt.rng_state) RCCHK(buf_ensure(ctx, ctx->d_rng, local_px(ctx) * sizeof(uint4)));
-    if ((ctx->opt.aov & RTGL_AOV_IDS) && ctx->visit_ids_dirty) {
-        const size_t bytes = ctx->h_visit_tri.size() * sizeof(uint32_t);
-        int rc = realloc_upload(ctx, ctx->d_visit_mesh, ctx->h_visit_mesh.data(), bytes);
-        if (!rc) rc = realloc_upload(ctx, ctx->d_visit_tri, ctx->h_visit_tri.data(), bytes);
-        if (rc) return rc;
-        ctx->visit_ids_dirty = false;
-    }
+    RCCHK(upload_visit_ids(ctx));
 
     const SceneView sc = scene_view(ctx);
     std::vector<FrameParams> frames(batch);
@@ -1824,6 +1838,21 @@ extern "C" void *rtgl_device_aov(rtgl_context *ctx, int plane)
     if (idx < 0) { ctx->error = "rtgl_device_aov: plane must be one RTGL_AOV_* bit"; return nullptr; }
     if (!aov_plane(ctx, idx)) { ctx->error = "rtgl_device_aov: this plane is not enabled (option \"aov\")"; return nullptr; }
     return aov_plane(ctx, idx);
+}
+
+// ---- guide pass (include/rtgl_amd.h, "guide pass"; kernel: rt_guides.hpp; host rules: rt_guides_plan.hpp) ---------------------------
+static_assert(rt_guides_plan::kOk == (int)RTGL_OK && rt_guides_plan::kErrInvalid == (int)RTGL_ERR_INVALID && rt_guides_plan::kErrState == (int)RTGL_ERR_STATE
+              && rt_guides_plan::kKernelSplit == (int)RTGL_KERNEL_WAVEFRONT_SPLIT && rt_guides_plan::kKernelSolo == (int)RTGL_KERNEL_WAVEFRONT_MFMA_SOLO, "the values of the header");
+
+#include "rt_guides_host.hpp"
+
+extern "C" int rtgl_guides_frame(rtgl_context *ctx)
+{
+    if (!ctx) return rt_guides_plan::refused(false, false, false, 0u).code;
+    ENTER(ctx);
+    const rt_guides_plan::Refusal refusal = rt_guides_plan::refused(true, !ctx->parts.empty(), ctx->have_params, (uint32_t)ctx->opt.aov);
+    if (refusal.why) return fail(ctx, refusal.code, refusal.why);
+    return guides_pass(ctx);
 }
 
 // ---- rtgl_denoise: edge-avoiding a-trous filter guided by the first-hit planes (rt_denoise.hpp) --------

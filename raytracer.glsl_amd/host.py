@@ -62,7 +62,7 @@ ABI_SYMBOLS = [
     "rtgl_bind_device_image", "rtgl_set_stream", "rtgl_get_counters", "rtgl_read_rng_state",
     "rtgl_set_option", "rtgl_get_option", "rtgl_last_frame_ms", "rtgl_last_frame_timing",
     "rtgl_accumulated_timing", "rtgl_timing_reset", "rtgl_create_multi", "rtgl_device_count", "rtgl_gather_tiles",
-    "rtgl_read_aov", "rtgl_device_aov",
+    "rtgl_read_aov", "rtgl_device_aov", "rtgl_guides_frame",
     "rtgl_denoise_defaults", "rtgl_denoise", "rtgl_read_denoised_f32", "rtgl_device_denoised",
     "rtgl_denoise_guided_defaults", "rtgl_denoise_guided", "rtgl_read_denoise_variance_f32", "rtgl_device_denoise_variance",
     "rtgl_temporal_defaults", "rtgl_temporal_accumulate", "rtgl_temporal_reset", "rtgl_read_temporal_f32", "rtgl_device_temporal",
@@ -230,7 +230,7 @@ def load_library() -> C.CDLL:
         getattr(L, name).argtypes = [vp, vp, u32]
     L.rtgl_upload_envmap.argtypes = [vp, vp, i, i, i, i]
     L.rtgl_set_frame_params.argtypes = [vp, C.POINTER(CFrameParams)]
-    for name in ("rtgl_render_frame", "rtgl_synchronize", "rtgl_clear_image", "rtgl_local_rows"):
+    for name in ("rtgl_render_frame", "rtgl_guides_frame", "rtgl_synchronize", "rtgl_clear_image", "rtgl_local_rows"):
         getattr(L, name).argtypes = [vp]
     L.rtgl_read_image_f32.argtypes = [vp, vp]
     L.rtgl_read_image_u8.argtypes = [vp, vp, i]
@@ -406,6 +406,14 @@ class Context:
         if p is not None:
             self.set_params(p)
         self._chk(self.lib.rtgl_render_frame(self.h))
+        if sync:
+            self._chk(self.lib.rtgl_synchronize(self.h))
+
+    def guides_frame(self, p: FrameParams | None = None, sync: bool = True):
+        """One guide pass (rtgl_guides_frame): the camera rays' first hits folded into the enabled first-hit planes, and nothing else."""
+        if p is not None:
+            self.set_params(p)
+        self._chk(self.lib.rtgl_guides_frame(self.h))
         if sync:
             self._chk(self.lib.rtgl_synchronize(self.h))
 
@@ -1129,6 +1137,19 @@ class HeadlessRenderer(FrameLoop):
         p = self.next_frame()
         self.ctx.render(p, sync=sync)
         return p
+
+    def render_guides(self, passes: int = 1) -> list:
+        """`passes` guide passes (Context.guides_frame) with the uniforms of session_frame(): one rand() per pass, like every frame, the
+        frame count is not advanced and a pending reset_buffer() stays pending, as in renderer.h.  Returns the parameters of the passes,
+        in order.  The planes then hold the mean of these passes and of whatever they held since their last restart."""
+        if passes < 1:
+            raise ValueError("render_guides: passes must be >= 1")
+        used = []
+        for _ in range(passes):
+            used.append(self.session_frame())
+            self.ctx.guides_frame(used[-1], sync=False)
+        self.ctx.synchronize()
+        return used
 
     def run(self, frames: int):
         for _ in range(frames):
